@@ -11,13 +11,19 @@ per rank, replicated weights, one gradient mean per step over R
     python bench.py --gpus 8 ...          # starts the 8 ranks itself (python -m torch.distributed.run, 127.0.0.1) before touching a GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line: `metric`, `value` (utterances/s over the timed steps), `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+(wall milliseconds of one timed step), the workload in `config`.  A plain run does only that: set up, warm up, time `--steps` steps, print.
+`--dump-outputs DIR` writes what the last timed step computed as float32 .npy files (see dump_outputs); inputs and weights are seeded,
+so two builds run with the same arguments compare output for output.
+`--full` adds everything else, each measured after the timed steps (and after the dump):
+  config.secondary -- the same step without clip+AdamW, batch 8, preset A (single GPU; `--no-secondary` drops them);
   roofline     -- the dominant kernel (gemm_nt, bf16 MFMA): algorithmic FLOPs / launch time measured live with HIP events
                   on the launch stream in a separate instrumented pass (the timed region itself is not instrumented);
                   `traffic` = HBM bytes per launch from the committed rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes of this same
                   command, used only while the kernel sources and the workload still match what was profiled (else null);
   cpu_baseline -- the CPU oracle (oracle/tav_oracle.py, fp32 PyTorch restatement of the reference path, kind "port") timed
                   on this box's host cores on a bounded sample (rank 0, N = 1 only).
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
 A failed hipGraph capture is fatal (exit code 3): an eager fallback would silently time a different launch mode.
 """
 import argparse
@@ -87,17 +93,21 @@ FAMILY_KERNELS = {"attention": ("attn_fwd_kernel", "attn_bwd_dq_kernel", "attn_b
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="after the headline: secondary measurements, roofline pass, CPU baseline (each can be "
+                    "dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; rank 0)")
     ap.add_argument("--global-batch", type=int, default=GLOBAL_BATCH, help="utterances per step over ALL GPUs (strong scaling: 32/N per rank)")
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="> 0: weak-scaling variant, this many utterances on every GPU")
     ap.add_argument("--preset", default="B")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8", "fp8-all", "fp8-wgrad8"],
                     help="fp8: e4m3 operands (per-tensor scales) in the linear layers of every transformer block, the rest as bf16 (BASELINE config 5)")
     ap.add_argument("--no-optimizer", action="store_true", help="time fwd+loss+bwd(+all-reduce) only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (fwd+bwd only, batch 8, preset A)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline pass")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary measurements (fwd+bwd only, batch 8, preset A)")
     ap.add_argument("--cpu-protocol", default="bounded", choices=["bounded", "full"],
                     help="bounded: b=1, 2 warm-ups, median of 5 (~25 s); full: BASELINE.md §3, b in {1, 8} (several minutes)")
     ap.add_argument("--bucket-mb", type=float, default=48.0)
@@ -122,6 +132,10 @@ def parse_args():
                          "GPU, profiles/r04_ab_ddp.txt) but a captured collective has never met a second rank on this project, and a hang at N = 8 "
                          "would cost the whole scaling measurement -- so the path that has run with two ranks stays the default")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_secondary = args.no_roofline = args.no_cpu_baseline = True
     if args.shard_optimizer and args.ddp_mode == "single":
         ap.error("--shard-optimizer runs as the graph chain (its exchanges are torch.distributed calls between the graphs): not with --ddp-mode single")
     return args
@@ -215,6 +229,44 @@ def cpu_baseline(torch, synthetic, cfg, pre, model, protocol, gpu_loss=None):
     return out
 
 
+DUMP_PARAM_ELEMS = 8192               # per parameter tensor in params_sample.npy
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, last, params):
+    """--dump-outputs: what the last timed step computed, as float32 arrays in `path`/<name>.npy (rank 0):
+      loss          [1]      the step's loss;
+      logits        [b, 7]   TAVForMAE's output for this rank's rows;
+      grad_norm     [1]      the total gradient norm clip_grad_norm_ saw (single-GPU steps; the data-parallel chain keeps it inside its graphs);
+      params_sample [n]      the parameters the step left behind, in TrainStep order: every element of a tensor up to DUMP_PARAM_ELEMS
+                             elements, beyond that a fixed sample of DUMP_PARAM_ELEMS (seeded, sorted indices -- the same for every build).
+    Returns the names written."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    if last.get("logits") is not None:
+        arrays["logits"] = last["logits"].detach()
+    if last.get("grad_norm") is not None:
+        arrays["grad_norm"] = last["grad_norm"].detach().reshape(1)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    parts = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_PARAM_ELEMS:
+            idx = torch.randint(flat.numel(), (DUMP_PARAM_ELEMS,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float())
+    arrays["params_sample"] = torch.cat(parts)
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return list(arrays)
+
+
 def main():
     args = parse_args()
     if args.profile_serial:
@@ -298,12 +350,20 @@ def main():
     stepper = TrainStep(model, pre, CrossEntropyLoss(), lr=1e-6, weight_decay=1e-4, clip=1.0, bucket_mb=args.bucket_mb,
                         reduce_dtype=torch.bfloat16 if args.reduce_bf16 else None)
 
+    # --dump-outputs: tensors of the step besides its loss -- the forward's logits (held by a hook: no launch, no copy) and the gradient norm
+    # of clip_grad_norm_.  Cleared before a capture, so that only what the replays rewrite is dumped.
+    last, hook = {}, None
+    if args.dump_outputs:
+        hook = model.register_forward_hook(lambda m, i, o: last.__setitem__("logits", o.detach()))
+
     def one_step():
         loss = stepper.forward_backward(inp, labels, check="val", epoch=0, n_visual_true=n_true)
         if args.no_optimizer:
             stepper.opt.zero_grad()
         else:
-            stepper.update()
+            norm = stepper.update()
+            if args.dump_outputs:
+                last["grad_norm"] = norm
         return loss
 
     def fence():
@@ -336,6 +396,7 @@ def main():
             fence()
             engine.bump_weight_epoch()
             stepper.opt.zero_grad()
+            last.clear()
             fwd = lambda: stepper.forward_loss(inp, labels, check="val", epoch=0, n_visual_true=n_true)      # noqa: E731
             gstep = None
             if args.ddp_mode == "single":
@@ -357,6 +418,7 @@ def main():
             torch.cuda.synchronize()
             engine.bump_weight_epoch()                       # the operand casts must be part of the captured step
             stepper.opt.zero_grad()
+            last.clear()
             graph = torch.cuda.CUDAGraph()
             with runtime.capture(graph, work_stream):
                 static_loss = one_step()
@@ -399,6 +461,12 @@ def main():
         log(f"[rank {rank}] loss {final_loss} is not finite after the timed steps: the measurement is INVALID, refusing to print a benchmark line")
         torch.cuda.synchronize()
         os._exit(4)
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, loss, last, stepper.params)
+        log(f"[rank {rank}] outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}")
+    if hook is not None:
+        hook.remove()
+        last.clear()
 
     # ---- secondary measurements (single GPU): the same step without clip+AdamW (the metric's "fwd+bwd"), and batch 8 (BASELINE configs[1])
     secondary = {}
