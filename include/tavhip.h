@@ -323,6 +323,10 @@ int tav_cross_entropy(const float* logits, const int64_t* target, const float* c
 
 /* dropout with a counter-based RNG (models/tav.py:497-498): y = x * keep / (1-p); mask bytes saved for backward */
 int tav_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream);
+/* v7: tav_dropout_fwd with the seed read from DEVICE memory (*seed_state, one uint64 word) when the kernel runs -- bit-identical to
+ * tav_dropout_fwd(seed = *seed_state).  A hipGraph that captured this launch draws whatever seed the host wrote into the word before the
+ * replay; the backward is tav_dropout_bwd on the mask bytes. */
+int tav_dropout_fwd_dev(const float* x, float* y, uint8_t* mask, int64_t n, float p, const uint64_t* seed_state, uint64_t offset, void* stream);
 int tav_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, int64_t n, float p, void* stream);
 
 /* wav2vec2 feature encoder pieces (HF wav2vec2/modeling_wav2vec2.py:275-323,382-419) -- activations are kept

@@ -59,6 +59,5 @@ class BertAudioClassifier(nn.Module):
             _, t = self.bert(input_ids, text_attention_mask)
         feat = E.PoolNormCatFn.apply(B, (0, Sa), t, aud, self.bert_norm.weight, self.bert_norm.bias, self.aud_norm.weight, self.aud_norm.bias)
         p = self.dropout_p if check == "train" else 0.0
-        self._drop_calls += 1
-        seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._drop_calls) & 0xFFFFFFFFFFFFFFFF
+        seed, = runtime.dropout_seeds(self, "_drop_calls", draw=p > 0.0)        # (a device word under a capture)
         return E.HeadFn.apply(feat, p, seed, self.linear1.weight, self.linear1.bias)

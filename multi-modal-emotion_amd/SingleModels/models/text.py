@@ -2,7 +2,6 @@
 check == "train") -> Linear(768, output_dim), executed by libtavhip (BASELINE.json configs[0]).
 The reference builds the encoder with `BertModel.from_pretrained('j-hartmann/emotion-english-distilroberta-base')` (:48), a network
 fetch; here the geometry comes from the preset's "text" block (config.py) and weights are loaded by the caller."""
-import torch
 from torch import nn
 
 from ... import config as C
@@ -28,6 +27,5 @@ class BertClassifier(nn.Module):
             raise RuntimeError("BertClassifier runs on libtavhip (GPU) only; there is no CPU fallback")
         _, x = self.bert(input_id.to(dev), mask.to(dev))                                    # :58 (pooled output)
         p = self.dropout_p if check == "train" else 0.0                                      # :61-62
-        self._drop_calls += 1
-        seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._drop_calls) & 0xFFFFFFFFFFFFFFFF
+        seed, = runtime.dropout_seeds(self, "_drop_calls", draw=p > 0.0)        # (a device word under a capture)
         return E.HeadFn.apply(x, p, seed, self.linear.weight, self.linear.bias)              # :65

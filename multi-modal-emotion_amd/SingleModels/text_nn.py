@@ -51,6 +51,8 @@ def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
 
 def main(argv=None):
     args = arg_parse("Text", argv)
+    if args.graph:
+        raise SystemExit("--graph 1: graph mode exists for the tri-modal loop only (tav_nn); run this entrypoint with --graph 0")
     np.random.seed(args.seed)
     torch.random.manual_seed(args.seed)
     C.set_default_preset(args.preset)

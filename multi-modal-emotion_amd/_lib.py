@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TAV_LIB") or os.path.join(_HERE, "libtavhip.so")      # TAV_LIB: developer knob, A/B of two builds (tools/ab_build.sh)
 
 TAV_F32, TAV_BF16, TAV_FP8 = 0, 1, 2
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -123,6 +123,7 @@ _SIGS = {
     "tav_tanh_bwd": (C.c_int, [vp, vp, vp, i64, vp]),
     "tav_cross_entropy": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, f32, vp]),
     "tav_dropout_fwd": (C.c_int, [vp, vp, vp, i64, f32, C.c_uint64, C.c_uint64, vp]),
+    "tav_dropout_fwd_dev": (C.c_int, [vp, vp, vp, i64, f32, vp, C.c_uint64, vp]),
     "tav_dropout_bwd": (C.c_int, [vp, vp, vp, i64, f32, vp]),
     "tav_conv0_fwd": (C.c_int, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, vp]),
     "tav_conv0_bwd_w": (C.c_int, [vp, vp, i32, vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, vp]),

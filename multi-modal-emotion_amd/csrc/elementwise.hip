@@ -454,15 +454,26 @@ TAV_DEV uint64_t mix64(uint64_t x) {
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
 }
-__global__ void dropout_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, long n, float p, uint64_t seed,
-                                   uint64_t offset) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+TAV_DEV void dropout_one(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, long i, float p, uint64_t seed, uint64_t offset) {
     const uint64_t r = mix64(seed ^ mix64(offset + (uint64_t)i));
     const float u = (float)(r >> 40) * (1.f / 16777216.f);
     const bool keep = u >= p;
     mask[i] = keep ? 1 : 0;
     y[i] = keep ? x[i] / (1.f - p) : 0.f;
+}
+__global__ void dropout_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, long n, float p, uint64_t seed,
+                                   uint64_t offset) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    dropout_one(x, y, mask, i, p, seed, offset);
+}
+// ABI v7: the same draw with the seed read from device memory when the kernel runs, so that a captured launch takes the seed the host
+// wrote into that word before the replay instead of the one baked into the graph at capture time.
+__global__ void dropout_fwd_dev_kernel(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, long n, float p,
+                                       const uint64_t* __restrict__ seed_state, uint64_t offset) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    dropout_one(x, y, mask, i, p, seed_state[0], offset);
 }
 __global__ void dropout_bwd_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ mask, float* __restrict__ dx, long n, float p) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -845,6 +856,13 @@ extern "C" int tav_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t 
     if (!x || !y || !mask) return TAV_ERR_NULL;
     if (n <= 0 || p < 0.f || p >= 1.f) return TAV_ERR_SHAPE;
     hipLaunchKernelGGL(dropout_fwd_kernel, G1(n), x, y, mask, (long)n, p, seed, offset);
+    return tav_last_error();
+}
+extern "C" int tav_dropout_fwd_dev(const float* x, float* y, uint8_t* mask, int64_t n, float p, const uint64_t* seed_state, uint64_t offset,
+                                   void* stream) {
+    if (!x || !y || !mask || !seed_state) return TAV_ERR_NULL;
+    if (n <= 0 || p < 0.f || p >= 1.f) return TAV_ERR_SHAPE;
+    hipLaunchKernelGGL(dropout_fwd_dev_kernel, G1(n), x, y, mask, (long)n, p, seed_state, offset);
     return tav_last_error();
 }
 extern "C" int tav_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, int64_t n, float p, void* stream) {

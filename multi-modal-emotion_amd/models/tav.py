@@ -279,8 +279,7 @@ class TAVForMAE(nn.Module):
                 runtime.stream_wait(main, st)
                 ten.record_stream(main)
         p_drop = self.dropout_p if check == "train" else 0.0
-        self._drop_calls += 1
-        seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._drop_calls) & 0xFFFFFFFFFFFFFFFF
+        seed, = runtime.dropout_seeds(self, "_drop_calls", draw=p_drop > 0.0)        # (a device word under a capture)
         return E.TailFn.apply(av.reshape(B * Sf, 768), t, aud, vid, B, Sf, Sa, Sv, p_drop, seed,
                               self.rand_norm.weight, self.rand_norm.bias, self.bert_norm.weight, self.bert_norm.bias,
                               self.aud_norm.weight, self.aud_norm.bias, self.vid_norm.weight, self.vid_norm.bias,

@@ -674,9 +674,16 @@ def cross_entropy(logits, target, class_weight=None, grad_scale=1.0, want_grad=T
 
 
 def dropout_fwd(x, p, seed, offset):
+    """seed: an int (passed by value), or a one-word int64 device tensor that the kernel reads when it runs (runtime.dropout_seeds under a
+    hipGraph capture: the host rewrites the word before every replay)."""
     y = torch.empty_like(x)
     mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    check(lib().tav_dropout_fwd(ptr(x), ptr(y), ptr(mask), x.numel(), p, seed, offset, stream()), "dropout_fwd")
+    if isinstance(seed, torch.Tensor):
+        if not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() != 1:
+            raise ValueError(f"dropout_fwd: a device seed is one int64 word on the GPU, got {seed.dtype} x {seed.numel()} on {seed.device}")
+        check(lib().tav_dropout_fwd_dev(ptr(x), ptr(y), ptr(mask), x.numel(), p, ptr(seed), offset, stream()), "dropout_fwd_dev")
+    else:
+        check(lib().tav_dropout_fwd(ptr(x), ptr(y), ptr(mask), x.numel(), p, seed, offset, stream()), "dropout_fwd")
     return y, mask
 
 

@@ -77,6 +77,7 @@ class FusedAdamW:
         # the partials of their own range and still reproduce this optimizer bit for bit.
         self.norm_buffers = None
         self._norm_tables = None
+        self.generation = 0          # bumped by load_state_dict (new moment tensors): a captured step that points at the old ones is stale
 
     def zero_grad(self, set_to_none=True):
         """set_to_none=True (torch >= 2.0 default): drop the gradients, the next step() skips those parameters.  set_to_none=False (the default of
@@ -175,6 +176,21 @@ class FusedAdamW:
     def step(self):
         return self.clip_and_step(None)
 
+    def sync_lr(self):
+        """Bring the device-side learning rate to self.lr OUTSIDE clip_and_step: a replayed step never runs its host code, so the graphed training
+        loop calls this before every replay (and before a capture, which then records no upload of its own).  A fill kernel carries the value
+        as an argument: nothing on the host can be overwritten before the device has read it."""
+        if self._tables is None:
+            raise RuntimeError("FusedAdamW.sync_lr: no optimizer step has run yet")
+        if self._lr_host != self.lr:
+            self._scal[4:5].fill_(self.lr)
+            self._lr_host = self.lr
+
+    def captures_released(self):
+        """Every hipGraph that captured this optimizer's step has been destroyed: the pinned upload slots those captures took may be reused."""
+        for t in self._tables or ():
+            t.cap_used = 0
+
     # ---- checkpoint format of torch.optim.AdamW (reference utils/global_functions.py:199-258 saves optimizer.state_dict() into best.pt and
     # reloads it into a fresh AdamW over the same parameter list): {'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]}
     def state_dict(self):
@@ -196,6 +212,7 @@ class FusedAdamW:
         g0 = groups[0]
         self.lr, self.betas, self.eps, self.weight_decay = g0["lr"], tuple(g0["betas"]), g0["eps"], g0["weight_decay"]
         self._lr_host = None
+        self.generation += 1
         steps = set()
         for pos, i in enumerate(idx):
             st = sd["state"].get(i)

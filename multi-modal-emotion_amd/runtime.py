@@ -112,18 +112,30 @@ def stream_wait(waiter, producer, event=None):
 
 class capture:
     """`with runtime.capture(graph, stream, **kw):` = torch.cuda.graph(graph, stream=stream, **kw) with the guard above armed: `stream` is the
-    origin; streams handed out by branch_streams() / front_streams() inside the block (or passed as `branches=`) are its branches."""
+    origin; streams handed out by branch_streams() / front_streams() inside the block (or passed as `branches=`) are its branches.
+    Dropout drawn inside the block reads its seeds from device words that live as long as the graph does (see dropout_seeds): a plain
+    graph.replay() repeats the draws that followed the capture, capture.replay() takes fresh ones as eager calls would."""
 
     def __init__(self, graph, stream, branches=(), **kw):
         import torch
         self._cm = torch.cuda.graph(graph, stream=stream, **kw)
+        self.graph = graph
         self._origin, self._branches = stream, list(branches)
+        self.seeds = []              # dropout draws the captured work takes, in call order (dropout_seeds)
+        self.seed_words = None
 
     def __enter__(self):
         global _capture
+        import torch
         if _capture is not None:
             raise RuntimeError("runtime.capture: a capture is already in progress in this process")
-        _capture = {"origin": self._origin, "branches": list(self._branches)}
+        # allocated BEFORE the capture: a buffer allocated inside it comes from the graph's pool, where memory that earlier nodes of the
+        # same graph used is handed out again -- a replay would overwrite the host-written seeds before the dropout kernels read them.
+        # A capture that draws nothing (check="val", the optimizer's graphs) hands the buffer on to the next one (__exit__).
+        dev = self._origin.device
+        words = _spare_words.pop(str(dev), None)
+        self.seed_words = words if words is not None else torch.zeros(SEED_WORDS, dtype=torch.int64, device=dev)
+        _capture = {"origin": self._origin, "branches": list(self._branches), "seeds": self.seeds, "words": self.seed_words, "used": 0}
         try:
             return self._cm.__enter__()
         except BaseException:
@@ -132,10 +144,36 @@ class capture:
 
     def __exit__(self, *exc):
         global _capture
+        import torch
+        used = _capture["used"] if _capture is not None else 0
         try:
             return self._cm.__exit__(*exc)
         finally:
             _capture = None
+            if used == 0:
+                _spare_words[str(self._origin.device)] = self.seed_words
+                self.seed_words = None
+            elif exc[0] is None:
+                # the captured kernels read these words at every replay: they live as long as the graph object, whether or not the caller
+                # keeps this capture object, and start out with the seeds of the draws that followed the capture (what a plain
+                # graph.replay() then repeats); capture.replay() rewrites them before each replay
+                try:
+                    self.graph._tav_seed_words = self.seed_words
+                except AttributeError:
+                    _kept_words.append(self.seed_words)
+                with torch.cuda.stream(self._origin):
+                    write_seeds(self.seeds, advance=False)
+
+    def advance_seeds(self):
+        """Take the dropout draws of one replay: every module that drew under the capture advances its counter as its eager call would
+        have, and its device seed words get the seeds of those draws.  Enqueued on the current stream (fill kernels: the value travels
+        as a kernel argument, no host staging buffer that a later step could overwrite before the copy ran)."""
+        write_seeds(self.seeds, advance=True)
+
+    def replay(self):
+        """advance_seeds() + the graph's replay, on the current stream (which must be the stream the graph was captured on)."""
+        self.advance_seeds()
+        self.graph.replay()
 
 
 class guard_only:
@@ -143,14 +181,76 @@ class guard_only:
 
     def __init__(self, origin, branches=()):
         self._origin, self._branches = origin, list(branches)
+        self.seeds = []
 
     def __enter__(self):
         global _capture
-        _capture = {"origin": self._origin, "branches": list(self._branches)}
+        import torch
+        _capture = {"origin": self._origin, "branches": list(self._branches), "seeds": self.seeds,
+                    "words": torch.empty(SEED_WORDS, dtype=torch.int64), "used": 0}
 
     def __exit__(self, *exc):
         global _capture
         _capture = None
+
+
+# ---- dropout seeds.  Every dropout site keeps a per-module call counter k on the host (the heads of TAVForMAE, BertClassifier and the
+# text+audio model: `_drop_calls`, one draw per forward; TransformerEncoder: `_calls`, one draw per layer) and draw k uses the seed
+# initial_seed + GOLDEN * k.  Eager, the counter advances and the seed goes to the kernel by value.  Under a capture the counter does NOT
+# advance (the capture runs nothing); the site draws from device words instead and is recorded on the capture, whose advance_seeds()
+# -- called before each replay -- advances the counter and writes the words.  So the k-th forward call of a module gets the same masks
+# whether call k ran eagerly or as a replay, in any interleaving of the two.
+GOLDEN = 0x9E3779B97F4A7C15
+_U64 = 0xFFFFFFFFFFFFFFFF
+SEED_WORDS = 256             # device seed words per capture (one per dropout draw the captured work takes)
+_spare_words = {}            # device -> a seed-word buffer no graph reads (left by a capture that drew nothing)
+_kept_words = []             # seed words of graphs that take no attributes: kept for the life of the process
+
+
+def dropout_seed(k):
+    """Seed of a module's k-th draw (1-based)."""
+    import torch
+    return (torch.initial_seed() + GOLDEN * k) & _U64
+
+
+def _as_i64(v):
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def dropout_seeds(owner, attr, n=1, draw=True):
+    """Seeds of the next `n` draws of `owner` (counter attribute `attr`).  Outside a capture: advances the counter by n and returns n ints.
+    Under a capture: leaves the counter alone, records the site on the capture and returns n one-word int64 device tensors (views of the
+    capture's seed words) that ops.dropout_fwd reads when the kernel runs -- or n placeholders when `draw` is False (p = 0: the counter still
+    has to advance per replay, as it does per eager call, but no kernel reads a seed)."""
+    if _capture is None:
+        k0 = getattr(owner, attr)
+        setattr(owner, attr, k0 + n)
+        return [dropout_seed(k0 + j + 1) for j in range(n)]
+    words = None
+    if draw:
+        used = _capture["used"]
+        if used + n > _capture["words"].numel():
+            raise RuntimeError(f"runtime.capture: more than {SEED_WORDS} dropout draws in one capture (raise runtime.SEED_WORDS)")
+        words = _capture["words"][used:used + n]
+        _capture["used"] = used + n
+    _capture["seeds"].append((owner, attr, n, words))
+    return [words[j:j + 1] for j in range(n)] if draw else [0] * n
+
+
+def write_seeds(sites, advance=True):
+    """Write the seeds of every recorded site's next draws into its words; advance=True also moves the counters past them (a replay takes
+    those draws), advance=False only initialises the words (end of a capture)."""
+    for owner, attr, n, words in sites:
+        k0 = getattr(owner, attr)
+        if advance:
+            setattr(owner, attr, k0 + n)
+        if words is not None:
+            for j in range(n):
+                words[j:j + 1].fill_(_as_i64(dropout_seed(k0 + j + 1)))
+
+
+def advance_seeds(sites):
+    write_seeds(sites, advance=True)
 
 
 def share_with(stream, *tensors):

@@ -46,7 +46,8 @@ def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
     model = TAVForMAE(model_param).to(device)
     PREFormer = PreFormer().to(device)
     model, PREFormer = train_tav_network(model, PREFormer, dl_train, dl_val, criterion, param_dict["lr"], param_dict["epoch"], param_dict["weight_decay"],
-                                         param_dict["T_max"], Metric, param_dict["patience"], param_dict["clip"], es, None)
+                                         param_dict["T_max"], Metric, param_dict["patience"], param_dict["clip"], es, None,
+                                         graphs=bool(param_dict.get("graph", 0)))
     evaluate_tav(model, PREFormer, dl_test, Metric)
     return model, PREFormer
 
@@ -63,7 +64,7 @@ def main(argv=None):
     param_dict = {"epoch": args.epoch, "patience": args.patience, "lr": args.learning_rate, "clip": args.clip, "batch_size": args.batch_size,
                   "weight_decay": args.weight_decay, "model": args.model, "T_max": args.T_max, "seed": args.seed, "label_task": args.label_task,
                   "mask": args.mask, "loss": args.loss, "beta": args.beta, "epoch_switch": args.epoch_switch, "weights": weights,
-                  "label2id": {v: k for k, v in id2label.items()}, "id2label": id2label}
+                  "label2id": {v: k for k, v in id2label.items()}, "id2label": id2label, "graph": args.graph}
     model_param = {"output_dim": args.output_dim, "dropout": args.dropout, "early_div": args.early_div, "num_layers": args.num_layers,
                    "learn_PosEmbeddings": args.learn_PosEmbeddings}
     small = cfg["video"]["image"] != 224

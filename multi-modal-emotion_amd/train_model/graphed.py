@@ -1,0 +1,182 @@
+"""Graph mode of the TAV training loop (`train_tav_network(..., graphs=True)`): each training batch replays a captured step -- forward,
+loss, backward, clip_grad_norm_, AdamW, weight re-casts -- instead of launching its ~3000 kernels one by one from Python.  Results equal the
+eager loop's bit for bit.
+
+What is captured: tav_train._statistics (PreFormer + TAVForMAE + criterion, Metric=None) on static input buffers, the division by the dialogue
+length (grad_accum) as a multiplication by a device scalar, backward and TrainStep.update().  What runs between replays, on the host:
+  * the batch is copied into the static buffers; the dialogue-length scale and the learning rate the scheduler set are written to their device
+    words (fill kernels: the value is a kernel argument, no host staging buffer can be overwritten before the device read it);
+  * the dropout sites advance their call counters and write the seeds of this replay's draws (runtime.capture.replay);
+  * the weight-cast cache is told the parameters moved (engine.bump_weight_epoch), so an eager validate() re-casts;
+  * metrics and the running loss are taken from the static logits / loss -- one host sync per step, the reference's per-batch loss.item().
+A batch whose signature (input shapes and dtypes, video tokens per row, loss branch, loop kind) has not been seen in this epoch runs the
+eager step -- the same code as graphs=False -- and is then captured (at most `max_graphs` per epoch; later new signatures stay eager).
+Graphs are freed at the end of every epoch and whenever the optimizer's state was reloaded (load_model builds new moment tensors).
+"""
+import weakref
+
+import numpy as np
+import torch
+
+from .. import engine, runtime
+from . import tav_train as T
+
+
+def _recip32(n):
+    """1 / n as torch's CUDA division by a Python scalar computes it (float32 reciprocal, then a multiply): the replay multiplies by this,
+    which reproduces the eager `loss / accum_iter` and its backward bit for bit."""
+    return float(np.float32(1.0) / np.float32(n))
+
+
+class _Captured:
+    """One captured step and its static tensors."""
+
+    def __init__(self, cap, static_in, static_label, scale, loss, logits, label):
+        self.cap, self.static_in, self.static_label, self.scale = cap, static_in, static_label, scale
+        self.loss, self.logits, self.label = loss, logits, label
+
+    def feed(self, input, label):
+        for d, sd in zip(input, self.static_in):
+            if sd is not None:
+                for k, t in sd.items():
+                    t.copy_(d[k], non_blocking=True)
+        self.static_label.copy_(label, non_blocking=True)
+
+    def set_scale(self, v):
+        self.scale.fill_(v)
+
+    def replay(self):
+        self.cap.replay()
+
+    def release(self):
+        self.cap.graph.reset()
+        self.cap = self.static_in = self.static_label = self.scale = self.loss = self.logits = self.label = None
+
+
+class GraphedSteps:
+    """The training step of not_grad_accum / grad_accum for one TrainStep, replayed from hipGraphs where the batch allows it."""
+
+    def __init__(self, stepper, max_graphs=2):
+        if stepper.reducer is not None:
+            raise ValueError("train_tav_network(graphs=True) does not support data-parallel training yet (TrainStep has a gradient reducer); "
+                             "run with graphs=False, or use ddp.GraphedStep")
+        if runtime.ctx().pol.fp8:
+            raise ValueError(f"train_tav_network(graphs=True) supports the bf16 and fp32 policies, not {runtime.precision()!r}: the fp8 scale "
+                             "roll-over runs on the host after every step")
+        self.stepper, self.max_graphs = stepper, max_graphs
+        self.graphs = {}
+        self._generation = stepper.opt.generation
+        self.eager_steps = self.captures = self.replays = 0
+        self._nv_seen = {}
+
+    # ---- what makes a batch replayable by a graph
+    def _n_visual(self, input):
+        """Video tokens per row (every row must keep the same number; None if they differ -- the eager step then raises as it always did).
+        A mask on the device costs a host read: remembered per tensor object (weak reference) and version, so batches cycled on the
+        device are counted once."""
+        vm = input[2]["attention_mask"]
+        hit = self._nv_seen.get(id(vm))
+        if hit is not None and hit[0]() is vm and hit[1] == vm._version:
+            return hit[2]
+        c = vm.sum(1).cpu()
+        nv = int(c[0]) if c.numel() and bool((c == c[0]).all()) else None
+        if vm.is_cuda:
+            if len(self._nv_seen) >= 64:
+                self._nv_seen.clear()
+            self._nv_seen[id(vm)] = (weakref.ref(vm), vm._version, nv)
+        return nv
+
+    def signature(self, input, label, epoch, accum):
+        nv = self._n_visual(input)
+        if nv is None:
+            return None
+        crit = self.stepper.criterion
+        branch = (epoch % crit.epoch_switch == 0) if hasattr(crit, "epoch_switch") else None      # NewCrossEntropyLoss: weighted or not
+        shapes = tuple(None if d is None else tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(d.items())) for d in input)
+        return (shapes, (tuple(label.shape), label.dtype), nv, "train", branch, bool(accum))
+
+    # ---- one training step
+    def step(self, input, label, epoch, Metric, accum_iter=None):
+        """-> the batch loss as a float (what the loops add to total_loss_train).  accum_iter: grad_accum's divisor, None in not_grad_accum."""
+        if self.stepper.opt.generation != self._generation:
+            self.invalidate()                    # optimizer state reloaded: captured pointer tables are stale
+        sig = self.signature(input, label, epoch, accum_iter is not None)
+        g = self.graphs.get(sig) if sig is not None else None
+        if g is not None:
+            return self._replay(g, input, label, Metric, accum_iter)
+        v = self._eager(input, label, epoch, Metric, accum_iter)
+        if sig is not None and len(self.graphs) < self.max_graphs:
+            self.graphs[sig] = self._capture(input, label, epoch, accum_iter is not None, sig[2])
+            self.captures += 1
+        return v
+
+    def _eager(self, input, label, epoch, Metric, accum_iter):
+        """Exactly the eager loop's step (tav_train.not_grad_accum / grad_accum without a reducer)."""
+        st = self.stepper
+        loss = T.get_statistics(input, label, st.model, st.pre, st.criterion, Metric, check="train", epoch=epoch)
+        if accum_iter is not None:
+            loss = loss / accum_iter
+        v = loss.item()
+        loss.backward()
+        st.update()
+        self.eager_steps += 1
+        return v
+
+    def _replay(self, g, input, label, Metric, accum_iter):
+        g.feed(input, label)
+        if accum_iter is not None:
+            g.set_scale(_recip32(accum_iter))
+        self.stepper.opt.sync_lr()               # the scheduler moved opt.lr after the last step; the replay reads the device copy
+        g.replay()                               # (advances the dropout counters and writes this replay's seeds first)
+        engine.bump_weight_epoch()               # the replayed AdamW moved the weights behind the cast cache's back
+        if Metric is not None:
+            Metric.update_metrics(torch.argmax(g.logits, dim=1), g.label)
+        self.replays += 1
+        return g.loss.item()
+
+    def _capture(self, input, label, epoch, accum, n_visual_true):
+        """Capture the step on the current stream (the one the loop runs on).  Runs right after an eager step of the same signature: the
+        optimizer's moments exist, and the capture itself executes nothing -- no dropout draw, no update is consumed."""
+        st = self.stepper
+        dev = torch.device("cuda", torch.cuda.current_device())
+        static_in = [None if d is None else {k: v.to(dev, copy=True) for k, v in d.items()} for d in input]
+        static_label = label.to(dev, copy=True)
+        scale = torch.ones((), dtype=torch.float32, device=dev) if accum else None
+        st.opt.sync_lr()                         # (so that the captured AdamW records no learning-rate upload of its own)
+        engine.bump_weight_epoch()               # the operand casts must be part of the captured step
+        graph = torch.cuda.CUDAGraph()
+        cap = runtime.capture(graph, torch.cuda.current_stream())
+        with cap:
+            loss, logits, lab = T._statistics(static_in, static_label, st.model, st.pre, st.criterion, None, check="train", epoch=epoch,
+                                              n_visual_true=n_visual_true)
+            if scale is not None:
+                loss = loss * scale
+            loss.backward()
+            st.update()
+        return _Captured(cap, static_in, static_label, scale, loss.detach(), logits.detach(), lab)
+
+    def invalidate(self):
+        """Free every captured step (end of an epoch, reloaded optimizer state)."""
+        if self.graphs:
+            if torch.cuda.is_initialized():
+                torch.cuda.synchronize()         # (epoch ends and reloads only) the last replays have finished reading their pinned uploads
+            for g in self.graphs.values():
+                g.release()
+            self.graphs.clear()
+            self.stepper.opt.captures_released()
+        self._generation = self.stepper.opt.generation
+
+
+def run_graphed(train_epochs, stepper, model, PREFormer, *args, max_graphs=2):
+    """train_tav_network's epochs in graph mode: warm-up, captures, replays, eager fallbacks and validate() all run on ONE side stream (autograd
+    ties each parameter's gradient accumulation to the stream of its first backward, and a capture cannot use the legacy default stream)."""
+    graphs = GraphedSteps(stepper, max_graphs=max_graphs)
+    caller = torch.cuda.current_stream()
+    work = torch.cuda.Stream()
+    work.wait_stream(caller)
+    try:
+        with torch.cuda.stream(work):
+            return train_epochs(stepper, model, PREFormer, *args, graphs=graphs)
+    finally:
+        graphs.invalidate()
+        caller.wait_stream(work)

@@ -50,6 +50,11 @@ class CosineWarmRestarts:
 
 
 def get_statistics(input, label, model, PREFormer, criterion, Metric, check="train", epoch=None, n_visual_true=None):
+    return _statistics(input, label, model, PREFormer, criterion, Metric, check, epoch, n_visual_true)[0]
+
+
+def _statistics(input, label, model, PREFormer, criterion, Metric, check="train", epoch=None, n_visual_true=None):
+    """get_statistics -> (batch loss, logits, labels as int64 on the device): the captured step of graphed.py keeps the last two for the metrics."""
     device = "cuda"
     batch_size = len(label)
     text, audio_features, video_embeds = input[0], input[1], input[2]
@@ -69,7 +74,7 @@ def get_statistics(input, label, model, PREFormer, criterion, Metric, check="tra
     batch_loss = None
     if criterion is not None:
         batch_loss = criterion(output, label, epoch=epoch if epoch is not None else 1)
-    return batch_loss
+    return batch_loss, output, label
 
 
 class TrainStep:
@@ -132,17 +137,21 @@ def _save_if_better(val_loss, prev_val_loss, model, PREFormer, stepper, criterio
     return prev_val_loss, PATIENCE_ITER == patience
 
 
-def not_grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path=None):
-    """reference :52-83: one optimisation step per batch."""
+def not_grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path=None,
+                   graphs=None):
+    """reference :52-83: one optimisation step per batch.  graphs: a graphed.GraphedSteps that takes the step instead (replays of a captured one)."""
     iters = len(train_dataloader)
     total_loss_train = 0.0
     for batch_idx, (train_input, train_label) in enumerate(train_dataloader):
-        loss = get_statistics(train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch)
-        total_loss_train += loss.item()
-        loss.backward()
-        if stepper.reducer is not None:
-            stepper.reducer.finish()
-        stepper.update()
+        if graphs is not None:
+            total_loss_train += graphs.step(train_input, train_label, epoch, Metric)
+        else:
+            loss = get_statistics(train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch)
+            total_loss_train += loss.item()
+            loss.backward()
+            if stepper.reducer is not None:
+                stepper.reducer.finish()
+            stepper.update()
         scheduler.step(epoch + batch_idx / iters)
         if ((batch_idx + 1) % log_val == 0) or (batch_idx + 1 == iters):
             log(Metric, total_loss_train / iters, "train")
@@ -153,7 +162,8 @@ def not_grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, cr
     return prev_val_loss
 
 
-def grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path=None):
+def grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path=None,
+               graphs=None):
     """reference :87-119, the dialogue-level variant used on epochs with epoch % epoch_switch != 0.  Kept with its quirk: the loss is
     divided by the dialogue length (`dataset.retGradAccum(i)` -> (accum_iter, accum_sum)) but the optimizer still steps -- and the
     gradients are zeroed -- after EVERY batch (:96-100), so the extra, unclipped `optimizer.step()` at a dialogue end (:102-106) runs on zeroed
@@ -164,17 +174,21 @@ def grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criter
         zero TENSORS, so AdamW still runs -- weights decay by (1 - lr * wd), both moments shrink by their betas, the step counter advances and
         the parameters move along the remaining momentum (`TrainStep(zero_grad_like_torch_1_10=True)` /
         `train_tav_network(..., zero_grad_like_torch_1_10=True)`).
-    Both readings are tested (tests/test_abi_and_host.py on the call sequence, tests/test_model_gpu.py against torch.optim.AdamW)."""
+    Both readings are tested (tests/test_abi_and_host.py on the call sequence, tests/test_model_gpu.py against torch.optim.AdamW).
+    graphs: as in not_grad_accum; the division by the dialogue length is then a device scalar the replay reads."""
     iters = len(train_dataloader)
     total_loss_train = 0.0
     for batch_idx, (train_input, train_label) in enumerate(train_dataloader):
         accum_iter, accum_sum = train_dataloader.dataset.retGradAccum(i=batch_idx)
-        loss = get_statistics(train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch) / accum_iter
-        total_loss_train += loss.item()
-        loss.backward()
-        if stepper.reducer is not None:
-            stepper.reducer.finish()
-        stepper.update()
+        if graphs is not None:
+            total_loss_train += graphs.step(train_input, train_label, epoch, Metric, accum_iter=accum_iter)
+        else:
+            loss = get_statistics(train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch) / accum_iter
+            total_loss_train += loss.item()
+            loss.backward()
+            if stepper.reducer is not None:
+                stepper.reducer.finish()
+            stepper.update()
         scheduler.step(epoch + batch_idx / iters)
         if ((batch_idx + 1) % accum_sum == 0) or (batch_idx + 1 == iters):
             stepper.update(clip=False)           # reference :103: optimizer.step() without clip_grad_norm_; no-op or a momentum / decay step (docstring)
@@ -189,20 +203,38 @@ def grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criter
 
 
 def one_epoch(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, epoch_switch, patience, Metric, prev_val_loss,
-              path=None, log_val=2400):
-    """reference :133-144: alternate the two loops by epoch parity, then reload the best checkpoint of the run (:143)."""
+              path=None, log_val=2400, graphs=None):
+    """reference :133-144: alternate the two loops by epoch parity, then reload the best checkpoint of the run (:143).  graphs (graph mode): the
+    epoch's captured steps are freed at its end -- the next epoch has the other loop and loss branch, and the reload replaces the optimizer's
+    moment tensors that a captured step points at."""
     loop = not_grad_accum if (epoch % epoch_switch == 0 or not hasattr(train_dataloader.dataset, "retGradAccum")) else grad_accum
-    prev_val_loss = loop(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path)
+    if graphs is None:
+        prev_val_loss = loop(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path)
+    else:
+        prev_val_loss = loop(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path,
+                             graphs=graphs)
+        graphs.invalidate()
     if path is not None and os.path.exists(checkpoint_file(path)):
         load_model(model, PREFormer, stepper.opt, criterion, path)
     return prev_val_loss
 
 
 def train_tav_network(model, PREFormer, train_dataloader, val_dataloader, criterion, learning_rate, epochs, weight_decay, T_max, Metric, patience, clip,
-                      epoch_switch, checkpoint=None, path=None, log_val=2400, zero_grad_like_torch_1_10=False):
+                      epoch_switch, checkpoint=None, path=None, log_val=2400, zero_grad_like_torch_1_10=False, graphs=False):
     """reference :147-164.  `path` (None = keep nothing on disk) replaces the cluster path hard-coded at :137; `checkpoint` is a loaded
-    best.pt dict whose optimizer / scheduler state resumes the run (:152-155)."""
+    best.pt dict whose optimizer / scheduler state resumes the run (:152-155).  graphs=True: every training batch whose shapes match an
+    earlier one of the epoch replays a captured step (graphed.py; same results bit for bit); the whole run then executes on one side stream."""
     stepper = TrainStep(model, PREFormer, criterion, lr=learning_rate, weight_decay=weight_decay, clip=clip, zero_grad_like_torch_1_10=zero_grad_like_torch_1_10)
+    if graphs:
+        from .graphed import run_graphed
+        return run_graphed(_train_epochs, stepper, model, PREFormer, train_dataloader, val_dataloader, criterion, epochs, T_max, Metric, patience,
+                           epoch_switch, checkpoint, path, log_val)
+    return _train_epochs(stepper, model, PREFormer, train_dataloader, val_dataloader, criterion, epochs, T_max, Metric, patience, epoch_switch, checkpoint,
+                         path, log_val)
+
+
+def _train_epochs(stepper, model, PREFormer, train_dataloader, val_dataloader, criterion, epochs, T_max, Metric, patience, epoch_switch, checkpoint, path,
+                  log_val, graphs=None):
     scheduler = CosineWarmRestarts(stepper.opt, T_0=T_max)
     prev_val_loss = 100
     if checkpoint is not None:
@@ -215,7 +247,7 @@ def train_tav_network(model, PREFormer, train_dataloader, val_dataloader, criter
             wandb.log({"epoch": epoch_num, "learning_rate": scheduler.get_last_lr()[0]})
         stepper.opt.zero_grad()
         prev_val_loss = one_epoch(epoch_num, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, epoch_switch, patience,
-                                  Metric, prev_val_loss, path, log_val)
+                                  Metric, prev_val_loss, path, log_val, graphs=graphs)
         if PATIENCE_ITER == patience:
             return model, PREFormer
     return model, PREFormer

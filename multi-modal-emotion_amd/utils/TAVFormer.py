@@ -170,8 +170,7 @@ class TransformerEncoder(nn.Module):
         key_mask = attention_mask.reshape(B, S).to(torch.float32).contiguous() if attention_mask is not None else None
         p = self.p if self.training else 0.0
         h = x.reshape(B * S, H)
-        for i, layer in enumerate(self.layers):
-            self._calls += 1
-            seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._calls) & 0xFFFFFFFFFFFFFFFF
+        seeds = runtime.dropout_seeds(self, "_calls", len(self.layers), draw=p > 0)      # one draw per layer, three masks each
+        for layer, seed in zip(self.layers, seeds):
             h = E.TransformerBlockFn.apply(h, key_mask, ectx, B, S, self.n_heads, p, seed, *layer.params())
         return h.view(B, S, H)

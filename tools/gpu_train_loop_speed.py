@@ -1,0 +1,90 @@
+"""Speed of the TRAINING LOOP's step machinery (train_model/tav_train.py not_grad_accum body: get_statistics with Metric, loss.item(), backward,
+clip + AdamW, scheduler step), eager against graph mode (train_model/graphed.GraphedSteps), at bench.py's preset and input shapes with
+check="train" (head dropout and SpecAugment on).  Batches are synthetic and resident on the device, cycled, so the loop -- not host-side data
+generation -- is what is timed.  One mode per process (a graph pool next to an eager run's caches would distort the memory picture).
+
+  python tools/gpu_train_loop_speed.py --global-batch 32 --mode graph --steps 30 --warmup 3
+prints one JSON line: ms per step and utterances per second over the timed steps.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--global-batch", type=int, default=32)
+    ap.add_argument("--mode", choices=["eager", "graph"], required=True)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--preset", default="B")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--cycle", type=int, default=2, help="distinct device-resident batches, used in turn")
+    args = ap.parse_args()
+
+    import torch
+    import tav_amd  # noqa: F401
+    from tav_amd import config as C
+    from tav_amd import runtime, synthetic
+    from tav_amd.models.tav import PreFormer, TAVForMAE
+    from tav_amd.train_model import tav_train as T
+    from tav_amd.train_model.graphed import GraphedSteps
+    from tav_amd.utils.global_functions import CrossEntropyLoss, Metrics
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    work = torch.cuda.Stream()
+    torch.cuda.set_stream(work)
+    cfg = C.preset(args.preset)
+    runtime.set_precision(args.dtype)
+    torch.manual_seed(0)
+    pre, model = PreFormer(cfg), TAVForMAE(dict(output_dim=7, dropout=0.5, learn_PosEmbeddings=True, num_layers=12), cfg)
+    synthetic.seeded_init_(pre, 1)
+    synthetic.seeded_init_(model, 2)
+    pre.to(dev)
+    model.to(dev)
+    b = args.global_batch
+    batches = [synthetic.make_batch(cfg, b, seed=1234 + i, device=dev) for i in range(args.cycle)]      # bench.py's input shapes
+    crit, metric = CrossEntropyLoss(), Metrics(7)
+    stepper = T.TrainStep(model, pre, crit, lr=1e-6, weight_decay=1e-4, clip=1.0)
+    sched = T.CosineWarmRestarts(stepper.opt, T_0=2)
+    n = args.warmup + args.steps
+    graphs = GraphedSteps(stepper) if args.mode == "graph" else None
+
+    def step(i):
+        inp, lab = batches[i % len(batches)]
+        if graphs is not None:
+            v = graphs.step(inp, lab, 0, metric)
+        else:
+            loss = T.get_statistics(inp, lab, model, pre, crit, metric, check="train", epoch=0)
+            v = loss.item()
+            loss.backward()
+            stepper.update()
+        sched.step(i / n)
+        return v
+
+    for i in range(args.warmup):
+        step(i)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    losses = [step(args.warmup + i) for i in range(args.steps)]
+    torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    ms = el / args.steps * 1e3
+    out = {"tool": "gpu_train_loop_speed", "mode": args.mode, "preset": args.preset, "dtype": args.dtype, "global_batch": b, "check": "train",
+           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "utt_per_s": round(b / (el / args.steps), 2),
+           "last_loss": round(losses[-1], 5), "finite": all(v == v and abs(v) != float("inf") for v in losses),
+           "peak_mem_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
+    if graphs is not None:
+        out.update(eager_steps=graphs.eager_steps, captures=graphs.captures, replays=graphs.replays)
+        graphs.invalidate()
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
