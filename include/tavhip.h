@@ -179,6 +179,13 @@ typedef struct tav_attn_args {
 } tav_attn_args;
 int tav_attn_fwd(const tav_attn_args* args, void* stream);
 int tav_attn_bwd(const tav_attn_args* args, void* stream);
+/* Length-aware (ragged) forms: seq_lens [B] int32 on the device gives the valid length L_b of each batch entry inside the padded
+ * S-row layout above (clamped into [0, S]).  Row b computes exactly what tav_attn_fwd / tav_attn_bwd compute for that entry alone
+ * with S = L_b (bitwise): keys >= L_b are outside the softmax and, in mask_mode 2, outside corr; key tiles past L_b are skipped.
+ * Rows >= L_b of o (o_soft), dq, dk and dv are written as zeros, lse entries as 0 (corr as 0 when L_b = 0); delta past L_b is
+ * not written.  Same argument checks as the plain forms; NULL seq_lens -> TAV_ERR_NULL. */
+int tav_attn_fwd_len(const tav_attn_args* args, const int32_t* seq_lens, void* stream);
+int tav_attn_bwd_len(const tav_attn_args* args, const int32_t* seq_lens, void* stream);
 /* Slow-path helpers for VideoMAEEncoder.forward(head_mask=, output_attentions=True) (reference utils/TAVFormer.py:190, :368-370, :389; never
  * used by the reference's training loop).  tav_attn_probs materialises, from q, k and the lse tav_attn_fwd wrote,
  *   probs[b][h][i][j] = head_scale[b*hs_bstride + h] * softmax_j(scale q_i.k_j (+ key_mask[b][j], mask_mode 1)) (+ key_mask[b][j], mask_mode 2)
@@ -306,6 +313,11 @@ int tav_gather_rows(const float* table, const int32_t* idx, float* out, int64_t 
 /* mean over tokens: y[b][:] = mean_s x[b][s][:] (models/tav.py:478,481,488) and its backward dx[b][s][:] = dy[b][:]/S */
 int tav_mean_pool_fwd(const float* x, float* y, int64_t B, int64_t S, int64_t W, void* stream);
 int tav_mean_pool_bwd(const float* dy, float* dx, void* dx_lp, int32_t lp_dtype, int64_t B, int64_t S, int64_t W, void* stream);
+/* length-aware forms (seq_lens [B] int32 on the device, clamped into [0, S]): y[b] = mean_{s < L_b} x[b][s] in the summation order of
+ * tav_mean_pool_fwd on S = L_b (bitwise equal; L_b = 0 gives 0); dx[b][s] = dy[b]/L_b for s < L_b and 0 beyond */
+int tav_mean_pool_fwd_len(const float* x, float* y, const int32_t* seq_lens, int64_t B, int64_t S, int64_t W, void* stream);
+int tav_mean_pool_bwd_len(const float* dy, float* dx, void* dx_lp, int32_t lp_dtype, const int32_t* seq_lens, int64_t B, int64_t S, int64_t W,
+                          void* stream);
 
 /* small dense head (N <= 16, e.g. Linear(3072,7), models/tav.py:499): y = x W^T + b ; all f32.
  * bwd: dx = dy W ; dW (+)= dy^T x ; db (+)= colsum(dy) */

@@ -93,6 +93,8 @@ _SIGS = {
     "tav_allreduce_bucket": (C.c_int, [vp, i64, i32, vp, vp]),
     "tav_attn_fwd": (C.c_int, [C.POINTER(AttnArgs), vp]),
     "tav_attn_bwd": (C.c_int, [C.POINTER(AttnArgs), vp]),
+    "tav_attn_fwd_len": (C.c_int, [C.POINTER(AttnArgs), vp, vp]),
+    "tav_attn_bwd_len": (C.c_int, [C.POINTER(AttnArgs), vp, vp]),
     "tav_attn_probs": (C.c_int, [C.POINTER(AttnArgs), vp, vp, i64, vp]),
     "tav_head_scale": (C.c_int, [vp, vp, vp, i32, vp, i64, f32, i64, i64, i64, i64, i64, i64, vp]),
     "tav_ln_fwd": (C.c_int, [C.POINTER(LnArgs), vp]),
@@ -117,6 +119,8 @@ _SIGS = {
     "tav_mask_to_index": (C.c_int, [vp, i32, vp, vp, i64, i64, i64, vp]),
     "tav_mean_pool_fwd": (C.c_int, [vp, vp, i64, i64, i64, vp]),
     "tav_mean_pool_bwd": (C.c_int, [vp, vp, vp, i32, i64, i64, i64, vp]),
+    "tav_mean_pool_fwd_len": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
+    "tav_mean_pool_bwd_len": (C.c_int, [vp, vp, vp, i32, vp, i64, i64, i64, vp]),
     "tav_head_fwd": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp]),
     "tav_head_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]),
     "tav_tanh_fwd": (C.c_int, [vp, vp, i64, vp]),

@@ -48,6 +48,10 @@ struct AttnP {
     int pre;       // q holds q * scale * log2(e) already (the QKV projection's q rows were scaled in the weight copy)
     int tiles;     // workgroups per (batch, head) slice of THIS launch (query tiles: forward, dQ; key tiles: dK/dV); grid = tiles * nh * B, 1-D
 };
+// arguments of a length-aware launch: the valid rows L_b of each batch entry ([B] int32, clamped into [0, S]); S stays the row stride.
+// (a separate type, so that the kernel arguments -- and the code -- of the plain instantiations stay exactly as they were)
+struct AttnPL : AttnP { const int* lens; };
+template <bool LEN> using AttnArg = std::conditional_t<LEN, AttnPL, AttnP>;
 
 // Which tile of which (batch, head) slice a workgroup owns.  The grid is one-dimensional and walked through xcd_remap with the tile index
 // fastest: every XCD gets a contiguous band of whole (batch, head) slices, so all the tiles that stream one slice's K / V (forward, dQ)
@@ -65,6 +69,26 @@ TAV_DEV AttnTile attn_tile(const AttnP& p) {
     AttnTile w;                    // (pinned to SGPRs: the slice bases feed the scalar operand of the LDS-DMA asm)
     w.x = to_sgpr(id - hb * p.tiles); w.head = to_sgpr(hb - b * p.nh); w.b = to_sgpr(b);
     return w;
+}
+
+// Length-aware launches (tav_attn_*_len): batch entry b holds L_b valid rows inside its S-row slice.  Every kernel below is written
+// against two sizes, S (the buffer layout: slice bases, lse / delta / mask rows, output rows) and L (everything the arithmetic sees:
+// tile counts, row clamps, -inf past the end).  Without LEN, L == S and the instantiation is the plain kernel.  With it, row b does
+// exactly what the plain kernel does on a B = 1 problem with S = L_b (same tiles, same clamps, same tail masking): bitwise equal.
+template <bool LEN> TAV_DEV int valid_len(const AttnArg<LEN>& p, int b) {
+    if constexpr (LEN) {
+        int L = p.lens[b];
+        L = L < 0 ? 0 : (L > p.S ? p.S : L);
+        return __builtin_amdgcn_readfirstlane(L);
+    } else return p.S;
+}
+// zero the head-h slice of rows [r0, min(r0 + nrows, S)) of one batch entry (a workgroup's rows past L_b: never left uninitialised)
+template <typename T>
+TAV_DEV void zero_head_rows(char* base, long ld, int b, int S, int head, int r0, int nrows, int tid) {
+    for (int e = tid; e < nrows * 16; e += 256) {
+        const int r = r0 + (e >> 4);
+        if (r < S) st4(reinterpret_cast<T*>(base) + ((long)b * S + r) * ld + head * 64 + 4 * (e & 15), f32x4{0.f, 0.f, 0.f, 0.f});
+    }
 }
 
 TAV_DEV float vmax3(float a, float b, float c) { return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c); }
@@ -264,8 +288,8 @@ constexpr bool ATT_ABL_NOBAR = false;
 #define TAV_ATT_FWD_NQ 2     // 16-query tiles per wave of the unmasked pre-scaled bf16 forward (3: K/V fragment reads, DMA and barriers amortised over 1.5x the MFMAs; two waves per SIMD)
 #endif
 template <typename T, int MODE, bool PRE> constexpr int fwd_nq() { return (sizeof(T) == 2 && MODE == 0 && PRE) ? TAV_ATT_FWD_NQ : 2; }
-template <typename T, int MODE, bool PRE>
-__global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_OCC)) void attn_fwd_kernel(const AttnP p) {
+template <typename T, int MODE, bool PRE, bool LEN = false>
+__global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_OCC)) void attn_fwd_kernel(const AttnArg<LEN> p) {
     constexpr int NQ = fwd_nq<T, MODE, PRE>();             // 16-query tiles per wave (2; 3 = 48 queries per wave, 192 per workgroup)
     using H = HD<T>;
     constexpr int ES = H::ES, NSD = H::NSD, KSTEP = ET<T>::KSTEP, BKV = 64;
@@ -282,8 +306,17 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
     const AttnTile wg = attn_tile(p);
-    const int head = wg.head, b = wg.b, S = p.S;
+    const int head = wg.head, b = wg.b, S = p.S, L = valid_len<LEN>(p, b);
     const int q0 = wg.x * (64 * NQ) + wave * (16 * NQ);
+    if constexpr (LEN) {
+        if (wg.x * (64 * NQ) >= L) {                          // (workgroup-uniform) no valid query here: zero o (o_soft), lse and, for L = 0, corr
+            zero_head_rows<T>(p.o, p.ld_o, b, S, head, wg.x * (64 * NQ), 64 * NQ, tid);
+            if (MODE == 2) zero_head_rows<T>(p.o_soft, p.ld_o, b, S, head, wg.x * (64 * NQ), 64 * NQ, tid);
+            if (tid < 64 * NQ && wg.x * (64 * NQ) + tid < S) p.lse[((long)b * p.nh + head) * S + wg.x * (64 * NQ) + tid] = 0.f;
+            if (MODE == 2 && wg.x == 0 && tid < 64) p.corr[((long)b * p.nh + head) * 64 + tid] = 0.f;
+            return;
+        }
+    }
     const long hoff = (long)head * 64 * ES;
     const char* Qb = p.q + (long)b * S * p.ld_q * ES + hoff;
     const char* Kb = p.k + (long)b * S * p.ld_k * ES + hoff;
@@ -292,7 +325,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
 
     uint4 qf[NQ][NSD];
 #pragma unroll
-    for (int qt = 0; qt < NQ; ++qt) row_frags_gload<T>(qf[qt], Qb, p.ld_q * ES, q0 + 16 * qt + i, S, g);
+    for (int qt = 0; qt < NQ; ++qt) row_frags_gload<T>(qf[qt], Qb, p.ld_q * ES, q0 + 16 * qt + i, L, g);
 
     // softmax runs in the exp2 domain: t = s*scale*log2(e) + mask*log2(e); p = exp2(t - m).  The row sums l come out of the MFMA
     // pipe (a ones-row operand times P^T) instead of 32 VALU adds + shuffles per tile: the kernel is VALU-issue bound.
@@ -328,22 +361,22 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
     }
     float corr_part = 0.f;
 
-    const int nkt = (S + BKV - 1) / BKV;
+    const int nkt = (L + BKV - 1) / BKV;
     uint4 rk[NCH], rv[NCH];
     float r_mask = 0.f;
     // gload only ISSUES loads (no arithmetic on a loaded value: that would put a vmcnt wait -- a drain of the whole prefetch --
     // right behind the issue); lstore, one tile of compute later, turns the raw mask value into the per-key additive terms.
     unsigned k_off0[NCH], k_max[NCH], v_off0[NCH], v_max[NCH];
     if constexpr (!DMA) {
-        tile_addr_init<T, BKV>(k_off0, k_max, p.ld_k * ES, S, tid);
-        tile_addr_init<T, BKV>(v_off0, v_max, p.ld_v * ES, S, tid);
+        tile_addr_init<T, BKV>(k_off0, k_max, p.ld_k * ES, L, tid);
+        tile_addr_init<T, BKV>(v_off0, v_max, p.ld_v * ES, L, tid);
     }
     const unsigned kstep_b = (unsigned)(BKV * p.ld_k * ES), vstep_b = (unsigned)(BKV * p.ld_v * ES);
     // DMA geometry: wave w fills rows [16w, 16w + 16) of both images, 8 rows per instruction; lane -> (row, slot), source chunk = slot ^ swizzle.
     // The lane offsets are constants of the kernel; the tile walks on the SCALAR base (one s_add per operand), so a regular tile costs no
     // vector instruction for its addresses.  Only the ragged last tile clamps rows past S (to row S-1: finite data, their scores are -inf).
     PairDma kv;
-    if constexpr (DMA) kv.init(Kb, Vb, p.ld_k * ES, p.ld_v * ES, S, smem, smem + KROW_B, tid);
+    if constexpr (DMA) kv.init(Kb, Vb, p.ld_k * ES, p.ld_v * ES, L, smem, smem + KROW_B, tid);
     auto dma = [&](int t, int buf, auto ragged_tag) __attribute__((always_inline)) {
         kv.template issue<decltype(ragged_tag)::value != 0>(t, (unsigned)(buf * BUF_B));
     };
@@ -354,7 +387,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
         }
         if (MODE != 0 && tid < BKV) {
             int key = t * BKV + tid;
-            key = key < S ? key : S - 1;
+            key = key < L ? key : L - 1;
             r_mask = maskb[key];
         }
     };
@@ -366,7 +399,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
             tile_lstore_nat<T, BKV>(rv, base + KROW_B, tid);
         }
         if ((MODE != 0 || t == nkt - 1) && tid < BKV) {
-            const bool ok = t * BKV + tid < S;
+            const bool ok = t * BKV + tid < L;
             float* f = reinterpret_cast<float*>(base + KROW_B + VNAT_B);
             f[tid] = ok ? (MODE == 1 ? r_mask * 1.4426950408889634f : 0.f) : -INFINITY;   // already in the exp2 domain
             f[BKV + tid] = (MODE == 2 && ok) ? r_mask : 0.f;
@@ -579,7 +612,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
     for (int qt = 0; qt < NQ; ++qt) {
         const float l = lacc[qt][0];          // the MFMA already summed over all keys (all lane groups)
         const int q = q0 + 16 * qt + i;
-        if (q < S) {
+        if (q < L) {
             const float inv = 1.f / l;
             T* orow = reinterpret_cast<T*>(p.o) + ((long)b * S + q) * p.ld_o + head * 64;
             T* srow = reinterpret_cast<T*>(p.o_soft) + ((long)b * S + q) * p.ld_o + head * 64;
@@ -593,6 +626,16 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
                 st4(orow + 16 * dt + 4 * g, v);
             }
             if (g == 0) p.lse[((long)b * p.nh + head) * S + q] = (m_run[qt] + log2f(l)) * 0.6931471805599453f;   // natural-log LSE
+        } else if (LEN && q < S) {                          // padded query rows of a length-aware launch
+            T* orow = reinterpret_cast<T*>(p.o) + ((long)b * S + q) * p.ld_o + head * 64;
+            T* srow = reinterpret_cast<T*>(p.o_soft) + ((long)b * S + q) * p.ld_o + head * 64;
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                if (MODE == 2) st4(srow + 16 * dt + 4 * g, z);
+                st4(orow + 16 * dt + 4 * g, z);
+            }
+            if (g == 0) p.lse[((long)b * p.nh + head) * S + q] = 0.f;
         }
     }
 }
@@ -814,8 +857,8 @@ template <typename T, int MODE, bool PRE> constexpr int dkdv_bq() { return sizeo
 #ifndef TAV_ATT_DQ_OCC
 #define TAV_ATT_DQ_OCC 2
 #endif
-template <typename T, int MODE, bool PRE>
-__global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKDV_OCC)) void attn_bwd_dkdv_kernel(const AttnP p) {
+template <typename T, int MODE, bool PRE, bool LEN = false>
+__global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKDV_OCC)) void attn_bwd_dkdv_kernel(const AttnArg<LEN> p) {
     using H = HD<T>;
     constexpr int ES = H::ES, NSD = H::NSD, KSTEP = ET<T>::KSTEP, BQ = dkdv_bq<T, MODE, PRE>(), NQT = BQ / 16;
     constexpr int NCH = BQ * H::ROWCH / 256;
@@ -827,8 +870,15 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
     const AttnTile wg = attn_tile(p);
-    const int head = wg.head, b = wg.b, S = p.S;
+    const int head = wg.head, b = wg.b, S = p.S, L = valid_len<LEN>(p, b);
     const int k0 = wg.x * 128 + wave * 32;
+    if constexpr (LEN) {
+        if (wg.x * 128 >= L) {                                // (workgroup-uniform) no valid key here: dK = dV = 0
+            zero_head_rows<T>(p.dk, p.ld_dk, b, S, head, wg.x * 128, 128, tid);
+            zero_head_rows<T>(p.dv, p.ld_dv, b, S, head, wg.x * 128, 128, tid);
+            return;
+        }
+    }
     const long hoff = (long)head * 64 * ES;
     const char* Qb = p.q + (long)b * S * p.ld_q * ES + hoff;
     const char* Kb = p.k + (long)b * S * p.ld_k * ES + hoff;
@@ -842,9 +892,9 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
         const int key = k0 + 16 * kt + i;
-        row_frags_gload<T>(kf[kt], Kb, p.ld_k * ES, key, S, g);
-        row_frags_gload<T>(vf[kt], Vb, p.ld_v * ES, key, S, g);
-        const bool ok = key < S;
+        row_frags_gload<T>(kf[kt], Kb, p.ld_k * ES, key, L, g);
+        row_frags_gload<T>(vf[kt], Vb, p.ld_v * ES, key, L, g);
+        const bool ok = key < L;
         const float mv = (MODE != 0 && ok) ? p.mask[(long)b * S + key] : 0.f;
         kadd[kt] = ok ? (MODE == 1 ? mv * 1.4426950408889634f : 0.f) : -INFINITY;    // exp2 domain
         cmk[kt] = (MODE == 2) ? mv : 0.f;
@@ -860,18 +910,18 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
         for (int c = 0; c < 2; ++c) { dVt[a][c] = f32x4{0.f, 0.f, 0.f, 0.f}; dKt[a][c] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     float dosum_part = 0.f;
 
-    const bool with_kadd = (MODE == 1) || (k0 + 32 > S);      // wave-uniform
-    const int nqt = (S + BQ - 1) / BQ;
+    const bool with_kadd = (MODE == 1) || (k0 + 32 > L);      // wave-uniform
+    const int nqt = (L + BQ - 1) / BQ;
     uint4 rq[NCH], rdo[NCH];
     float r_lse = 0.f, r_delta = 0.f;
     unsigned q_off0[NCH], q_max[NCH], do_off0[NCH], do_max[NCH];
     if constexpr (!DMA) {
-        tile_addr_init<T, BQ>(q_off0, q_max, p.ld_q * ES, S, tid);
-        tile_addr_init<T, BQ>(do_off0, do_max, p.ld_do * ES, S, tid);
+        tile_addr_init<T, BQ>(q_off0, q_max, p.ld_q * ES, L, tid);
+        tile_addr_init<T, BQ>(do_off0, do_max, p.ld_do * ES, L, tid);
     }
     const unsigned qstep_b = (unsigned)(BQ * p.ld_q * ES), dostep_b = (unsigned)(BQ * p.ld_do * ES);
     PairDmaT<(ES == 2 ? BQ : 64)> qd;
-    if constexpr (DMA) qd.init(Qb, dOb, p.ld_q * ES, p.ld_do * ES, S, smem, smem + ROW_B, tid);
+    if constexpr (DMA) qd.init(Qb, dOb, p.ld_q * ES, p.ld_do * ES, L, smem, smem + ROW_B, tid);
     // lane constants of the fragment reads (bf16 row images; see attn_fwd_kernel): the row reads of Q and dO share one per k-step, the
     // transposed reads one per d-tile
     unsigned roff[NSD], toff[4];
@@ -891,7 +941,7 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
         }
         if (tid < BQ) {                                   // raw loads only (see attn_fwd_kernel::gload)
             int q = t * BQ + tid;
-            q = q < S ? q : S - 1;
+            q = q < L ? q : L - 1;
             r_lse = lseb[q];
             r_delta = deltab[q];
         }
@@ -899,8 +949,8 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
     auto lstore = [&](int t, int buf) {
         char* base = smem + buf * BUF_B;
         if constexpr (!DMA) {
-            tile_zero_pad<T, BQ>(rq, t * BQ, S, tid);
-            tile_zero_pad<T, BQ>(rdo, t * BQ, S, tid);
+            tile_zero_pad<T, BQ>(rq, t * BQ, L, tid);
+            tile_zero_pad<T, BQ>(rdo, t * BQ, L, tid);
             tile_lstore_row<T, BQ>(rq, base, tid);
             tile_lstore_row<T, BQ>(rdo, base + ROW_B, tid);
             if constexpr (!H::DUAL) {
@@ -909,7 +959,7 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
             }
         }
         if (tid < BQ) {
-            const bool ok = t * BQ + tid < S;
+            const bool ok = t * BQ + tid < L;
             float* f = reinterpret_cast<float*>(base + 2 * ROW_B + 2 * NAT_B);
             f[tid] = ok ? -r_lse * lse_mul : -INFINITY;     // S accumulators start at -lse/scale (PRE: -lse*log2e); -inf => p = 0 for rows past S
             f[BQ + tid] = ok ? -r_delta : 0.f;                // dP accumulators start at -delta
@@ -980,7 +1030,7 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
                     // (without a pre-softmax mask the term is 0 / -inf past S: re-derived here, on the ragged key block only, instead of
                     // living in two registers across the whole loop -- the 32-query form of this kernel sits at the 168-register line)
                     float ka = kadd[kt];
-                    if constexpr (MODE != 1) { int ky = k0 + 16 * kt + i; asm volatile("" : "+v"(ky)); ka = ky < S ? 0.f : -INFINITY; }
+                    if constexpr (MODE != 1) { int ky = k0 + 16 * kt + i; asm volatile("" : "+v"(ky)); ka = ky < L ? 0.f : -INFINITY; }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) sacc[qt][kt][r] = fast_exp2(PRE ? sacc[qt][kt][r] + ka : __builtin_fmaf(sacc[qt][kt][r], c2, ka));
                 }
@@ -1032,7 +1082,7 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
             for (int rr = 0; rr < BQ / 4; ++rr) {
                 const int row = rq8 * (BQ / 4) + rr;
                 const float v = tile_elem<T>(dOrow, dOnat, row, d);
-                dosum_part += (!DMA || qbase + row < S) ? v : 0.f;
+                dosum_part += (!DMA || qbase + row < L) ? v : 0.f;
             }
         }
         if constexpr (NEXT != 0) lstore(t + 1, cur ^ 1);
@@ -1053,7 +1103,7 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
         const int key = k0 + 16 * kt + i;
-        if (key < S) {
+        if (key < L) {
             T* dkrow = reinterpret_cast<T*>(p.dk) + ((long)b * S + key) * p.ld_dk + head * 64;
             T* dvrow = reinterpret_cast<T*>(p.dv) + ((long)b * S + key) * p.ld_dv + head * 64;
 #pragma unroll
@@ -1063,13 +1113,19 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
                 st4(dvrow + 16 * dt + 4 * g, dvv);
                 st4(dkrow + 16 * dt + 4 * g, dKt[dt][kt] * dk_mul);
             }
+        } else if (LEN && key < S) {                        // padded key rows of a length-aware launch
+            T* dkrow = reinterpret_cast<T*>(p.dk) + ((long)b * S + key) * p.ld_dk + head * 64;
+            T* dvrow = reinterpret_cast<T*>(p.dv) + ((long)b * S + key) * p.ld_dv + head * 64;
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) { st4(dvrow + 16 * dt + 4 * g, z); st4(dkrow + 16 * dt + 4 * g, z); }
         }
     }
 }
 
 // ================================================================================================= backward: dQ
-template <typename T, int MODE, bool PRE>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? TAV_ATT_DQ_OCC : 1)) void attn_bwd_dq_kernel(const AttnP p) {
+template <typename T, int MODE, bool PRE, bool LEN = false>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? TAV_ATT_DQ_OCC : 1)) void attn_bwd_dq_kernel(const AttnArg<LEN> p) {
     using H = HD<T>;
     constexpr int ES = H::ES, NSD = H::NSD, KSTEP = ET<T>::KSTEP, BKV = 64;
     constexpr int NCH = BKV * H::ROWCH / 256;
@@ -1080,8 +1136,14 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? TAV_ATT_DQ_OCC : 1)) void at
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
     const AttnTile wg = attn_tile(p);
-    const int head = wg.head, b = wg.b, S = p.S;
+    const int head = wg.head, b = wg.b, S = p.S, L = valid_len<LEN>(p, b);
     const int q0 = wg.x * 128 + wave * 32;
+    if constexpr (LEN) {
+        if (wg.x * 128 >= L) {                                // (workgroup-uniform) no valid query here: dQ = 0 (delta past L is never read)
+            zero_head_rows<T>(p.dq, p.ld_dq, b, S, head, wg.x * 128, 128, tid);
+            return;
+        }
+    }
     const long hoff = (long)head * 64 * ES;
     const char* Qb = p.q + (long)b * S * p.ld_q * ES + hoff;
     const char* Kb = p.k + (long)b * S * p.ld_k * ES + hoff;
@@ -1094,16 +1156,16 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? TAV_ATT_DQ_OCC : 1)) void at
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
         int q = q0 + 16 * qt + i;
-        row_frags_gload<T>(qf[qt], Qb, p.ld_q * ES, q, S, g);
-        row_frags_gload<T>(dof[qt], dOb, p.ld_do * ES, q, S, g);
-        if (q >= S) q = S - 1;
+        row_frags_gload<T>(qf[qt], Qb, p.ld_q * ES, q, L, g);
+        row_frags_gload<T>(dof[qt], dOb, p.ld_do * ES, q, L, g);
+        if (q >= L) q = L - 1;
         lse_q[qt] = -p.lse[((long)b * p.nh + head) * S + q] * (PRE ? 1.4426950408889634f : 1.0f / p.scale);   // S accumulators start at -lse/scale (PRE: -lse*log2e), dP at -delta
         // delta[q] = sum_d dO[q][d] * (softmax(s) v)[q][d], formed HERE (this kernel runs first and has the dO rows in registers anyway; the
         // separate delta kernel of rounds 1-2 cost a launch and 33 us at batch 32) and written out for the dK/dV kernel.  Lane (g, i) holds
         // chunks 4s + g of query i's rows: 16 of the 64 products; the four lane groups meet in two permlane swaps.
         const char* Ob = (MODE == 2 ? p.o_soft : p.o) + ((long)b * S * p.ld_o + (long)head * 64) * ES;     // (mode 2: the softmax-only part, never o - corr)
         uint4 of[NSD];
-        row_frags_gload<T>(of, Ob, p.ld_o * ES, q, S, g);
+        row_frags_gload<T>(of, Ob, p.ld_o * ES, q, L, g);
         float part = 0.f;
 #pragma unroll
         for (int s = 0; s < NSD; ++s) {
@@ -1118,24 +1180,24 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? TAV_ATT_DQ_OCC : 1)) void at
         }
         part = sum_over_row_groups(part);
         delta_q[qt] = -part;                                               // (row constants as the initial accumulators)
-        if (g == 0 && q0 + 16 * qt + i < S) p.delta[((long)b * p.nh + head) * S + q] = part;
+        if (g == 0 && q0 + 16 * qt + i < L) p.delta[((long)b * p.nh + head) * S + q] = part;
     }
     const float c2 = PRE ? 1.0f : p.scale * 1.4426950408889634f;
     f32x4 dQt[4][2];
 #pragma unroll
     for (int a = 0; a < 4; ++a) { dQt[a][0] = f32x4{0.f, 0.f, 0.f, 0.f}; dQt[a][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
-    const int nkt = (S + BKV - 1) / BKV;
+    const int nkt = (L + BKV - 1) / BKV;
     uint4 rk[NCH], rv[NCH];
     float r_kadd = 0.f;
     unsigned k_off0[NCH], k_max[NCH], v_off0[NCH], v_max[NCH];
     if constexpr (!DMA) {
-        tile_addr_init<T, BKV>(k_off0, k_max, p.ld_k * ES, S, tid);
-        tile_addr_init<T, BKV>(v_off0, v_max, p.ld_v * ES, S, tid);
+        tile_addr_init<T, BKV>(k_off0, k_max, p.ld_k * ES, L, tid);
+        tile_addr_init<T, BKV>(v_off0, v_max, p.ld_v * ES, L, tid);
     }
     const unsigned kstep_b = (unsigned)(BKV * p.ld_k * ES), vstep_b = (unsigned)(BKV * p.ld_v * ES);
     PairDma kv;
-    if constexpr (DMA) kv.init(Kb, Vb, p.ld_k * ES, p.ld_v * ES, S, smem, smem + ROW_B, tid);
+    if constexpr (DMA) kv.init(Kb, Vb, p.ld_k * ES, p.ld_v * ES, L, smem, smem + ROW_B, tid);
     // lane constants of the fragment reads (bf16 row images; see attn_fwd_kernel): row reads of K and V share one, the transposed K reads four
     unsigned koff[NSD], ktoff[4];
     if constexpr (ES == 2) {
@@ -1154,7 +1216,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? TAV_ATT_DQ_OCC : 1)) void at
         }
         if (MODE == 1 && tid < BKV) {                     // raw load only (see attn_fwd_kernel::gload)
             int key = t * BKV + tid;
-            key = key < S ? key : S - 1;
+            key = key < L ? key : L - 1;
             r_kadd = maskb[key];
         }
     };
@@ -1166,7 +1228,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? TAV_ATT_DQ_OCC : 1)) void at
             if constexpr (!H::DUAL) tile_lstore_nat<T, BKV>(rk, base + 2 * ROW_B, tid);
         }
         if ((MODE == 1 || t == nkt - 1) && tid < BKV)     // (only the masked / ragged tiles read the per-key terms)
-            reinterpret_cast<float*>(base + 2 * ROW_B + NAT_B)[tid] = (t * BKV + tid < S) ? (MODE == 1 ? r_kadd * 1.4426950408889634f : 0.f) : -INFINITY;
+            reinterpret_cast<float*>(base + 2 * ROW_B + NAT_B)[tid] = (t * BKV + tid < L) ? (MODE == 1 ? r_kadd * 1.4426950408889634f : 0.f) : -INFINITY;
     };
     if constexpr (DMA) { if (nkt == 1) kv.template issue<true>(0, 0u); else kv.template issue<false>(0, 0u); }
     gload(0); lstore(0, 0);
@@ -1271,10 +1333,14 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? TAV_ATT_DQ_OCC : 1)) void at
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
         const int q = q0 + 16 * qt + i;
-        if (q < S) {
+        if (q < L) {
             T* dqrow = reinterpret_cast<T*>(p.dq) + ((long)b * S + q) * p.ld_dq + head * 64;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) st4(dqrow + 16 * dt + 4 * g, dQt[dt][qt] * p.scale);
+        } else if (LEN && q < S) {                          // padded query rows of a length-aware launch
+            T* dqrow = reinterpret_cast<T*>(p.dq) + ((long)b * S + q) * p.ld_dq + head * 64;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) st4(dqrow + 16 * dt + 4 * g, f32x4{0.f, 0.f, 0.f, 0.f});
         }
     }
 }
@@ -1372,32 +1438,55 @@ static AttnP pack(const tav_attn_args* a) {
     return p;
 }
 
-template <typename T, int MODE, bool PRE> static int launch_fwd(const AttnP& p, hipStream_t st) {
+template <typename T, int MODE, bool PRE, bool LEN> static int launch_fwd(const AttnArg<LEN>& p, hipStream_t st) {
 #if TAV_ATT_FWD32
-    if constexpr (sizeof(T) == 2 && MODE == 0 && PRE) {
+    if constexpr (sizeof(T) == 2 && MODE == 0 && PRE && !LEN) {
         AttnP pl = p; pl.tiles = (p.S + 127) / 128;
         hipLaunchKernelGGL(attn_fwd32_kernel, dim3((unsigned)pl.tiles * p.nh * p.B), dim3(256), fwd_lds<bf16>(), st, pl);
         return (int)hipGetLastError();
     }
 #endif
     constexpr int QW = 64 * fwd_nq<T, MODE, PRE>();          // queries per workgroup
-    AttnP pl = p; pl.tiles = (p.S + QW - 1) / QW;
-    hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, PRE>), dim3((unsigned)pl.tiles * p.nh * p.B), dim3(256), fwd_lds<T>(), st, pl);
+    AttnArg<LEN> pl = p; pl.tiles = (p.S + QW - 1) / QW;
+    hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, PRE, LEN>), dim3((unsigned)pl.tiles * p.nh * p.B), dim3(256), fwd_lds<T>(), st, pl);
     return (int)hipGetLastError();
 }
-template <typename T, int MODE, bool PRE> static int launch_bwd(const AttnP& p, hipStream_t st) {
-    AttnP pl = p; pl.tiles = (p.S + 127) / 128;
+// (length-aware launches keep the grid of the padded problem, sized by S: workgroups past L_b zero their rows and leave)
+template <typename T, int MODE, bool PRE, bool LEN> static int launch_bwd(const AttnArg<LEN>& p, hipStream_t st) {
+    AttnArg<LEN> pl = p; pl.tiles = (p.S + 127) / 128;
     const dim3 grid((unsigned)pl.tiles * p.nh * p.B);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, PRE>), grid, dim3(256), dq_lds<T>(), st, pl);        // also writes delta [B][nh][S]
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, PRE, LEN>), grid, dim3(256), dq_lds<T>(), st, pl);        // also writes delta [B][nh][S]
     constexpr size_t lds_dkdv = dkdv_lds<T, MODE, PRE>();
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, MODE, PRE>), grid, dim3(256), lds_dkdv, st, pl);    // reads it
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, MODE, PRE, LEN>), grid, dim3(256), lds_dkdv, st, pl);    // reads it
     return (int)hipGetLastError();
 }
-template <typename T, bool PRE> static int dispatch_fwd(const AttnP& p, int mode, hipStream_t st) {
-    switch (mode) { case 0: return launch_fwd<T, 0, PRE>(p, st); case 1: return launch_fwd<T, 1, PRE>(p, st); default: return launch_fwd<T, 2, PRE>(p, st); }
+template <typename T, bool PRE, bool LEN> static int dispatch_fwd(const AttnArg<LEN>& p, int mode, hipStream_t st) {
+    switch (mode) {
+        case 0: return launch_fwd<T, 0, PRE, LEN>(p, st);
+        case 1: return launch_fwd<T, 1, PRE, LEN>(p, st);
+        default: return launch_fwd<T, 2, PRE, LEN>(p, st);
+    }
 }
-template <typename T, bool PRE> static int dispatch_bwd(const AttnP& p, int mode, hipStream_t st) {
-    switch (mode) { case 0: return launch_bwd<T, 0, PRE>(p, st); case 1: return launch_bwd<T, 1, PRE>(p, st); default: return launch_bwd<T, 2, PRE>(p, st); }
+template <typename T, bool PRE, bool LEN> static int dispatch_bwd(const AttnArg<LEN>& p, int mode, hipStream_t st) {
+    switch (mode) {
+        case 0: return launch_bwd<T, 0, PRE, LEN>(p, st);
+        case 1: return launch_bwd<T, 1, PRE, LEN>(p, st);
+        default: return launch_bwd<T, 2, PRE, LEN>(p, st);
+    }
+}
+template <bool LEN> static int run_fwd(const tav_attn_args* a, const int32_t* seq_lens, hipStream_t st) {
+    AttnArg<LEN> p;
+    static_cast<AttnP&>(p) = pack(a);
+    if constexpr (LEN) p.lens = seq_lens;
+    if (a->dtype == TAV_BF16) return p.pre ? dispatch_fwd<bf16, true, LEN>(p, a->mask_mode, st) : dispatch_fwd<bf16, false, LEN>(p, a->mask_mode, st);
+    return p.pre ? dispatch_fwd<float, true, LEN>(p, a->mask_mode, st) : dispatch_fwd<float, false, LEN>(p, a->mask_mode, st);
+}
+template <bool LEN> static int run_bwd(const tav_attn_args* a, const int32_t* seq_lens, hipStream_t st) {
+    AttnArg<LEN> p;
+    static_cast<AttnP&>(p) = pack(a);
+    if constexpr (LEN) p.lens = seq_lens;
+    if (a->dtype == TAV_BF16) return p.pre ? dispatch_bwd<bf16, true, LEN>(p, a->mask_mode, st) : dispatch_bwd<bf16, false, LEN>(p, a->mask_mode, st);
+    return p.pre ? dispatch_bwd<float, true, LEN>(p, a->mask_mode, st) : dispatch_bwd<float, false, LEN>(p, a->mask_mode, st);
 }
 
 }  // namespace tav
@@ -1407,19 +1496,27 @@ using namespace tav;
 extern "C" int tav_attn_fwd(const tav_attn_args* a, void* stream) {
     int e = check(a, false);
     if (e) return e;
-    const AttnP p = pack(a);
-    hipStream_t st = (hipStream_t)stream;
-    if (a->dtype == TAV_BF16) return p.pre ? dispatch_fwd<bf16, true>(p, a->mask_mode, st) : dispatch_fwd<bf16, false>(p, a->mask_mode, st);
-    return p.pre ? dispatch_fwd<float, true>(p, a->mask_mode, st) : dispatch_fwd<float, false>(p, a->mask_mode, st);
+    return run_fwd<false>(a, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int tav_attn_bwd(const tav_attn_args* a, void* stream) {
     int e = check(a, true);
     if (e) return e;
-    const AttnP p = pack(a);
-    hipStream_t st = (hipStream_t)stream;
-    if (a->dtype == TAV_BF16) return p.pre ? dispatch_bwd<bf16, true>(p, a->mask_mode, st) : dispatch_bwd<bf16, false>(p, a->mask_mode, st);
-    return p.pre ? dispatch_bwd<float, true>(p, a->mask_mode, st) : dispatch_bwd<float, false>(p, a->mask_mode, st);
+    return run_bwd<false>(a, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int tav_attn_fwd_len(const tav_attn_args* a, const int32_t* seq_lens, void* stream) {
+    int e = check(a, false);
+    if (e) return e;
+    if (!seq_lens) return TAV_ERR_NULL;
+    return run_fwd<true>(a, seq_lens, (hipStream_t)stream);
+}
+
+extern "C" int tav_attn_bwd_len(const tav_attn_args* a, const int32_t* seq_lens, void* stream) {
+    int e = check(a, true);
+    if (e) return e;
+    if (!seq_lens) return TAV_ERR_NULL;
+    return run_bwd<true>(a, seq_lens, (hipStream_t)stream);
 }
 
 extern "C" int tav_attn_probs(const tav_attn_args* a, float* probs, const float* head_scale, int64_t hs_bstride, void* stream) {

@@ -368,6 +368,35 @@ __global__ void mean_pool_bwd_kernel(const float* __restrict__ dy, float* __rest
     if (dx) st4(dx + 4 * i, v);
     if (dx_lp) st4(dx_lp + 4 * i, v);
 }
+// length-aware forms: batch entry b averages its first L_b = clamp(lens[b], 0, S) rows of an S-row slice, in the order of
+// mean_pool_fwd_kernel on S = L_b (bitwise equal to it); L_b = 0 gives y = 0.  Backward: dy[b]/L_b on those rows, 0 on the rest.
+__device__ inline int pool_len(const int* lens, int b, int S) { const int L = lens[b]; return L < 0 ? 0 : (L > S ? S : L); }
+__global__ __launch_bounds__(256) void mean_pool_fwd_len_kernel(const float* __restrict__ x, float* __restrict__ y, const int* __restrict__ lens, int S, int W) {
+    __shared__ f32x4 red[16][16];
+    const int b = blockIdx.y, cq = threadIdx.x & 15, rg = threadIdx.x >> 4;
+    const int c = (blockIdx.x * 16 + cq) * 4, L = pool_len(lens, b, S);
+    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+    if (c < W) for (int s = rg; s < L; s += 16) a += ld4(x + ((long)b * S + s) * W + c);
+    red[rg][cq] = a;
+    __syncthreads();
+    if (rg == 0 && c < W) {
+#pragma unroll
+        for (int k = 1; k < 16; ++k) a += red[k][cq];
+        st4(y + (long)b * W + c, L > 0 ? a * (1.f / (float)L) : f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+}
+template <typename TL>
+__global__ void mean_pool_bwd_len_kernel(const float* __restrict__ dy, float* __restrict__ dx, TL* __restrict__ dx_lp, const int* __restrict__ lens, long n4,
+                                         int S, int W4) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const long row = i / W4; const int c = (int)(i - row * W4) * 4;
+    const long b = row / S;
+    const int s = (int)(row - b * S), L = pool_len(lens, (int)b, S);
+    const f32x4 v = s < L ? ld4(dy + b * W4 * 4 + c) * (1.f / (float)L) : f32x4{0.f, 0.f, 0.f, 0.f};
+    if (dx) st4(dx + 4 * i, v);
+    if (dx_lp) st4(dx_lp + 4 * i, v);
+}
 
 __global__ void head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ Wt, const float* __restrict__ bias, float* __restrict__ y,
                                 int Bn, int K, int N) {
@@ -818,6 +847,22 @@ extern "C" int tav_mean_pool_bwd(const float* dy, float* dx, void* dx_lp, int32_
     const long n4 = B * S * W / 4;
     if (dx_lp && lp == TAV_BF16) hipLaunchKernelGGL((mean_pool_bwd_kernel<bf16>), G1(n4), dy, dx, (bf16*)dx_lp, n4, (int)S, (int)(W / 4));
     else hipLaunchKernelGGL((mean_pool_bwd_kernel<float>), G1(n4), dy, dx, (float*)dx_lp, n4, (int)S, (int)(W / 4));
+    return tav_last_error();
+}
+extern "C" int tav_mean_pool_fwd_len(const float* x, float* y, const int32_t* seq_lens, int64_t B, int64_t S, int64_t W, void* stream) {
+    if (!x || !y || !seq_lens) return TAV_ERR_NULL;
+    if (B <= 0 || S <= 0 || W <= 0) return TAV_ERR_SHAPE;
+    if (W % 4) return TAV_ERR_SHAPE;
+    hipLaunchKernelGGL(mean_pool_fwd_len_kernel, dim3(tav_cdiv(W, 64), (unsigned)B), dim3(256), 0, ST, x, y, seq_lens, (int)S, (int)W);
+    return tav_last_error();
+}
+extern "C" int tav_mean_pool_bwd_len(const float* dy, float* dx, void* dx_lp, int32_t lp, const int32_t* seq_lens, int64_t B, int64_t S, int64_t W,
+                                     void* stream) {
+    if (!dy || (!dx && !dx_lp) || !seq_lens) return TAV_ERR_NULL;
+    if (B <= 0 || S <= 0 || W <= 0 || W % 4) return TAV_ERR_SHAPE;
+    const long n4 = B * S * W / 4;
+    if (dx_lp && lp == TAV_BF16) hipLaunchKernelGGL((mean_pool_bwd_len_kernel<bf16>), G1(n4), dy, dx, (bf16*)dx_lp, seq_lens, n4, (int)S, (int)(W / 4));
+    else hipLaunchKernelGGL((mean_pool_bwd_len_kernel<float>), G1(n4), dy, dx, (float*)dx_lp, seq_lens, n4, (int)S, (int)(W / 4));
     return tav_last_error();
 }
 extern "C" int tav_head_fwd(const float* x, const float* W, const float* b, float* y, int64_t B, int64_t K, int64_t N, void* stream) {

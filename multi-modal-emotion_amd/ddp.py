@@ -343,6 +343,9 @@ class GraphedStep:
 
     def __init__(self, stepper, forward_loss, stream=None, segments=4, use_graphs=True, fractions=None, mode="chain", tail_bf16=False, shard_optimizer=False):
         from . import runtime
+        if runtime.visual_rows() != "equal":
+            raise ValueError("ddp.GraphedStep captures fixed shapes: ragged visual rows (runtime.set_visual_rows('ragged')) run on the eager "
+                             "data-parallel step")
         red = stepper.reducer
         self.red, self.stepper, self.stream = red, stepper, stream
         red.set_manual(True)

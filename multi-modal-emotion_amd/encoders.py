@@ -272,12 +272,22 @@ class VideoEncoder(nn.Module):
                 L.attention.output.dense.weight, L.attention.output.dense.bias, L.layernorm_after.weight, L.layernorm_after.bias,
                 L.intermediate.dense.weight, L.intermediate.dense.bias, L.output.dense.weight, L.output.dense.bias)
 
-    def embed(self, video, bool_masked_pos, nkeep=None):
+    def embed(self, video, bool_masked_pos, nkeep=None, ragged=False):
         """VideoMAEEmbeddings(pixel_values, bool_masked_pos): tokens where bool_masked_pos is False, in order.
-        Returns (x f32 [B*nkeep, H], nkeep).  Every row must keep the same number of tokens (HF's reshape(B,-1,C))."""
+        Returns (x f32 [B*nkeep, H], nkeep).  Every row must keep the same number of tokens (HF's reshape(B,-1,C)).
+        ragged=True: rows keep their own counts; nkeep is the LARGEST count (None: one host read of the B counts), short rows are padded at
+        their end (with copies of their last kept token) and the result is (x [B*nkeep, H], nkeep, kept int32 [B] on the device)."""
         ectx = runtime.ctx()
         _need_cuda(video, "VideoEncoder")
         B = video.shape[0]
+        if ragged:
+            if nkeep is None:
+                nkeep = int((~bool_masked_pos).sum(1).max().item())
+            if not 0 < nkeep <= bool_masked_pos.shape[1]:
+                raise ValueError(f"VideoEncoder.embed: at most {nkeep} kept tokens per row out of {bool_masked_pos.shape[1]}")
+            idx, counts = ops.mask_to_index(bool_masked_pos.contiguous(), False, nkeep)
+            p = self.embeddings.patch_embeddings.projection
+            return E.PatchEmbedFn.apply(video, idx, p.weight, p.bias, self._pos_table, ectx), nkeep, counts
         host_checked = nkeep is None
         if nkeep is None:
             total = int((~bool_masked_pos).sum().item())        # host sync; pass nkeep to avoid it
@@ -299,13 +309,17 @@ class VideoEncoder(nn.Module):
         x = E.PatchEmbedFn.apply(video, idx, p.weight, p.bias, self._pos_table, ectx)
         return x, nkeep
 
-    def forward(self, video, bool_masked_pos, nkeep=None):
-        """VideoMAEModel(pixel_values, bool_masked_pos)[0] with use_mean_pooling=True (no final LayerNorm)."""
+    def forward(self, video, bool_masked_pos, nkeep=None, ragged=False):
+        """VideoMAEModel(pixel_values, bool_masked_pos)[0] with use_mean_pooling=True (no final LayerNorm).
+        ragged=True (see embed): returns (x [B*nkeep, H], nkeep = the largest row, kept int32 [B]); the layers run length-aware."""
         ectx, c = runtime.ctx(), self.cfg
-        x, nkeep = self.embed(video, bool_masked_pos, nkeep)
-        spec = E.LayerSpec(video.shape[0], nkeep, c["heads"], c["eps"], pre_ln=True, mask_mode=0, branch="video")
+        if ragged:
+            x, nkeep, seq_lens = self.embed(video, bool_masked_pos, nkeep, ragged=True)
+        else:
+            (x, nkeep), seq_lens = self.embed(video, bool_masked_pos, nkeep), None
+        spec = E.LayerSpec(video.shape[0], nkeep, c["heads"], c["eps"], pre_ln=True, mask_mode=0, branch="video", seq_lens=seq_lens)
         n = len(self.encoder.layer)
         for i, L in enumerate(self.encoder.layer):
             x = runtime.cut_point("video", i, n, x)
             x, _ = E.encoder_layer(ectx, spec, x, None, None, self._layer_params(L))
-        return x, nkeep
+        return (x, nkeep, seq_lens) if ragged else (x, nkeep)

@@ -244,8 +244,12 @@ def _DGRAD_OUT(pol):
 
 # ---------------------------------------------------------------------------------------------- encoder layer
 class LayerSpec:
-    def __init__(self, B, S, nheads, eps, pre_ln, mask_mode=0, branch=None, head_scale=None, probs_out=None):
+    def __init__(self, B, S, nheads, eps, pre_ln, mask_mode=0, branch=None, head_scale=None, probs_out=None, seq_lens=None):
         self.B, self.S, self.nheads, self.eps, self.pre_ln, self.mask_mode, self.branch = B, S, nheads, eps, pre_ln, mask_mode, branch
+        # seq_lens: None, or int32 [B] on the device -- batch entry b holds seq_lens[b] valid tokens of its S (padding at the end of the
+        # row); attention runs length-aware (ops.attn_fwd / attn_bwd), every row-wise op runs on the padded rows, whose content never
+        # reaches a valid row and whose gradient comes out zero
+        self.seq_lens = seq_lens
         # slow-path options of the fusion encoder (reference utils/TAVFormer.py:190, :368-370, :389; never set by the training loop):
         # head_scale: f32 [nheads] / [B, nheads] factor on the softmax part of the context (head_mask); probs_out: list that receives the
         # layer's attention probabilities [B, nheads, S, S] f32 (output_attentions; detached)
@@ -315,7 +319,8 @@ class EncoderLayerFn(torch.autograd.Function):
             a = x_lp if x_lp is not None else _to_lp(pol, x)
             mean1 = rstd1 = None
         qkv = ops.gemm_nt(a, wqkv, bias=bqkv)
-        o, lse, aux = ops.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=QSC is not None)
+        o, lse, aux = ops.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=QSC is not None,
+                                   seq_lens=spec.seq_lens)
         hs, o_ctx = spec.head_scale, o
         if hs is not None:                                      # head_mask: context = m_h * softmax(s) v (+ the rank-1 mask term, unscaled)
             if spec.mask_mode == 2:
@@ -385,7 +390,7 @@ class EncoderLayerFn(torch.autograd.Function):
         qs, ks, vs, pre = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], QSC is not None
         if hs is None:
             dqkv = ops.attn_bwd(qs, ks, vs, o, do, lse, (corr, o_soft) if spec.mask_mode == 2 else None,
-                                B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=pre)
+                                B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=pre, seq_lens=spec.seq_lens)
         elif spec.mask_mode == 2:
             # context = o + (m_h - 1) o_soft: the whole of dO goes through the usual backward, (m_h - 1) dO once more through the softmax part alone
             dqkv = ops.attn_bwd(qs, ks, vs, o, do, lse, (corr, o_soft), B, S, nh, key_mask=key_mask, mask_mode=2, q_prescaled=pre)
@@ -571,6 +576,11 @@ def encoder_layer(ectx, spec, x, x_lp, key_mask, params):
     fn = EncoderLayerFp8Fn if (ectx.pol.fp8 and spec.branch in ectx.pol.fp8_stacks) else EncoderLayerFn
     if fn is EncoderLayerFp8Fn and (spec.head_scale is not None or spec.probs_out is not None):
         raise NotImplementedError("head_mask / output_attentions are built for the bf16 and fp32 policies only")
+    if spec.seq_lens is not None:
+        if fn is EncoderLayerFp8Fn:
+            raise ValueError("per-row sequence lengths (seq_lens) are built for the bf16 and fp32 policies only, not fp8")
+        if spec.head_scale is not None or spec.probs_out is not None:
+            raise NotImplementedError("head_mask / output_attentions are not built for per-row sequence lengths (seq_lens)")
     x2, x2_lp = fn.apply(x, x_lp, key_mask, ectx, spec, *params)
     return x2, (x2_lp if x2_lp.numel() else None)
 
@@ -966,9 +976,12 @@ class TailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, av_seq, t_pooled, aud_seq, vid_seq, B, S_av, S_aud, S_vid, p_drop, seed, rand_w, rand_b, bert_w, bert_b, aud_w, aud_b,
-                vid_w, vid_b, lin_w, lin_b):
+                vid_w, vid_b, lin_w, lin_b, av_lens=None, vid_lens=None):
+        """av_lens / vid_lens (optional, int32 [B] on the device): per-row valid lengths of the fusion / video streams (ragged visual rows):
+        their pools average the first av_lens[b] / vid_lens[b] rows of each S_av / S_vid-row slice."""
         W = 768
-        pooled = [ops.mean_pool_fwd(_c(av_seq), B, S_av), _c(t_pooled), ops.mean_pool_fwd(_c(aud_seq), B, S_aud), ops.mean_pool_fwd(_c(vid_seq), B, S_vid)]
+        pooled = [ops.mean_pool_fwd(_c(av_seq), B, S_av, seq_lens=av_lens), _c(t_pooled), ops.mean_pool_fwd(_c(aud_seq), B, S_aud),
+                  ops.mean_pool_fwd(_c(vid_seq), B, S_vid, seq_lens=vid_lens)]
         norms = [(rand_w, rand_b), (bert_w, bert_b), (aud_w, aud_b), (vid_w, vid_b)]
         cat = torch.empty(B, 4 * W, dtype=torch.float32, device=av_seq.device)
         stats = []
@@ -982,6 +995,7 @@ class TailFn(torch.autograd.Function):
             feat, mask = ops.dropout_fwd(cat, p_drop, seed, 0)
         logits = ops.head_fwd(feat, lin_w.detach(), lin_b.detach())
         ctx.geom = (B, S_av, S_aud, S_vid, p_drop)
+        ctx.lens = (av_lens, vid_lens)
         ctx.save_for_backward(feat, mask, lin_w, *pooled, *stats, rand_w, rand_b, bert_w, bert_b, aud_w, aud_b, vid_w, vid_b)
         return logits
 
@@ -1001,10 +1015,11 @@ class TailFn(torch.autograd.Function):
             dx, _, dg, dbt = ops.ln_bwd(dy, pooled[j], nw[2 * j], nw[2 * j + 1], stats[2 * j], stats[2 * j + 1], want_f32=True)
             dpool.append(dx)
             dparams += [dg, dbt]
-        d_av, _ = ops.mean_pool_bwd(dpool[0], B, S_av)
+        av_lens, vid_lens = ctx.lens
+        d_av, _ = ops.mean_pool_bwd(dpool[0], B, S_av, seq_lens=av_lens)
         d_aud, _ = ops.mean_pool_bwd(dpool[2], B, S_aud)
-        d_vid, _ = ops.mean_pool_bwd(dpool[3], B, S_vid)
-        return (d_av, dpool[1], d_aud, d_vid, None, None, None, None, None, None, *dparams, dW, db)
+        d_vid, _ = ops.mean_pool_bwd(dpool[3], B, S_vid, seq_lens=vid_lens)
+        return (d_av, dpool[1], d_aud, d_vid, None, None, None, None, None, None, *dparams, dW, db, None, None)
 
 
 class HeadFn(torch.autograd.Function):
@@ -1032,7 +1047,8 @@ class HeadFn(torch.autograd.Function):
 
 class PoolNormCatFn(torch.autograd.Function):
     """cat_j LN_j(pool_j(x_j)) for a list of branches, each either already pooled [B, 768] or a sequence [B*S_j, 768] that is
-    mean-pooled over its S_j tokens first (models/tav.py:478-495 without the fusion branch)."""
+    mean-pooled over its S_j tokens first (models/tav.py:478-495 without the fusion branch).  seq_lens[j] may also be a pair
+    (S_j, lens_j), lens_j int32 [B] on the device: row b of that branch is pooled over its first lens_j[b] tokens only."""
 
     @staticmethod
     def forward(ctx, B, seq_lens, *args):
@@ -1040,7 +1056,8 @@ class PoolNormCatFn(torch.autograd.Function):
         xs, params = args[:n], args[n:]
         pooled, stats, outs = [], [], []
         for j in range(n):
-            xp = _c(xs[j]) if seq_lens[j] == 0 else ops.mean_pool_fwd(_c(xs[j]), B, seq_lens[j])
+            S_j, lens_j = seq_lens[j] if isinstance(seq_lens[j], tuple) else (seq_lens[j], None)
+            xp = _c(xs[j]) if S_j == 0 else ops.mean_pool_fwd(_c(xs[j]), B, S_j, seq_lens=lens_j)
             y, _, mean, rstd = ops.ln_fwd(xp, params[2 * j], params[2 * j + 1], 1e-5, want_f32=True)
             pooled.append(xp)
             stats += [mean, rstd]
@@ -1060,8 +1077,9 @@ class PoolNormCatFn(torch.autograd.Function):
         for j in range(n):
             dy = ops.cast2d(g[:, j * W:(j + 1) * W], torch.float32)
             dx, _, dg, dbt = ops.ln_bwd(dy, pooled[j], params[2 * j], params[2 * j + 1], stats[2 * j], stats[2 * j + 1], want_f32=True)
-            if seq_lens[j]:
-                dx, _ = ops.mean_pool_bwd(dx, B, seq_lens[j])
+            S_j, lens_j = seq_lens[j] if isinstance(seq_lens[j], tuple) else (seq_lens[j], None)
+            if S_j:
+                dx, _ = ops.mean_pool_bwd(dx, B, S_j, seq_lens=lens_j)
             dxs.append(dx)
             dparams += [dg, dbt]
         return (None, None, *dxs, *dparams)

@@ -33,6 +33,28 @@ def _dev(device):
     return d
 
 
+def visual_true_counts(visual_mask, n_visual_true=None):
+    """Per-row number of True entries of visual_mask (the tokens the fusion stack sees) as a host list, or an int when every row has the
+    same count.  n_visual_true: an int, a per-row sequence, or None (ragged mode: one host read of the B counts; equal mode: None back,
+    the video encoder counts and checks as it always did).  In equal mode unequal per-row counts are an error."""
+    B = visual_mask.shape[0]
+    if n_visual_true is None:
+        if runtime.visual_rows() != "ragged":
+            return None
+        n_visual_true = visual_mask.sum(1).cpu().tolist()
+    if isinstance(n_visual_true, (int, np.integer)):
+        return int(n_visual_true)
+    counts = [int(c) for c in (n_visual_true.tolist() if torch.is_tensor(n_visual_true) else n_visual_true)]
+    if len(counts) != B:
+        raise ValueError(f"n_visual_true has {len(counts)} entries for a batch of {B}")
+    if all(c == counts[0] for c in counts):
+        return counts[0]
+    if runtime.visual_rows() != "ragged":
+        raise ValueError(f"visual mask keeps {counts} True tokens per row; every row must keep the same number "
+                         "(runtime.set_visual_rows('ragged') trains on unequal rows)")
+    return counts
+
+
 class PreFormer(nn.Module):
     """Modality front-ends (reference models/tav.py:249-417)."""
 
@@ -111,7 +133,9 @@ class PreFormer(nn.Module):
 
     def forward(self, input_ids=None, audio_features=None, video_embeds=None, text_mask=None, audio_mask=None, visual_mask=None,
                 device="cpu", train=False, n_visual_true=None):
-        """n_visual_true (optional): number of True entries per row of visual_mask; passing it avoids one host sync."""
+        """n_visual_true (optional): number of True entries per row of visual_mask (an int, or per row in ragged mode); passing it avoids one
+        host sync.  Ragged mode with unequal rows: the video segment (last) is max_b n_true_b tokens long, padded at the end of each row
+        (tav_embed 2, attention_mask 0 there)."""
         dev = _dev(device if str(device) != "cpu" else None)
         ectx = runtime.ctx()
         if audio_features.is_cuda:
@@ -120,12 +144,17 @@ class PreFormer(nn.Module):
         parts = []
         St = 0
         audio_features, video_embeds, visual_mask = audio_features.to(dev, torch.float32), video_embeds.to(dev, torch.float32), visual_mask.to(dev)
+        nt = visual_true_counts(visual_mask, n_visual_true)
+        ragged = isinstance(nt, list)
         Sa = self.wav2vec2.conv_out_len(audio_features.shape[1])
         if audio_mask is not None:
             audio_mask = self._get_feature_vector_attention_mask(Sa, audio_mask.to(dev))     # :355 bool [B, Sa]
 
         def video_frontend():
-            xv, nv = self.videomae.embed(video_embeds, ~visual_mask, n_visual_true)    # :368
+            if ragged:
+                xv, nv, _ = self.videomae.embed(video_embeds, ~visual_mask, max(nt), ragged=True)
+            else:
+                xv, nv = self.videomae.embed(video_embeds, ~visual_mask, nt)          # :368
             if hasattr(self, "vid_2_768"):
                 xv = E.LinearFn.apply(xv, None, self.vid_2_768.weight, self.vid_2_768.bias, None, ectx, True)
             return xv, nv
@@ -235,12 +264,23 @@ class TAVForMAE(nn.Module):
         dev = _dev(hidden_states.device if hidden_states.is_cuda else None)
         B, Sf, _ = hidden_states.shape
         ectx = runtime.ctx()
-        nkeep = None if n_visual_true is None else visual_mask.shape[1] - n_visual_true
         audio_features, video_embeds = audio_features.to(dev, torch.float32), video_embeds.to(dev, torch.float32)
         visual_mask, input_ids, text_attention_mask = visual_mask.to(dev), input_ids.to(dev), text_attention_mask.to(dev)
+        nt = visual_true_counts(visual_mask, n_visual_true)
+        ragged = isinstance(nt, list)           # (ragged mode with unequal rows; equal rows take the equal path, bit for bit)
+        ntok = visual_mask.shape[1]
+        nkeep = None if nt is None else ntok - (min(nt) if ragged else nt)
+        vid_lens = av_lens = None
+        if ragged:
+            # fusion rows: St + Sa + n_true_b valid tokens of Sf (the video segment is last); formed on the device, no copy
+            av_lens = (visual_mask.sum(1) + (Sf - max(nt))).to(torch.int32)
 
         def video_branch():
-            v, sv = self.videomae(video_embeds, visual_mask, nkeep)                      # :480
+            nonlocal vid_lens
+            if ragged:
+                v, sv, vid_lens = self.videomae(video_embeds, visual_mask, nkeep, ragged=True)      # ntok - n_true_b per row
+            else:
+                v, sv = self.videomae(video_embeds, visual_mask, nkeep)                  # :480
             if hasattr(self, "vid_2_768_2"):
                 v = E.LinearFn.apply(v, None, self.vid_2_768_2.weight, self.vid_2_768_2.bias, None, ectx, True)
             return v, sv
@@ -273,17 +313,19 @@ class TAVForMAE(nn.Module):
             vid, Sv = video_branch()
             _, t = self.bert(input_ids, text_attention_mask)
         av = E.EmbedAddFn.apply(hidden_states.to(dev).reshape(B * Sf, 768), pos_embed.to(dev).reshape(-1).contiguous(), self.embedding.weight)   # :474
-        av = self.random_mae_encoder(av.view(B, Sf, 768), attention_mask.to(dev))       # :487 (fusion branch stays on the caller's stream)
+        av = self.random_mae_encoder(av.view(B, Sf, 768), attention_mask.to(dev), seq_lens=av_lens)     # :487 (fusion branch stays on the caller's stream)
         if runtime.multistream[0]:
             for st, ten in ((s_aud, aud), (s_vid, vid), (s_txt, t)):
                 runtime.stream_wait(main, st)
                 ten.record_stream(main)
+            if vid_lens is not None:
+                vid_lens.record_stream(main)
         p_drop = self.dropout_p if check == "train" else 0.0
         seed, = runtime.dropout_seeds(self, "_drop_calls", draw=p_drop > 0.0)        # (a device word under a capture)
         return E.TailFn.apply(av.reshape(B * Sf, 768), t, aud, vid, B, Sf, Sa, Sv, p_drop, seed,
                               self.rand_norm.weight, self.rand_norm.bias, self.bert_norm.weight, self.bert_norm.bias,
                               self.aud_norm.weight, self.aud_norm.bias, self.vid_norm.weight, self.vid_norm.bias,
-                              self.linear1.weight, self.linear1.bias)                   # :486-499
+                              self.linear1.weight, self.linear1.bias, av_lens, vid_lens)   # :486-499
 
 
 def remap_reference_keys(state_dict):
@@ -309,12 +351,24 @@ def remap_reference_keys(state_dict):
     return out
 
 
-def collate_batch(batch, check):
+def _draw_visual_mask(B, ntok):
+    """reference :207-209: True w.p. 1/15 per token, drawn on the host (per-row counts Binomial(ntok, 1/15), unequal)."""
+    m = torch.randint(-13, 2, (B, ntok))
+    m[m < 0] = 0
+    return m.bool()
+
+
+def collate_batch(batch, check, visual_rows="equal"):
     """Batch assembly contract of reference models/tav.py:174-246 for ALREADY DECODED items
     ([{'input_ids','attention_mask'}, waveform 1-D tensor, video [16,3,224,224] (or [3,16,H,W])], label).
     Reproduces: random video token mask True w.p. 1/15 (:207-209) then flips so every row keeps the same number of False
     (the reference only equalises the total, which breaks batch>1 -- SURVEY.md 'Hard parts'); zero padding of audio with a
-    0/1 mask (:225-228); labels as float tensor."""
+    0/1 mask (:225-228); labels as float tensor.
+    visual_rows="ragged": the video mask is drawn exactly as :207-209 and left as drawn -- every row keeps its own count (train with
+    runtime.set_visual_rows("ragged")).  The reference's fix-up of the batch TOTAL (:211-217) only exists to make its reshape(B, -1, C) legal
+    and is not applied."""
+    if visual_rows not in ("equal", "ragged"):
+        raise ValueError(f"visual_rows must be 'equal' or 'ragged', got {visual_rows!r}")
     texts, masks, speech, vids, labels = [], [], [], [], []
     for (inp, label) in batch:
         texts.append(torch.as_tensor(inp[0]["input_ids"]).reshape(-1))
@@ -325,11 +379,9 @@ def collate_batch(batch, check):
         labels.append(label)
     B = len(labels)
     ntok = (vids[0].shape[0] // 2) * (vids[0].shape[2] // 16) * (vids[0].shape[3] // 16)
-    vid_mask = torch.randint(-13, 2, (B, ntok))
-    vid_mask[vid_mask < 0] = 0
-    vid_mask = vid_mask.bool()
+    vid_mask = _draw_visual_mask(B, ntok)
     target = int(vid_mask.sum(1).max().item())
-    for b in range(B):                                   # equal per-row counts (needed for reshape(B,-1,C) semantics)
+    for b in range(B if visual_rows == "equal" else 0):                                   # equal per-row counts (needed for reshape(B,-1,C) semantics)
         short = target - int(vid_mask[b].sum().item())
         if short > 0:
             idx = torch.where(~vid_mask[b])[0]
@@ -358,10 +410,14 @@ def sample_video_mask(B, ntok, n_true=None, device="cpu", generator=None):
     return torch.zeros(B, ntok, dtype=torch.bool, device=device).scatter_(1, idx, True)
 
 
-def collate_batch_device(batch, check, device="cuda", n_visual_true=None, generator=None):
+def collate_batch_device(batch, check, device="cuda", n_visual_true=None, generator=None, visual_rows="equal"):
     """collate_batch with the tensor work on `device`: items are decoded utterances as for collate_batch; every
     tensor is shipped once (non-blocking) and padding, the audio length mask (reference :225-228) and the video token mask are built
-    there, sync-free: nothing in the step reads them back (PreFormer / TAVForMAE take `n_visual_true` instead of counting)."""
+    there, sync-free: nothing in the step reads them back (PreFormer / TAVForMAE take `n_visual_true` instead of counting).
+    visual_rows="ragged": the video mask is drawn on the HOST as in collate_batch(visual_rows="ragged") and shipped; its per-row True
+    counts come back as visual["n_visual_true"] (a list), to be passed on as n_visual_true -- known without a device read."""
+    if visual_rows not in ("equal", "ragged"):
+        raise ValueError(f"visual_rows must be 'equal' or 'ragged', got {visual_rows!r}")
     texts, masks, speech, vids, labels = [], [], [], [], []
     for (inp, label) in batch:
         texts.append(torch.as_tensor(inp[0]["input_ids"]).reshape(-1))
@@ -378,8 +434,13 @@ def collate_batch_device(batch, check, device="cuda", n_visual_true=None, genera
     amask = (torch.arange(T, device=dev)[None, :] < lens.to(dev, non_blocking=True)[:, None]).float()
     video = torch.stack([v.to(dev, non_blocking=True) for v in vids])
     ntok = (video.shape[1] // 2) * (video.shape[3] // 16) * (video.shape[4] // 16)
-    vid_mask = sample_video_mask(B, ntok, n_visual_true, dev, generator)
+    visual = {"visual_embeds": video}
+    if visual_rows == "ragged":
+        m = _draw_visual_mask(B, ntok)
+        visual["attention_mask"], visual["n_visual_true"] = m.to(dev, non_blocking=True), m.sum(1).tolist()
+    else:
+        visual["attention_mask"] = sample_video_mask(B, ntok, n_visual_true, dev, generator)
     text = {"input_ids": torch.stack(texts).long().to(dev, non_blocking=True), "attention_mask": torch.stack(masks).to(dev, non_blocking=True)}
-    return [text, {"audio_features": audio, "attention_mask": amask}, {"visual_embeds": video, "attention_mask": vid_mask}], \
+    return [text, {"audio_features": audio, "attention_mask": amask}, visual], \
         torch.tensor(labels, dtype=torch.float32).to(dev, non_blocking=True)
 

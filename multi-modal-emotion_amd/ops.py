@@ -310,9 +310,18 @@ def _attn_args(q, k, v, o, B, S, nheads, key_mask, lse, corr, mask_mode, scale, 
 ATTN_Q_PRESCALE = 0.125 * 1.4426950408889634      # what a prescaled q carries: softmax scale (head dim 64) x log2(e)
 
 
-def attn_fwd(q, k, v, B, S, nheads, *, key_mask=None, mask_mode=0, scale=0.125, q_prescaled=False):
+def _seq_lens(seq_lens, B, device):
+    """Per-row valid lengths of a length-aware launch: an int32 [B] tensor on the attention's device (a bad one is an error, not a copy)."""
+    if not (isinstance(seq_lens, torch.Tensor) and seq_lens.dtype == torch.int32 and seq_lens.device == device and seq_lens.numel() == B
+            and seq_lens.is_contiguous()):
+        raise ValueError(f"seq_lens must be a contiguous int32 tensor of {B} entries on {device}, got {seq_lens!r}")
+    return seq_lens
+
+
+def attn_fwd(q, k, v, B, S, nheads, *, key_mask=None, mask_mode=0, scale=0.125, q_prescaled=False, seq_lens=None):
     """q,k,v: [B*S, >=nheads*64] views (row stride arbitrary).  Returns o [B*S, nheads*64], lse, corr.
-    q_prescaled: q already holds q * scale * log2(e) (tav_attn_args.q_prescaled)."""
+    q_prescaled: q already holds q * scale * log2(e) (tav_attn_args.q_prescaled).
+    seq_lens: None, or int32 [B] on the device: row b holds L_b valid tokens of its S (tav_attn_fwd_len; rows past L_b come out zero)."""
     H = nheads * 64
     o = torch.empty(B * S, H, dtype=q.dtype, device=q.device)
     lse = torch.empty(B, nheads, S, dtype=torch.float32, device=q.device)
@@ -320,13 +329,19 @@ def attn_fwd(q, k, v, B, S, nheads, *, key_mask=None, mask_mode=0, scale=0.125, 
     o_soft = torch.empty_like(o) if mask_mode == 2 else None
     a = _attn_args(q, k, v, o, B, S, nheads, key_mask, lse, corr, mask_mode, scale, o_soft, q_prescaled)
     es = q.element_size()
+    if seq_lens is None:
+        run = lambda: check(lib().tav_attn_fwd(C.byref(a), stream()), "attn_fwd")      # noqa: E731
+    else:
+        sl = _seq_lens(seq_lens, B, q.device)
+        run = lambda: check(lib().tav_attn_fwd_len(C.byref(a), ptr(sl), stream()), "attn_fwd_len")      # noqa: E731
     _prof_launch("attn", "bf16" if q.dtype == torch.bfloat16 else "f32", 4.0 * B * nheads * S * S * 64, 4 * B * S * H * es,      # Q, K, V, O once
-                 lambda: check(lib().tav_attn_fwd(C.byref(a), stream()), "attn_fwd"))
+                 run)
     return o, lse, (corr, o_soft)
 
 
-def attn_bwd(q, k, v, o, dout, lse, corr, B, S, nheads, *, key_mask=None, mask_mode=0, scale=0.125, dqkv=None, q_prescaled=False):
-    """Returns dqkv [B*S, 3H] (dq | dk | dv), the layout the fused QKV projection's backward consumes."""
+def attn_bwd(q, k, v, o, dout, lse, corr, B, S, nheads, *, key_mask=None, mask_mode=0, scale=0.125, dqkv=None, q_prescaled=False, seq_lens=None):
+    """Returns dqkv [B*S, 3H] (dq | dk | dv), the layout the fused QKV projection's backward consumes.
+    seq_lens: as in attn_fwd (tav_attn_bwd_len; dq / dk / dv rows past L_b come out zero)."""
     H = nheads * 64
     if dqkv is None:
         dqkv = torch.empty(B * S, 3 * H, dtype=q.dtype, device=q.device)
@@ -339,8 +354,13 @@ def attn_bwd(q, k, v, o, dout, lse, corr, B, S, nheads, *, key_mask=None, mask_m
     es = q.element_size()
     # algorithmic work by the contract (BASELINE.md section 2 / SURVEY.md section 8d: fwd + bwd = 3 x fwd, so the backward is 2 x 4 B h S^2 d); the two
     # atomic-free kernels EXECUTE 14 B h S^2 d (S and dP are recomputed in both), reported beside it as `frac_executed`
+    if seq_lens is None:
+        run = lambda: check(lib().tav_attn_bwd(C.byref(a), stream()), "attn_bwd")      # noqa: E731
+    else:
+        sl = _seq_lens(seq_lens, B, q.device)
+        run = lambda: check(lib().tav_attn_bwd_len(C.byref(a), ptr(sl), stream()), "attn_bwd_len")      # noqa: E731
     _prof_launch("attn", "bf16" if q.dtype == torch.bfloat16 else "f32", 8.0 * B * nheads * S * S * 64, 8 * B * S * H * es,     # Q, K, V, O, dO in; dQ, dK, dV out
-                 lambda: check(lib().tav_attn_bwd(C.byref(a), stream()), "attn_bwd"), work_exec=14.0 * B * nheads * S * S * 64)
+                 run, work_exec=14.0 * B * nheads * S * S * 64)
     return dqkv
 
 
@@ -620,18 +640,27 @@ def patchify(video, keep_idx, dtype):
     return out
 
 
-def mean_pool_fwd(x, B, S):
+def mean_pool_fwd(x, B, S, *, seq_lens=None):
+    """y[b] = mean over the S rows of batch entry b, or over its first seq_lens[b] (int32 [B] on the device; tav_mean_pool_fwd_len)."""
     W = x.shape[-1]
     y = torch.empty(B, W, dtype=torch.float32, device=x.device)
-    check(lib().tav_mean_pool_fwd(ptr(x), ptr(y), B, S, W, stream()), "mean_pool_fwd")
+    if seq_lens is None:
+        check(lib().tav_mean_pool_fwd(ptr(x), ptr(y), B, S, W, stream()), "mean_pool_fwd")
+    else:
+        check(lib().tav_mean_pool_fwd_len(ptr(x), ptr(y), ptr(_seq_lens(seq_lens, B, x.device)), B, S, W, stream()), "mean_pool_fwd_len")
     return y
 
 
-def mean_pool_bwd(dy, B, S, *, want_f32=True, lp_dtype=None):
+def mean_pool_bwd(dy, B, S, *, want_f32=True, lp_dtype=None, seq_lens=None):
     W = dy.shape[-1]
     dx = torch.empty(B * S, W, dtype=torch.float32, device=dy.device) if want_f32 else None
     dxlp = torch.empty(B * S, W, dtype=lp_dtype, device=dy.device) if lp_dtype is not None else None
-    check(lib().tav_mean_pool_bwd(ptr(dy), ptr(dx), ptr(dxlp), dt(lp_dtype) if lp_dtype is not None else 0, B, S, W, stream()), "mean_pool_bwd")
+    lp = dt(lp_dtype) if lp_dtype is not None else 0
+    if seq_lens is None:
+        check(lib().tav_mean_pool_bwd(ptr(dy), ptr(dx), ptr(dxlp), lp, B, S, W, stream()), "mean_pool_bwd")
+    else:
+        check(lib().tav_mean_pool_bwd_len(ptr(dy), ptr(dx), ptr(dxlp), lp, ptr(_seq_lens(seq_lens, B, dy.device)), B, S, W, stream()),
+              "mean_pool_bwd_len")
     return dx, dxlp
 
 

@@ -22,6 +22,22 @@ def precision():
     return ctx().pol.name
 
 
+# ---- visual rows: "equal" (every row of a batch keeps the same number of video tokens; unequal rows raise ValueError) or "ragged"
+# (each utterance keeps its own count: the video and fusion stacks run on padded rows with per-row lengths)
+_visual_rows = ["equal"]
+
+
+def set_visual_rows(mode="equal"):
+    if mode not in ("equal", "ragged"):
+        raise ValueError(f"visual rows must be 'equal' or 'ragged', got {mode!r}")
+    _visual_rows[0] = mode
+    return mode
+
+
+def visual_rows():
+    return _visual_rows[0]
+
+
 # ---- branch streams: text / audio / video encoders run beside the fusion encoder (reference models/tav.py:476-487 are
 # four independent sub-graphs that meet only at the concat, :495).  Autograd replays each branch's backward on the stream its
 # forward used, so the backward overlaps the same way; under hipGraph capture the fork/join becomes parallel graph branches.

@@ -5,7 +5,8 @@ import torch
 
 def make_batch(cfg, batch_size, *, seed=1234, s_text=128, t_audio=80000, n_visual_true=104, device="cpu", text_only=False, with_video=True):
     """Returns ([text, audio, visual] dicts exactly as collate_batch yields them, labels float [B]).  text_only / with_video=False skip
-    the (large) modalities the single- and dual-modal entrypoints do not read (their dicts come back as None)."""
+    the (large) modalities the single- and dual-modal entrypoints do not read (their dicts come back as None).  n_visual_true: True tokens
+    per row of the video mask, an int or one count per row (unequal counts: train with runtime.set_visual_rows("ragged"))."""
     g = torch.Generator(device="cpu").manual_seed(seed)
     tc, vc = cfg["text"], cfg["video"]
     B = batch_size
@@ -29,9 +30,12 @@ def make_batch(cfg, batch_size, *, seed=1234, s_text=128, t_audio=80000, n_visua
                 {"audio_features": audio.to(device), "attention_mask": audio_mask.to(device)}, None], labels.to(device)
     video = torch.randn(B, vc["frames"], 3, vc["image"], vc["image"], generator=g)
     ntok = (vc["image"] // vc["patch"]) ** 2 * (vc["frames"] // vc["tubelet"])
+    nts = [int(n_visual_true)] * B if isinstance(n_visual_true, int) else [int(n) for n in n_visual_true]
+    if len(nts) != B or not all(0 <= n <= ntok for n in nts):
+        raise ValueError(f"n_visual_true {n_visual_true!r}: need {B} counts in [0, {ntok}]")
     vmask = torch.zeros(B, ntok, dtype=torch.bool)
     for b in range(B):
-        vmask[b, torch.randperm(ntok, generator=g)[:n_visual_true]] = True      # exactly n True per row
+        vmask[b, torch.randperm(ntok, generator=g)[:nts[b]]] = True             # exactly n True per row
     labels = torch.randint(0, 7, (B,), generator=g).float()
     text = {"input_ids": ids.to(device), "attention_mask": text_mask.to(device)}
     audio_d = {"audio_features": audio.to(device), "attention_mask": audio_mask.to(device)}

@@ -24,6 +24,9 @@ class SyntheticTAVBatches(Dataset):
 
     def __getitem__(self, i):
         nv = 104 if self.cfg["video"]["image"] == 224 else 4
+        if runtime.visual_rows() == "ragged":     # unequal rows around the same mean (a seeded spread of +-2 tokens)
+            g = torch.Generator().manual_seed(self.seed + i)
+            nv = [nv + int(d) for d in torch.randint(-2, 3, (self.bs,), generator=g)]
         return synthetic.make_batch(self.cfg, self.bs, seed=self.seed + i, s_text=self.s_text, t_audio=self.t_audio, n_visual_true=nv)
 
 
@@ -58,6 +61,7 @@ def main(argv=None):
     torch.random.manual_seed(args.seed)
     C.set_default_preset(args.preset)
     runtime.set_precision(args.dtype)
+    runtime.set_visual_rows(args.visual_rows)
     cfg = C.default_config()
     weights = torch.linspace(0.6, 0.95, args.output_dim)            # reference: 1 - class frequency (tav_nn.py:171)
     id2label = {i: f"class{i}" for i in range(args.output_dim)}

@@ -72,7 +72,8 @@ class VideoMAEEncoder(nn.Module):
         self.gradient_checkpointing = False
 
     def forward(self, hidden_states, attention_mask=None, head_mask=None, output_attentions: bool = False, output_hidden_states: bool = False,
-                return_dict: bool = True):
+                return_dict: bool = True, seq_lens=None):
+        """seq_lens (optional, int32 [B] on the device): row b holds seq_lens[b] valid tokens, padding at the end of the row (ragged visual rows)."""
         if not hidden_states.is_cuda:
             raise RuntimeError("VideoMAEEncoder runs on libtavhip (GPU) only; there is no CPU fallback")
         ectx = runtime.ctx()
@@ -81,7 +82,7 @@ class VideoMAEEncoder(nn.Module):
         if attention_mask is not None:
             key_mask = attention_mask.reshape(B, S).to(torch.float32).contiguous()      # [B,1,1,S] broadcast over heads and queries
             mode = 2
-        spec = E.LayerSpec(B, S, self.num_heads, self.eps, pre_ln=True, mask_mode=mode, branch="fusion")
+        spec = E.LayerSpec(B, S, self.num_heads, self.eps, pre_ln=True, mask_mode=mode, branch="fusion", seq_lens=seq_lens)
         x = hidden_states.reshape(B * S, H)
         all_hidden = () if output_hidden_states else None
         all_attn = [] if output_attentions else None
@@ -95,7 +96,7 @@ class VideoMAEEncoder(nn.Module):
                 # added, and the probabilities themselves as a (detached) f32 tensor.  The training loop never asks for either.
                 lspec = E.LayerSpec(B, S, self.num_heads, self.eps, pre_ln=True, mask_mode=mode, branch="fusion",
                                     head_scale=self._head_scale(head_mask[i], B) if head_mask is not None and head_mask[i] is not None else None,
-                                    probs_out=all_attn)
+                                    probs_out=all_attn, seq_lens=seq_lens)
             x, _ = E.encoder_layer(ectx, lspec, x, None, key_mask, layer.params())
         out = x.view(B, S, H)
         if output_hidden_states:

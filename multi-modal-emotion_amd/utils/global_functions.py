@@ -168,6 +168,8 @@ def arg_parse(description, argv=None):
     parser.add_argument("--preset", default="A", help="model geometry: A (reference names) | B (BASELINE trio) | *-tiny")
     parser.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     parser.add_argument("--synthetic", default=64, type=int, help="number of synthetic utterances per split (no dataset files are read)")
+    parser.add_argument("--visual-rows", dest="visual_rows", default="equal", choices=["equal", "ragged"],
+                        help="ragged: every utterance keeps its own number of visible video tokens (runtime.set_visual_rows)")
     parser.add_argument("--graph", default=0, type=int, choices=[0, 1],
                         help="1: replay each training step from a captured hipGraph (tav_nn only; train_tav_network(graphs=True))")
     return parser.parse_args(argv)
