@@ -230,12 +230,16 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
     int t1 = t0 + per; t1 = t1 < Tn ? t1 : Tn;
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
     f32x4 mean = a0, rstd = a0, gam = a0, bet = a0;
+    // forward: sums of (x - pivot) and (x - pivot)^2, pivot = the entry's first row (the same in every split).  E[x^2] - mean^2 on the raw
+    // values loses the variance to cancellation when it is small beside mean^2 (a handful of steps per channel: 3e-4 on the output at T = 2).
+    f32x4 pivot = a0;
+    if (!BWD && live) pivot = ld4(x + (long)b * Tn * C + c);
     if (BWD && live) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) { mean[k] = stats[((long)b * C + c + k) * 2]; rstd[k] = stats[((long)b * C + c + k) * 2 + 1]; gam[k] = gamma[c + k]; bet[k] = beta[c + k]; }
     }
     auto one = [&](f32x4 v, f32x4 dyv) __attribute__((always_inline)) {
-        if (!BWD) { a0 += v; a1 += v * v; }
+        if (!BWD) { const f32x4 d = v - pivot; a0 += d; a1 += d * d; }
         else {
             const f32x4 xh = (v - mean) * rstd;
             f32x4 dz;
@@ -269,17 +273,19 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
         }
     }
 }
-// fwd: stats[b][c] = (mean, rstd);   bwd: sums[b][c] = (sum dz, sum dz*xhat)
-__global__ void gn_finalize_kernel(const float* __restrict__ part, float* out, int Tn, int C, int B, float eps, int fwd) {
+// fwd: stats[b][c] = (mean, rstd) from the pivoted sums (x: the activation, for the pivot);   bwd: sums[b][c] = (sum dz, sum dz*xhat), x unused
+template <typename T>
+__global__ void gn_finalize_kernel(const float* __restrict__ part, float* out, const T* __restrict__ x, int Tn, int C, int B, float eps, int fwd) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long)B * C) return;
     const int b = (int)(idx / C), c = (int)(idx - (long)b * C);
     float s0 = 0.f, s1 = 0.f;
     for (int sp = 0; sp < GN_SPLIT; ++sp) { s0 += part[(((long)b * GN_SPLIT + sp) * C + c) * 2]; s1 += part[(((long)b * GN_SPLIT + sp) * C + c) * 2 + 1]; }
     if (fwd) {
-        const float mean = s0 / Tn;
-        float var = s1 / Tn - mean * mean; var = var > 0.f ? var : 0.f;
-        out[idx * 2] = mean; out[idx * 2 + 1] = rsqrtf(var + eps);
+        const f32x4 pq = ld4(x + (long)b * Tn * C + (c & ~3));
+        const float m = s0 / Tn;                             // mean - pivot
+        float var = s1 / Tn - m * m; var = var > 0.f ? var : 0.f;
+        out[idx * 2] = pq[c & 3] + m; out[idx * 2 + 1] = rsqrtf(var + eps);
     } else { out[idx * 2] = s0; out[idx * 2 + 1] = s1; }
 }
 // Apply passes: thread = 4 channels (one 8-B / 16-B access per row) x GN_AR rows at a stride of 4, so the per-(batch, channel) statistics
@@ -472,7 +478,8 @@ extern "C" int tav_gn_gelu_fwd(const void* x, void* y, int32_t dtype, const floa
     if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_stats_kernel<bf16, false>), grid, dim3(256), 0, st, (const bf16*)x, (const bf16*)nullptr, gamma, beta, stats, workspace, (int)T, (int)C);
     else if (dtype == TAV_F32) hipLaunchKernelGGL((gn_stats_kernel<float, false>), grid, dim3(256), 0, st, (const float*)x, (const float*)nullptr, gamma, beta, stats, workspace, (int)T, (int)C);
     else return TAV_ERR_DTYPE;
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, stats, (int)T, (int)C, (int)B, eps, 1);
+    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_finalize_kernel<bf16>), dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, stats, (const bf16*)x, (int)T, (int)C, (int)B, eps, 1);
+    else hipLaunchKernelGGL((gn_finalize_kernel<float>), dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, stats, (const float*)x, (int)T, (int)C, (int)B, eps, 1);
     if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_apply_fwd_kernel<bf16>), agrid, dim3(256), 0, st, (const bf16*)x, (bf16*)y, gamma, beta, stats, (int)T, (int)C);
     else hipLaunchKernelGGL((gn_apply_fwd_kernel<float>), agrid, dim3(256), 0, st, (const float*)x, (float*)y, gamma, beta, stats, (int)T, (int)C);
     return (int)hipGetLastError();
@@ -489,7 +496,7 @@ extern "C" int tav_gn_gelu_bwd(const void* x, const void* dy, void* dx, int32_t 
     if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_stats_kernel<bf16, true>), grid, dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, gamma, beta, stats, workspace, (int)T, (int)C);
     else if (dtype == TAV_F32) hipLaunchKernelGGL((gn_stats_kernel<float, true>), grid, dim3(256), 0, st, (const float*)x, (const float*)dy, gamma, beta, stats, workspace, (int)T, (int)C);
     else return TAV_ERR_DTYPE;
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, sums, (int)T, (int)C, (int)B, 0.f, 0);
+    hipLaunchKernelGGL((gn_finalize_kernel<float>), dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, sums, (const float*)nullptr, (int)T, (int)C, (int)B, 0.f, 0);
     hipLaunchKernelGGL(gn_param_grad_kernel, dim3(tav_cdiv(C, 256)), dim3(256), 0, st, sums, dgamma, dbeta, (int)B, (int)C, accumulate);
     if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_apply_bwd_kernel<bf16>), agrid, dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, (bf16*)dx, gamma, beta, stats, sums, (int)T, (int)C);
     else hipLaunchKernelGGL((gn_apply_bwd_kernel<float>), agrid, dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, gamma, beta, stats, sums, (int)T, (int)C);

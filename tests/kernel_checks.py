@@ -3,19 +3,76 @@
 Each check returns (name, max_abs_err, tolerance, ok).  Used by tests/test_kernels_gpu.py (asserts) and by
 tools/gpu_kernel_check.py (prints a table without stopping at the first failure).
 """
+import contextlib
 import math
 
 import torch
 import torch.nn.functional as F
 
+import guarded
 import tav_amd.ops as ops
 
 DEV = "cuda"
 
 
+def _in(t, pitch_extra=0):
+    """Input hook: the identity without a guard; inside guarded.active() the tensor moves into a 0xFF-filled buffer (tests/guarded.py), with
+    pitch_extra > 0 as a strided view whose rows are pitch_extra elements further apart than they are long."""
+    g = guarded.current()
+    if g is not None:
+        return g.input(t, pitch_extra)
+    if not pitch_extra:
+        return t
+    wide = _blank(tuple(t.shape[:-1]) + (t.shape[-1] + pitch_extra,), t.dtype)
+    wide[..., :t.shape[-1]] = t
+    return wide[..., :t.shape[-1]]
+
+
+def _blank(shape, dtype):
+    """A tensor whose every byte is 0xFF (NaN / -1), under guard when one is active: for outputs the checks hand to the library themselves."""
+    g = guarded.current()
+    if g is not None:
+        return g.empty(shape, dtype=dtype, device=DEV)
+    n = 1
+    for s_ in shape:
+        n *= s_
+    return torch.full((n * dtype.itemsize,), 0xFF, dtype=torch.uint8, device=DEV).view(dtype).view(shape)
+
+
+def _all_ff(name, *tensors):
+    """Result tuple: every byte of these (possibly strided) tensors is still 0xFF -- nothing stored into them."""
+    bad = sum(int(t.contiguous().view(torch.uint8).ne(0xFF).sum().item()) for t in tensors if t.numel())
+    return (name, float(bad), 0.0, bad == 0)
+
+
+_REF = [torch.float32]
+
+
+def _r(t):
+    """A tensor in the precision the references are computed in: f32 as the checks were written, fp64 inside ref64()."""
+    return t.to(_REF[0])
+
+
+@contextlib.contextmanager
+def ref64():
+    """Inside: every check that builds its reference through _r() computes it in fp64 (the edge cases do)."""
+    old, _REF[0] = _REF[0], torch.float64
+    try:
+        yield
+    finally:
+        _REF[0] = old
+
+
+def _in64(fn):
+    def run():
+        with ref64():
+            return fn()
+    return run
+
+
 def _rnd(*shape, dtype=torch.float32, scale=1.0, seed=0):
     g = torch.Generator(device="cpu").manual_seed(seed + sum(shape))
-    return (torch.randn(*shape, generator=g) * scale).to(DEV).to(dtype)
+    return _in((torch.randn(*shape, generator=g) * scale).to(DEV).to(dtype))
 
 
 def _res(name, got, ref, tol):
@@ -224,14 +281,14 @@ def check_conv_as_gemm(dtype, B=2, T_in=203, Cc=64, k=3, s=2):
     wn, wt, _ = ops.cast_conv_weight(w, dtype)
     y, pre = ops.gemm_nt(x, wn, act=1, want_pre=True, M=T_out, N=Cc, K=k * Cc, lda=s * Cc, ldb=k * Cc, ldc=Cc,
                          nzb=B, a_zb=T_in * Cc, c_zb=T_out * Cc, out_shape=(B, T_out, Cc))
-    xr = x.float().permute(0, 2, 1).requires_grad_(True)
-    wr = w.clone().requires_grad_(True)
-    pre_ref = F.conv1d(xr, wr if dtype == torch.float32 else wr.to(dtype).float(), stride=s)
+    xr = _r(x).permute(0, 2, 1).requires_grad_(True)
+    wr = _r(w).clone().requires_grad_(True)
+    pre_ref = F.conv1d(xr, wr if dtype == torch.float32 else _r(wr.to(dtype)), stride=s)
     y_ref = F.gelu(pre_ref)
     tol = 1e-2 if dtype == torch.bfloat16 else 2e-5
     rs = [_res(f"conv_gemm.fwd[{dtype}]", y, y_ref.permute(0, 2, 1), tol)]
     dy = _rnd(B, T_out, Cc, dtype=dtype, seed=12)
-    y_ref.backward(dy.float().permute(0, 2, 1))
+    y_ref.backward(_r(dy).permute(0, 2, 1))
     du = ops.gelu_bwd(pre, dy)
     dcol = ops.gemm_nt(du.view(B * T_out, Cc), wt, out_shape=(B * T_out, k * Cc))
     dx = ops.col2im_1d(dcol, B, T_in, T_out, Cc, k, s)
@@ -307,7 +364,7 @@ def check_attention(dtype, mode, B=2, S=200, nh=3, bwd=True, ref_style_mask=Fals
     H = nh * 64
     qkv = _rnd(B * S, 3 * H, dtype=dtype, seed=20 + mode)
     if spike:
-        qkv = qkv.float()
+        qkv = qkv.float().clone()
         for row in {min(S - 1, 3), S // 2, max(0, S - 40), S - 1}:
             qkv.view(B, S, 3 * H)[:, row, H:2 * H] *= spike
         qkv = qkv.to(dtype)
@@ -329,6 +386,10 @@ def check_attention(dtype, mode, B=2, S=200, nh=3, bwd=True, ref_style_mask=Fals
             mask[:, S // 4 - 9: S // 4] = -65504.0          # padded text tokens
             mask[:, S // 4: S // 4 + S // 2] = 65505.0      # valid audio frames
             mask[0, S // 4 + S // 2 - 20: S // 4 + S // 2] = 1.0   # padded audio frames of row 0
+    if spike or pre:
+        qkv = _in(qkv)
+    if mask is not None:
+        mask = _in(mask)
     q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
     o, lse, corr = ops.attn_fwd(q, k, v, B, S, nh, key_mask=mask, mask_mode=mode, q_prescaled=pre)
 
@@ -365,17 +426,17 @@ def check_layernorm(x_dtype, W=768, rows=333, act=0):
     gamma = 1.0 + 0.1 * _rnd(W, seed=41)
     beta = 0.1 * _rnd(W, seed=42)
     y32, ylp, mean, rstd = ops.ln_fwd(x, gamma, beta, 1e-5, want_f32=True, lp_dtype=torch.bfloat16, act=act)
-    xr = x.float().requires_grad_(True)
-    gr, br = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    xr = _r(x).requires_grad_(True)
+    gr, br = _r(gamma).clone().requires_grad_(True), _r(beta).clone().requires_grad_(True)
     ref = F.layer_norm(xr, (W,), gr, br, 1e-5)
     if act:
         ref = F.gelu(ref)
     rs = [_res(f"ln.fwd[{x_dtype},W{W},act{act}]", y32, ref, 2e-5), _res("ln.fwd.lp", ylp, ref, 1e-2)]
     dy = _rnd(rows, W, seed=43)
     add = _rnd(rows, W, seed=44)
-    ref.backward(dy)
+    ref.backward(_r(dy))
     dx32, dxlp, dg, db = ops.ln_bwd(dy, x, gamma, beta, mean, rstd, dx_add=add, want_f32=True, lp_dtype=torch.bfloat16, act=act)
-    rs += [_res("ln.dx", dx32, xr.grad + add, 5e-5), _res("ln.dx.lp", dxlp, xr.grad + add, 1e-2),
+    rs += [_res("ln.dx", dx32, xr.grad + _r(add), 5e-5), _res("ln.dx.lp", dxlp, xr.grad + _r(add), 1e-2),
            _res("ln.dgamma", dg, gr.grad, 1e-4), _res("ln.dbeta", db, br.grad, 1e-4)]
     return rs
 
@@ -435,12 +496,12 @@ def check_colsum():
     return [_res("colsum", ops.colsum(x), x.float().sum(0), 1e-5)]
 
 
-def check_text_embed(pad_id=1):
-    B, S, W, V = 3, 50, 768, 1000
+def check_text_embed(pad_id=1, B=3, S=50):
+    W, V = 768, 1000
     g = torch.Generator().manual_seed(5)
     ids = torch.randint(3, V, (B, S), generator=g)
-    ids[:, S - 9:] = 1
-    ids = ids.to(DEV)
+    ids[:, S - min(9, S // 2):] = 1
+    ids = _in(ids.to(DEV))
     word, pos, typ = _rnd(V, W, seed=52), _rnd(S + 10, W, seed=53), _rnd(1, W, seed=54)
     gamma, beta = 1 + 0.1 * _rnd(W, seed=55), 0.1 * _rnd(W, seed=56)
     y32, _, pre, pos_ids, _, _ = ops.text_embed_fwd(ids, word, pos, typ, gamma, beta, 1e-5, pad_id)
@@ -449,67 +510,72 @@ def check_text_embed(pad_id=1):
         pid = (torch.cumsum(m, 1) * m).long() + pad_id
     else:
         pid = torch.arange(S, device=DEV)[None].expand(B, S)
-    ref = F.layer_norm(word[ids] + pos[pid] + typ[0], (W,), gamma, beta, 1e-5).reshape(B * S, W)
+    ref = F.layer_norm(_r(word)[ids] + _r(pos)[pid] + _r(typ)[0], (W,), _r(gamma), _r(beta), 1e-5).reshape(B * S, W)
     return [_res(f"text_embed[pad{pad_id}]", y32, ref, 2e-5), _res("text_embed.pos_ids", pos_ids.float(), pid.float(), 0.0)]
 
 
-def check_patchify(dtype=torch.float32):
-    B, Fr, H, W, nkeep = 2, 4, 32, 48, 5
+def check_patchify(dtype=torch.float32, B=2, nkeep=5):
+    Fr, H, W = 4, 32, 48
     video = _rnd(B, Fr, 3, H, W, seed=57)
     ntok = (Fr // 2) * (H // 16) * (W // 16)
     mask = torch.zeros(B, ntok, dtype=torch.bool)
-    mask[0, [0, 3, 4, 7, 11]] = True
-    mask[1, [1, 2, 5, 9, 10]] = True
-    mask = mask.to(DEV)
+    if (B, nkeep) == (2, 5):
+        mask[0, [0, 3, 4, 7, 11]] = True
+        mask[1, [1, 2, 5, 9, 10]] = True
+    else:
+        g = torch.Generator().manual_seed(59)
+        for b_ in range(B):
+            mask[b_, torch.randperm(ntok, generator=g)[:nkeep]] = True
+    mask = _in(mask.to(DEV))
     idx, counts = ops.mask_to_index(mask, True, nkeep)
     patches = ops.patchify(video, idx, dtype)
     wconv = _rnd(8, 3, 2, 16, 16, scale=0.05, seed=58)
-    emb = F.conv3d(video.permute(0, 2, 1, 3, 4), wconv, stride=(2, 16, 16)).flatten(2).transpose(1, 2)   # [B, ntok, 8]
+    emb = F.conv3d(_r(video).permute(0, 2, 1, 3, 4), _r(wconv), stride=(2, 16, 16)).flatten(2).transpose(1, 2)   # [B, ntok, 8]
     ref = emb[mask].reshape(B * nkeep, 8)
-    got = patches.float() @ wconv.reshape(8, -1).t()
+    got = _r(patches) @ _r(wconv).reshape(8, -1).t()
     return [_res("patchify+gemm", got, ref, 1e-4), _res("mask_to_index.counts", counts.float(), torch.full((B,), float(nkeep), device=DEV), 0.0)]
 
 
-def check_pool_head_ce():
-    B, S, W = 3, 77, 768
+def check_pool_head_ce(B=3, S=77):
+    W = 768
     x = _rnd(B * S, W, seed=60)
-    rs = [_res("mean_pool", ops.mean_pool_fwd(x, B, S), x.reshape(B, S, W).mean(1), 1e-5)]
+    rs = [_res("mean_pool", ops.mean_pool_fwd(x, B, S), _r(x).reshape(B, S, W).mean(1), 1e-5)]
     dy = _rnd(B, W, seed=61)
     dx, _ = ops.mean_pool_bwd(dy, B, S)
-    rs.append(_res("mean_pool.bwd", dx, (dy / S)[:, None, :].expand(B, S, W).reshape(B * S, W), 1e-6))
+    rs.append(_res("mean_pool.bwd", dx, (_r(dy) / S)[:, None, :].expand(B, S, W).reshape(B * S, W), 1e-6))
     xh = _rnd(B, 3072, seed=62)
     Wh, bh = _rnd(7, 3072, scale=0.05, seed=63), _rnd(7, seed=64)
     y = ops.head_fwd(xh, Wh, bh)
-    xr, Wr, br = xh.clone().requires_grad_(True), Wh.clone().requires_grad_(True), bh.clone().requires_grad_(True)
+    xr, Wr, br = _r(xh).clone().requires_grad_(True), _r(Wh).clone().requires_grad_(True), _r(bh).clone().requires_grad_(True)
     yr = F.linear(xr, Wr, br)
     rs.append(_res("head.fwd", y, yr, 1e-5))
-    tgt = torch.tensor([1, 6, 3], device=DEV)
-    cw = torch.rand(7, device=DEV) + 0.5
+    tgt = _in(torch.tensor([1, 6, 3, 0, 5, 2, 4][:B], device=DEV))
+    cw = _in(torch.rand(7, device=DEV) + 0.5)
     for weights in (None, cw):
         loss, dlog = ops.cross_entropy(y, tgt, weights)
-        yl = y.clone().requires_grad_(True)
-        lr = F.cross_entropy(yl, tgt, weight=weights)
+        yl = _r(y).clone().requires_grad_(True)
+        lr = F.cross_entropy(yl, tgt, weight=None if weights is None else _r(weights))
         lr.backward()
         rs.append(_res(f"ce.loss[w{weights is not None}]", loss, lr.reshape(1), 1e-5))
         rs.append(_res(f"ce.dlogits[w{weights is not None}]", dlog, yl.grad, 1e-5))
     dyh = _rnd(B, 7, seed=65)
-    yr.backward(dyh)
+    yr.backward(_r(dyh))
     dxh, dWh, dbh = ops.head_bwd(xh, Wh, dyh)
     rs += [_res("head.dx", dxh, xr.grad, 1e-5), _res("head.dW", dWh, Wr.grad, 1e-5), _res("head.db", dbh, br.grad, 1e-5)]
     t = _rnd(5, 768, seed=66)
     ty = ops.tanh_fwd(t)
-    rs += [_res("tanh", ty, torch.tanh(t), 1e-6), _res("tanh.bwd", ops.tanh_bwd(ty, t), t * (1 - torch.tanh(t) ** 2), 1e-5)]
+    rs += [_res("tanh", ty, torch.tanh(_r(t)), 1e-6), _res("tanh.bwd", ops.tanh_bwd(ty, t), _r(t) * (1 - torch.tanh(_r(t)) ** 2), 1e-5)]
     return rs
 
 
-def check_embed_add():
-    rows, W = 500, 768
+def check_embed_add(rows=500):
+    W = 768
     x = _rnd(rows, W, seed=67)
-    ids = torch.randint(0, 3, (rows,), generator=torch.Generator().manual_seed(1)).to(DEV)
+    ids = _in(torch.randint(0, 3, (rows,), generator=torch.Generator().manual_seed(1)).to(DEV))
     table = _rnd(3, W, seed=68)
-    rs = [_res("embed_add.fwd", ops.embed_add_fwd(x, ids, table), x + table[ids], 1e-6)]
+    rs = [_res("embed_add.fwd", ops.embed_add_fwd(x, ids, table), _r(x) + _r(table)[ids], 1e-6)]
     dy = _rnd(rows, W, seed=69)
-    ref = torch.zeros(3, W, device=DEV).index_add_(0, ids, dy)
+    ref = torch.zeros(3, W, device=DEV, dtype=_REF[0]).index_add_(0, ids, _r(dy))
     rs.append(_res("embed_add.bwd", ops.embed_add_bwd(dy, ids, 3), ref, 1e-5))
     rs.append(_res("scatter_add_rows", ops.scatter_add_rows(dy, ids, 3), ref, 1e-5))
     return rs
@@ -560,37 +626,44 @@ def check_index_safety():
     return rs
 
 
-def check_conv0_gn(dtype):
-    B, T_in, Cc, K, s = 2, 1605, 512, 10, 5
+def check_conv0_gn(dtype, B=2, T_in=1605, ref64=False):
+    """ref64: every reference in fp64, the group norm written out by hand (mean and biased variance over time, per entry and channel) -- torch's
+    own group_norm refuses one value per channel, which is exactly the smallest launch (B = 1, one output step: y = gelu(beta), dx = 0)."""
+    Cc, K, s = 512, 10, 5
+    rd = torch.float64 if ref64 else torch.float32
     T_out = (T_in - K) // s + 1
     wave = _rnd(B, T_in, scale=0.5, seed=70)
     w = _rnd(Cc, 1, K, scale=0.3, seed=71)
     gamma, beta = 1 + 0.1 * _rnd(Cc, seed=72), 0.1 * _rnd(Cc, seed=73)
     y0 = ops.conv0_fwd(wave, w, None, T_out, s, dtype)
-    wr = w.clone().requires_grad_(True)
-    gr, br = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
-    c_ref = F.conv1d(wave[:, None], wr, stride=s)            # [B, C, T_out]
+    wr = w.to(rd).clone().requires_grad_(True)
+    gr, br = gamma.to(rd).clone().requires_grad_(True), beta.to(rd).clone().requires_grad_(True)
+    c_ref = F.conv1d(wave.to(rd)[:, None], wr, stride=s)     # [B, C, T_out]
     tol = 1e-2 if dtype == torch.bfloat16 else 3e-5
     rs = [_res(f"conv0.fwd[{dtype}]", y0, c_ref.permute(0, 2, 1), tol)]
     y1, stats = ops.gn_gelu_fwd(y0, gamma, beta, 1e-5)
-    c_in = y0.float().permute(0, 2, 1).detach().requires_grad_(True)
-    g_ref = F.gelu(F.group_norm(c_in, Cc, gr, br, 1e-5))
+    c_in = y0.to(rd).permute(0, 2, 1).detach().requires_grad_(True)
+    if ref64:
+        mu, var = c_in.mean(2, keepdim=True), c_in.var(2, unbiased=False, keepdim=True)
+        g_ref = F.gelu((c_in - mu) / torch.sqrt(var + 1e-5) * gr[None, :, None] + br[None, :, None])
+    else:
+        g_ref = F.gelu(F.group_norm(c_in, Cc, gr, br, 1e-5))
     rs.append(_res(f"gn_gelu.fwd[{dtype}]", y1, g_ref.permute(0, 2, 1), tol))
     dy = _rnd(B, T_out, Cc, dtype=dtype, seed=74)
-    g_ref.backward(dy.float().permute(0, 2, 1))
+    g_ref.backward(dy.to(rd).permute(0, 2, 1))
     dx, dg, db = ops.gn_gelu_bwd(y0, dy, gamma, beta, stats)
     tolb = 3e-2 if dtype == torch.bfloat16 else 2e-4
     rs += [_res(f"gn_gelu.dx[{dtype}]", dx, c_in.grad.permute(0, 2, 1), tolb), _res("gn_gelu.dgamma", dg, gr.grad, tolb),
            _res("gn_gelu.dbeta", db, br.grad, tolb)]
-    c_ref.backward(dx.float().permute(0, 2, 1))
+    c_ref.backward(dx.to(rd).permute(0, 2, 1))
     dw, _ = ops.conv0_bwd_w(wave, dx, K, s, False)
     rs.append(_res(f"conv0.dw[{dtype}]", dw, wr.grad, 1e-4))
     return rs
 
 
-def check_posconv(dtype):
+def check_posconv(dtype, B=2, T=49):
     """grouped conv k=128, pad 64, drop last, GELU, + residual: forward and all gradients vs torch."""
-    B, T, H, G, K = 2, 49, 256, 4, 128
+    H, G, K = 256, 4, 128
     Cg = H // G
     x = _rnd(B, T, H, seed=80)                                   # f32 residual stream
     v = _rnd(H, Cg, K, scale=0.05, seed=81)
@@ -602,15 +675,15 @@ def check_posconv(dtype):
     y, pre = ops.gemm_nt(xg, w, bias=bias, act=1, resid=x.view(B * T, H), want_pre=True, out_dtype=torch.float32,
                          M=T, N=Cg, K=K * Cg, lda=Cg, ldb=K * Cg, ldc=H, nzb=B, nzg=G, a_zb=G * TP * Cg, a_zg=TP * Cg,
                          b_zg=Cg * K * Cg, c_zb=T * H, c_zg=Cg, bias_zg=Cg, out_shape=(B * T, H))
-    xr = x.clone().requires_grad_(True)
-    vr, gr_, br = v.clone().requires_grad_(True), g.clone().requires_grad_(True), bias.clone().requires_grad_(True)
+    xr = _r(x).clone().requires_grad_(True)
+    vr, gr_, br = _r(v).clone().requires_grad_(True), _r(g).clone().requires_grad_(True), _r(bias).clone().requires_grad_(True)
     wr = gr_[None, None, :] * vr / vr.pow(2).sum((0, 1), keepdim=True).sqrt()
     conv = F.conv1d(xr.permute(0, 2, 1), wr, br, padding=64, groups=G)[:, :, :-1]
     ref = xr + F.gelu(conv).permute(0, 2, 1)
     tol = 2e-2 if dtype == torch.bfloat16 else 5e-5
     rs = [_res(f"posconv.fwd[{dtype}]", y, ref.reshape(B * T, H), tol)]
     gout = _rnd(B * T, H, seed=84)
-    ref.backward(gout.view(B, T, H))
+    ref.backward(_r(gout).view(B, T, H))
     du = ops.gelu_bwd(pre, gout)                                  # f32 [B*T, H]
     dug = ops.group_pad(du, B, T, H, G, 63, 64, dtype)
     TPd = T + 127
@@ -618,7 +691,7 @@ def check_posconv(dtype):
                      a_zb=G * TPd * Cg, a_zg=TPd * Cg, b_zg=Cg * K * Cg, c_zb=T * H, c_zg=Cg, out_shape=(B * T, H))
     rs.append(_res(f"posconv.dx[{dtype}]", dx, xr.grad.reshape(B * T, H), tol))
     du_lp = ops.cast2d(du, dtype)
-    dw = torch.empty(G, Cg, K * Cg, dtype=torch.float32, device=DEV)
+    dw = _blank((G, Cg, K * Cg), torch.float32)
     for gi in range(G):
         ops.gemm_tn(du_lp[:, gi * Cg:], xg[:, gi], out=dw[gi], N1=Cg, N2=K * Cg, lda=H, ldb=Cg, rows_per_batch=T, nbatch=B,
                     a_zb=T * H, b_zb=G * TP * Cg)
@@ -626,6 +699,480 @@ def check_posconv(dtype):
     tolw = 3e-2 if dtype == torch.bfloat16 else 2e-4
     rs += [_res(f"posconv.dv[{dtype}]", dv, vr.grad, tolw), _res(f"posconv.dg[{dtype}]", dg, gr_.grad, tolw),
            _res(f"posconv.dbias[{dtype}]", ops.colsum(du), br.grad, tolw)]
+    return rs
+
+
+# ------------------------------------------------------------------------------------------------ edges that only make sense under guard
+# Every case below hands the library 0xFF-filled outputs (NaN until written) and, inside guarded.active(), operands with 0xFF all around
+# them: an element left unwritten, a store outside the logical tensor and an outside read that reaches the result all fail.  References are
+# fp64; tolerances are the constants of the family's existing check.
+def _gelu_d(x):
+    xx = x.detach().clone().requires_grad_(True)
+    (g,) = torch.autograd.grad(F.gelu(xx).sum(), xx)
+    return g
+
+
+def check_gemm_nt_edges(dtype, hint):
+    """M in {1, tile-1, tile, tile+1} of the hint's tile height (128 for the library's own choice, hints 0 and 17), N in {4, 132, 260}, K = one
+    and three K-tiles (128 bytes of operand), every epilogue flavour in turn; each once into a contiguous output and once with out / C_pre /
+    resid / gelu_in as column slices of wider buffers (ldc > N).  The columns outside the slice must still be 0xFF."""
+    bm = {2: 64, 3: 96, 4: 128, 8: 256, 16: 256}.get(hint, 128)
+    kt = 128 // dtype.itemsize
+    lp = dtype == torch.bfloat16
+    rs, n = [], 0
+    for M in (1, bm - 1, bm, bm + 1):
+        for N in (4, 132, 260):
+            for K in (kt, 3 * kt):
+                flavour = n % 5
+                n += 1
+                a = _rnd(M, K, dtype=dtype, seed=500 + n)
+                b = _rnd(N, K, dtype=dtype, scale=0.1, seed=600 + n)
+                bias = _rnd(N, seed=700 + n)
+                prod = a.double() @ b.double().t()
+                for strided in (False, True):
+                    ex = 16 if strided else 0
+
+                    def side(t):
+                        return _in(t, ex) if strided else t
+                    kw, want_pre = {}, None
+                    if flavour == 0:                                  # plain: bias only
+                        kw = dict(bias=bias)
+                        want = prod + bias
+                    elif flavour == 1:                                # f32 out + f32 residual
+                        r = _rnd(M, N, seed=800 + n)
+                        kw = dict(bias=bias, resid=side(r), out_dtype=torch.float32)
+                        want = prod + bias + r.double()
+                    elif flavour == 2:                                # GELU out + gelu' in C_pre
+                        kw = dict(bias=bias, act=3, want_pre=True)
+                        want, want_pre = F.gelu(prod + bias), _gelu_d(prod + bias)
+                    elif flavour == 3:                                # multiply by a stored derivative
+                        u = _rnd(M, N, dtype=dtype, seed=810 + n)
+                        kw = dict(gelu_in=side(u), act=4)
+                        want = prod * u.double()
+                    else:                                             # the generic epilogue with every side tensor at once
+                        r, u = _rnd(M, N, seed=820 + n), _rnd(M, N, dtype=dtype, seed=830 + n)
+                        kw = dict(bias=bias, want_pre=True, gelu_in=side(u), act=4, resid=side(r))
+                        want, want_pre = (prod + bias) * u.double() + r.double(), prod + bias
+                    odt = kw.get("out_dtype", dtype)
+                    wide = None
+                    if strided:
+                        wide = _blank((M, N + 16), odt)
+                        kw["out"] = wide[:, 8:8 + N]
+                    res = ops.gemm_nt(a, b, tile_m=hint, **kw)
+                    out, pre = res if isinstance(res, tuple) else (res, None)
+                    tol = 2e-5 if not lp else (1e-2 if odt == torch.bfloat16 else 2e-3)
+                    tag = f"gemm_nt.edge[{dtype},tm{hint},M{M},N{N},K{K},f{flavour},{'strided' if strided else 'dense'}]"
+                    rs.append(_res(tag, out, want, tol))
+                    if pre is not None:
+                        rs.append(_res(tag + ".pre", pre, want_pre, tol))
+                    if strided:
+                        assert out.data_ptr() == wide[:, 8:].data_ptr() and (pre is None or pre.stride(0) == N + 16)
+                        rs.append(_all_ff(tag + ".gap", wide[:, :8], wide[:, 8 + N:]))
+    return rs
+
+
+def check_fp8_quantize_edges():
+    """rows not a multiple of the transposing tile (1, 33, 1025: one past the padding unit too), the smallest legal cols (4) and a ragged 132:
+    q against torch's own e4m3 conversion, qt its transpose, qt's padding columns exactly zero; nothing past rows_pad (the guard)."""
+    rs = []
+    for rows, cols in ((1, 4), (33, 4), (33, 132), (1025, 132), (1, 1024)):
+        for dtype in (torch.float32, torch.bfloat16):
+            ops.clear_workspaces()                                    # scratch at exactly this shape's size, not the running maximum
+            x = _rnd(rows, cols, dtype=dtype, seed=900)
+            f = ops.fp8_quantize(x, want_t=True)
+            ref_q = (x.float() * f.scales[0]).to(torch.float8_e4m3fn).float()
+            tag = f"fp8.edge[{dtype},{rows}x{cols}]"
+            rs.append(_res(tag + ".q", f.q.float(), ref_q, 0.0))
+            rs.append(_res(tag + ".qt", f.qt.float()[:, :rows], ref_q.t(), 0.0))
+            pad = f.qt[:, rows:].contiguous().view(torch.uint8)
+            rs.append((tag + ".qt_pad bytes zero", float(pad.ne(0).sum().item()), 0.0, not bool(pad.ne(0).any())))
+            rs.append(_res(tag + ".amax", f.scales[2:3], x.float().abs().max().reshape(1), 0.0))
+    return rs
+
+
+def check_gemm_tn_edges(dtype):
+    """rows in {1, 63, 64, 65} (around the 64-row chunk), one batch and three (rows_per_batch not a multiple of the chunk), N1 / N2 ragged against
+    the 128-wide tile, `out=` a slice of a gradient arena with unused floats on both sides."""
+    rs = []
+    for rows in (1, 63, 64, 65):
+        for nb in (1, 3):
+            N1, N2 = 136, 264
+            ops.clear_workspaces()                                    # slabs / bias partials at exactly tav_gemm_tn_splits' size for this shape
+            a = _rnd(nb * rows, N1, dtype=dtype, seed=910 + rows)
+            b = _rnd(nb * rows, N2, dtype=dtype, seed=920 + rows)
+            arena = _blank((64 + N1 * N2 + 64,), torch.float32)
+            out, dbias = ops.gemm_tn(a, b, out=arena[64:64 + N1 * N2].view(N1, N2), N1=N1, N2=N2, lda=N1, ldb=N2, rows_per_batch=rows, nbatch=nb,
+                                     a_zb=rows * N1, b_zb=rows * N2, want_bias=True)
+            tag = f"gemm_tn.edge[{dtype},rows{rows},nb{nb}]"
+            rs.append(_res(tag, out, a.double().t() @ b.double(), 2e-3 if dtype == torch.bfloat16 else 2e-5))
+            rs.append(_res(tag + ".dbias", dbias, a.double().sum(0), 1e-5))
+            rs.append(_all_ff(tag + ".arena gaps", arena[:64], arena[64 + N1 * N2:]))
+    return rs
+
+
+def check_gemm_tn_grouped_edges(dtype):
+    """Four weight gradients in one launch written straight into four slices of ONE arena buffer (`into=`) with unused floats between them,
+    rows in {1, 63, 64, 65}, every form and split count the library accepts for that size (`flags` as in check_gemm_tn_grouped_big)."""
+    shapes = [(384, 136), (136, 264), (256, 512), (520, 128)]
+    rs = []
+    for rows in (1, 63, 64, 65):
+        wide_a = _rnd(rows, 640, dtype=dtype, seed=930 + rows)
+        pairs, refs = [], []
+        for k, (n1, n2) in enumerate(shapes):
+            a = wide_a[:, 64:64 + n1] if k == 0 else _rnd(rows, n1, dtype=dtype, seed=940 + k + rows)
+            b = _rnd(rows, n2, dtype=dtype, seed=950 + k + rows)
+            pairs.append((a, b))
+            refs.append((a.double().t() @ b.double(), a.double().sum(0)))
+        forms = [0, 2] + ([1] if dtype == torch.bfloat16 else [])
+        for form in forms:
+            for nsplit in ((0,) if form != 1 else (0, 1, 2, 3)):
+                if nsplit and (nsplit - 1) * (((rows + nsplit - 1) // nsplit + 63) // 64 * 64) >= rows:     # (the library refuses an empty split)
+                    continue
+                total = sum(n1 * n2 + n1 + 2 * 36 for n1, n2 in shapes)
+                arena = _blank((total,), torch.float32)
+                into, gaps, off = [], [], 0
+                for n1, n2 in shapes:
+                    gaps.append(arena[off:off + 36])
+                    dW = arena[off + 36:off + 36 + n1 * n2].view(n1, n2)
+                    off += 36 + n1 * n2
+                    gaps.append(arena[off:off + 36])
+                    db = arena[off + 36:off + 36 + n1]
+                    off += 36 + n1
+                    into.append((dW, db))
+                assert off == total
+                outs = ops.gemm_tn_grouped(pairs, want_bias=True, flags=form | (nsplit << 8), into=into)
+                tag = f"gemm_tn_grouped.edge[{dtype},rows{rows},form{form},splits{nsplit}]"
+                for k, ((dW, db), (rW, rb)) in enumerate(zip(outs, refs)):
+                    assert dW.data_ptr() == into[k][0].data_ptr() and db.data_ptr() == into[k][1].data_ptr()
+                    rs.append(_res(f"{tag}.dW{k}", dW, rW, 2e-3 if dtype == torch.bfloat16 else 2e-5))
+                    rs.append(_res(f"{tag}.db{k}", db, rb, 1e-5))
+                rs.append(_all_ff(tag + ".arena gaps", *gaps))
+    return rs
+
+
+def check_attention_edges(dtype, mode, S, B=3, nh=3, pre=False, lens=None):
+    """q / k / v as slices of a qkv buffer whose row pitch is wider than 3H, dq / dk / dv into a column slice of a wider buffer, S around the
+    64- and 128-row tiles, B * nheads * tiles not a multiple of 8 -- against an fp64 reference.  lens: the length-aware entry points with these
+    per-row lengths (0 and S included): rows past a length come out zero, the others equal attention over the first L keys."""
+    H = nh * 64
+    g = torch.Generator(device="cpu").manual_seed(1000 + S + mode)
+    qkv0 = torch.randn(B * S, 3 * H, generator=g).to(DEV).to(dtype)
+    c2 = ops.ATTN_Q_PRESCALE
+    if pre:
+        qkv0[:, :H] = (qkv0[:, :H].float() * c2).to(dtype)
+    qkv = _in(qkv0, 24)                                               # row pitch 3H + 24 elements (16-B aligned rows in both dtypes)
+    do = _in(torch.randn(B * S, H, generator=g).to(DEV).to(dtype), 8)
+    mask = None
+    if mode == 1:
+        mask = torch.zeros(B, S)
+        mask[:, S - S // 3:] = torch.finfo(torch.float32).min
+    if mode == 2:
+        mask = torch.where(torch.rand(B, S, generator=g) < 0.3, -0.5, 0.0) + torch.where(torch.rand(B, S, generator=g) < 0.2, 2.0, 0.0)
+    if mask is not None:
+        mask = _in(mask.float().to(DEV))
+    sl = None if lens is None else _in(torch.tensor(lens, dtype=torch.int32, device=DEV))
+    q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
+    o, lse, corr = ops.attn_fwd(q, k, v, B, S, nh, key_mask=mask, mask_mode=mode, q_prescaled=pre, seq_lens=sl)
+    wide = _blank((B * S, 3 * H + 16), dtype)
+    dqkv = ops.attn_bwd(q, k, v, o, do, lse, corr, B, S, nh, key_mask=mask, mask_mode=mode, q_prescaled=pre, seq_lens=sl, dqkv=wide[:, 8:8 + 3 * H])
+
+    o_ref = torch.zeros(B, S, H, dtype=torch.float64, device=DEV)
+    lse_ref = torch.zeros(B, nh, S, dtype=torch.float64, device=DEV)
+    d_ref = torch.zeros(B, S, 3 * H, dtype=torch.float64, device=DEV)
+    for b_ in range(B):
+        L = S if lens is None else min(max(lens[b_], 0), S)
+        if L == 0:
+            continue
+        rows = slice(b_ * S, b_ * S + L)
+
+        def heads(t, div=1.0):
+            return (t[rows].double() / div).reshape(1, L, nh, 64).permute(0, 2, 1, 3).contiguous().requires_grad_(True)
+        qr, kr, vr = heads(q, c2 if pre else 1.0), heads(k), heads(v)
+        mb = None if mask is None else mask[b_:b_ + 1, :L].double()
+        ob = _attn_ref(qr, kr, vr, mb, mode, 0.125)
+        ob.backward(do[rows].double().reshape(1, L, nh, 64).permute(0, 2, 1, 3))
+        o_ref[b_, :L] = ob.detach().permute(0, 2, 1, 3).reshape(L, H)
+        sc = torch.einsum("bhqd,bhkd->bhqk", qr.detach(), kr.detach()) * 0.125 + (mb[:, None, None, :] if mode == 1 else 0.0)
+        lse_ref[b_, :, :L] = torch.logsumexp(sc, dim=-1)[0]
+        for j, t in enumerate((qr, kr, vr)):
+            d_ref[b_, :L, j * H:(j + 1) * H] = t.grad.permute(0, 2, 1, 3).reshape(L, H)
+    lp = dtype == torch.bfloat16
+    tolb = (6e-2 if mode == 2 else 3e-2) if lp else 1e-4
+    tag = f"attn.edge[{dtype},mode{mode},S{S},B{B},nh{nh},pre{int(pre)},lens{lens}]"
+    d_ref = d_ref.reshape(B * S, 3 * H)
+    rs = [_res(tag + ".fwd", o, o_ref.reshape(B * S, H), 2e-2 if lp else 5e-5), _res(tag + ".lse", lse, lse_ref, 2e-2 if lp else 1e-5),
+          _res(tag + ".dq", dqkv[:, :H], d_ref[:, :H], tolb), _res(tag + ".dk", dqkv[:, H:2 * H], d_ref[:, H:2 * H], tolb),
+          _res(tag + ".dv", dqkv[:, 2 * H:], d_ref[:, 2 * H:], tolb), _all_ff(tag + ".dqkv gap", wide[:, :8], wide[:, 8 + 3 * H:])]
+    if lens is not None:
+        for b_, L in enumerate(lens):
+            L = min(max(L, 0), S)
+            pad = slice(b_ * S + L, (b_ + 1) * S)
+            z = o[pad].float().abs().sum() + dqkv[pad].float().abs().sum() + lse[b_, :, L:].abs().sum()
+            rs.append((f"{tag}.row{b_} padding exactly zero", float(z.item()), 0.0, float(z.item()) == 0.0))
+    return rs
+
+
+def check_elementwise_tails():
+    """Element counts around the 4-wide vector and the 256-thread block (x 4 elements): n in {1, 3, 4k+1, 4k+3, 1024 +- 1} where the kernel takes
+    any n (tanh, dropout, fill); add_f32 and gelu_bwd require n % 4 == 0 (TAV_ERR_SHAPE otherwise), so they run at the nearest multiples of 4
+    (4, 1020, 1024, 1028); cast2d at C % 4 == 0 with both sides strided with gaps."""
+    rs = []
+    for n in (1, 3, 41, 43, 1023, 1025):
+        x = _rnd(n, seed=960)
+        dy = _rnd(n, seed=961)
+        y = ops.tanh_fwd(x)
+        rs.append(_res(f"tanh[n{n}]", y, torch.tanh(x.double()), 1e-6))
+        rs.append(_res(f"tanh.bwd[n{n}]", ops.tanh_bwd(y, dy), dy.double() * (1 - y.double() ** 2), 1e-5))
+        z = ops.zeros_f32((n,), DEV)
+        rs.append((f"zeros_f32[n{n}]", float(z.abs().sum().item()), 0.0, bool((z == 0).all())))
+        for p in (0.0, 0.3):
+            yd, m = ops.dropout_fwd(x, p, 1234, 7)
+            keep = m.ne(0)
+            # element i's draw depends on (seed, offset + i) alone: the n-element mask is the prefix of a longer launch's, and the launch
+            # at offset + 1 is that mask shifted by one -- a tail lane that always kept / always dropped would break both; p = 0 keeps all
+            xl = _rnd(n + 2049, seed=967)
+            _, ml = ops.dropout_fwd(xl, p, 1234, 7)
+            _, ms = ops.dropout_fwd(x, p, 1234, 8)
+            same = torch.equal(m, ml[:n]) and torch.equal(ms, ml[1:n + 1]) and (p > 0 or bool(keep.all()))
+            rs.append((f"dropout.mask == prefix of a longer launch[n{n},p{p}]", 0.0 if same else 1.0, 0.0, bool(same)))
+            if p > 0:
+                frac = float(ml.float().mean().item())                # 2k draws: 5 sigma of a fair p = 0.3 coin is 0.05
+                rs.append((f"dropout.keep fraction[p{p}]", abs(frac - (1 - p)), 0.05, abs(frac - (1 - p)) <= 0.05))
+            ok_m = bool(((m == 0) | (m == 1)).all())
+            rs.append((f"dropout.mask is 0/1[n{n},p{p}]", 0.0 if ok_m else 1.0, 0.0, ok_m))
+            rs.append(_res(f"dropout.fwd[n{n},p{p}]", yd, torch.where(keep, x.double() / (1 - p), torch.zeros_like(x, dtype=torch.float64)), 1e-6))
+            rs.append(_res(f"dropout.bwd[n{n},p{p}]", ops.dropout_bwd(dy, m, p), torch.where(keep, dy.double() / (1 - p), torch.zeros_like(dy, dtype=torch.float64)), 1e-6))
+    for n in (4, 1020, 1024, 1028):
+        a, b = _rnd(n, seed=962), _rnd(n, seed=963)
+        for lpd in (None, torch.bfloat16, torch.float32):
+            y, ylp = ops.add_f32(a, b, want_f32=True, lp_dtype=lpd)
+            same = torch.equal(y, a + b) and (ylp is None or torch.equal(ylp, (a + b).to(lpd)))
+            rs.append((f"add_f32[n{n},lp{lpd}] exact", 0.0 if same else 1.0, 0.0, bool(same)))
+        _, only_lp = ops.add_f32(a, b, want_f32=False, lp_dtype=torch.bfloat16)
+        same = torch.equal(only_lp, (a + b).bfloat16())
+        rs.append((f"add_f32[n{n}] bf16 only exact", 0.0 if same else 1.0, 0.0, bool(same)))
+        for dtype in (torch.float32, torch.bfloat16):
+            x, dy = _rnd(n, dtype=dtype, seed=964), _rnd(n, dtype=dtype, seed=965)
+            rs.append(_res(f"gelu_bwd[{dtype},n{n}]", ops.gelu_bwd(x, dy), dy.double() * _gelu_d(x.double()), 1e-2 if dtype == torch.bfloat16 else 2e-5))
+    for R, Cc in ((1, 4), (3, 132), (65, 1028)):
+        for sd in (torch.float32, torch.bfloat16):
+            for dd in (torch.float32, torch.bfloat16):
+                x = _in(_rnd(R, Cc, dtype=sd, seed=966), 8)
+                wide = _blank((R, Cc + 16), dd)
+                out = ops.cast2d(x, dd, out=wide[:, 8:8 + Cc])
+                same = torch.equal(out, x.to(dd))
+                rs.append((f"cast2d[{sd}->{dd},{R}x{Cc}] strided exact", 0.0 if same else 1.0, 0.0, bool(same)))
+                rs.append(_all_ff(f"cast2d[{sd}->{dd},{R}x{Cc}].gap", wide[:, :8], wide[:, 8 + Cc:]))
+    return rs
+
+
+def check_layernorm_edges():
+    """rows in {1, 2} and one less / one more than the rows a workgroup handles (4 in the forward: one wave per row, 4 waves; 16 in the backward's
+    column-sum blocks), all three widths; mean, rstd and the partial slabs sit under guard."""
+    rs = []
+    for W in (512, 768, 1024):
+        for rows in (1, 2, 3, 5, 15, 17):
+            for xd in (torch.float32, torch.bfloat16):
+                ops.clear_workspaces()                                # the partial slab at exactly tav_ln_bwd_partials(rows) * 2 W
+                rs += [(f"{n}[rows{rows},W{W},{xd}]", e, t, ok) for n, e, t, ok in check_layernorm(xd, W=W, rows=rows, act=rows % 2)]
+    return rs
+
+
+def check_attn_probs(dtype, S, B=2, nh=3):
+    """tav_attn_probs against fp64 softmax(q k^T * scale [+ mask]) (+ post-softmax mask in mode 2, as _attn_ref does), the softmax part times
+    head_scale in its [nheads] and [B, nheads] layouts and None; raw and q_prescaled.  Tolerance: the attn.fwd constants of check_attention."""
+    H = nh * 64
+    rs = []
+    tol = 2e-2 if dtype == torch.bfloat16 else 5e-5
+    for mode in (0, 1, 2):
+        for pre in (False, True):
+            g = torch.Generator(device="cpu").manual_seed(1100 + S + mode)
+            qkv0 = torch.randn(B * S, 3 * H, generator=g).to(DEV).to(dtype)
+            if pre:
+                qkv0[:, :H] = (qkv0[:, :H].float() * ops.ATTN_Q_PRESCALE).to(dtype)
+            qkv = _in(qkv0, 8)
+            mask = None
+            if mode == 1:
+                mask = torch.zeros(B, S)
+                mask[:, S - S // 3:] = torch.finfo(torch.float32).min
+            if mode == 2:
+                mask = torch.where(torch.rand(B, S, generator=g) < 0.3, -0.5, 0.0)
+            if mask is not None:
+                mask = _in(mask.float().to(DEV))
+            q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
+            _, lse, _ = ops.attn_fwd(q, k, v, B, S, nh, key_mask=mask, mask_mode=mode, q_prescaled=pre)
+
+            def heads(t, div=1.0):
+                return (t.double() / div).reshape(B, S, nh, 64).permute(0, 2, 1, 3)
+            sc = torch.einsum("bhqd,bhkd->bhqk", heads(q, ops.ATTN_Q_PRESCALE if pre else 1.0), heads(k)) * 0.125
+            if mode == 1:
+                sc = sc + mask.double()[:, None, None, :]
+            soft = torch.softmax(sc, dim=-1)
+            for name, hs in (("none", None), ("[nh]", _rnd(nh, seed=1101)), ("[B,nh]", _rnd(B, nh, seed=1102))):
+                got = ops.attn_probs(q, k, lse, B, S, nh, key_mask=mask, mask_mode=mode, q_prescaled=pre, head_scale=hs)
+                f = 1.0 if hs is None else (hs.double().reshape(1, nh, 1, 1) if hs.dim() == 1 else hs.double().reshape(B, nh, 1, 1))
+                want = soft * f + (mask.double()[:, None, None, :] if mode == 2 else 0.0)
+                rs.append(_res(f"attn_probs[{dtype},S{S},mode{mode},pre{int(pre)},hs{name}]", got, want, tol))
+    return rs
+
+
+def check_head_scale(dtype, B=2, S=37, nh=3):
+    """out = (a or 0) + (c0 + hs[b, h]) * b: `a` present / absent, hs [nheads] / [B, nheads] / None, in place (out = a, as the engine's head-mask
+    path calls it) and into a fresh tensor, every operand a strided slice.  The kernel does one multiply-add in f32: f32 results within
+    tol_for(f32) of the fp64 value; a bf16 result within ONE bf16 rounding of it, |err| <= 2^-8 |ref|.  That bound is applied as it stands
+    wherever the two terms do not cancel (|ref| >= (|a| + |f b|) / 2: a half ulp is below 2^-8 (1 - 2^-8) |ref|, the f32 roundings of f, f b
+    and the sum below 2^-21 |ref|).  Where they cancel further no f32 multiply-add can meet a bound relative to the result alone, and the
+    f32 rounding of the terms, 2^-22 (|a| + |f b|), is added."""
+    H = nh * 64
+    rs = []
+    for use_a in (False, True):
+        for name, hs in (("none", None), ("[nh]", _rnd(nh, seed=1201)), ("[B,nh]", _rnd(B, nh, seed=1202))):
+            for inplace in ((False, True) if use_a else (False,)):
+                for c0 in (-1.0, 1.0):
+                    a_vals = _rnd(B * S, H, dtype=dtype, seed=1203) if use_a else None
+                    a, awide = (_in(a_vals, 8) if use_a else None), None
+                    if inplace:                                       # (a destination, so not a watched input: a slice of a 0xFF buffer)
+                        awide = _blank((B * S, H + 16), dtype)
+                        a = awide[:, 8:8 + H]
+                        a.copy_(a_vals)
+                    b = _in(_rnd(B * S, H, dtype=dtype, seed=1204), 16)
+                    a0 = a_vals.double() if use_a else torch.zeros(B * S, H, dtype=torch.float64, device=DEV)
+                    f = torch.full((B, nh), c0, dtype=torch.float64, device=DEV)
+                    if hs is not None:
+                        f = f + (hs.double()[None, :] if hs.dim() == 1 else hs.double())
+                    fb = (f[:, None, :, None] * b.double().reshape(B, S, nh, 64)).reshape(B * S, H)
+                    want = a0 + fb
+                    wide = None
+                    if inplace:
+                        out = ops.head_scale(a, b, hs, c0, B, S, nh, out=a)
+                    else:
+                        wide = _blank((B * S, H + 16), dtype)
+                        out = ops.head_scale(a, b, hs, c0, B, S, nh, out=wide[:, 8:8 + H])
+                    tag = f"head_scale[{dtype},a{int(use_a)},hs{name},inplace{int(inplace)},c0{c0:g}]"
+                    if dtype == torch.float32:
+                        rs.append(_res(tag, out, want, tol_for(torch.float32)))
+                    else:
+                        mag = a0.abs() + fb.abs()
+                        bound = torch.where(2 * want.abs() >= mag, 2.0 ** -8 * want.abs(), 2.0 ** -8 * want.abs() + 2.0 ** -22 * mag)
+                        err = (out.double() - want).abs()
+                        ok = bool((err <= bound).all()) and bool(torch.isfinite(out.float()).all())
+                        rs.append((tag, float((err / bound.clamp_min(1e-300)).max().item()), 1.0, ok))
+                    for w_ in (wide, awide):
+                        if w_ is not None:
+                            rs.append(_all_ff(tag + ".gap", w_[:, :8], w_[:, 8 + H:]))
+    return rs
+
+
+def _bits(t):
+    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.dtype.itemsize])
+
+
+def check_transpose2d():
+    """Bitwise against x.view(nb, R, C).transpose(1, 2): R and C not multiples of the 32 x 32 tile, one batch and three, both dtypes."""
+    rs = []
+    for dtype in (torch.float32, torch.bfloat16):
+        for nb in (1, 3):
+            for R, Cc in ((1, 1), (33, 31), (70, 130), (37, 64)):
+                x = _rnd(nb * R, Cc, dtype=dtype, seed=1300)
+                got = ops.transpose2d(x, R, Cc, nb)
+                same = got.shape == x.shape and torch.equal(_bits(got).view(nb, Cc, R), _bits(x).view(nb, R, Cc).transpose(1, 2))
+                rs.append((f"transpose2d[{dtype},nb{nb},{R}x{Cc}] bitwise", 0.0 if same else 1.0, 0.0, bool(same)))
+    return rs
+
+
+def check_zero_pad_rows():
+    """The `pad` leading and trailing rows of each batch entry become zero; the T interior rows keep 0xFF in every byte (never touched)."""
+    rs = []
+    for dtype in (torch.float32, torch.bfloat16):
+        for B, T, Cc, pad in ((1, 1, 4, 1), (3, 5, 132, 2), (2, 70, 64, 3)):
+            buf = _blank((B, T + 2 * pad, Cc), dtype)
+            ops.zero_pad_rows(buf, B, T, Cc, pad)
+            frame = torch.cat([buf[:, :pad], buf[:, pad + T:]], 1).contiguous().view(torch.uint8)
+            tag = f"zero_pad_rows[{dtype},B{B},T{T},C{Cc},pad{pad}]"
+            rs.append((tag + ".frame bytes zero", float(frame.ne(0).sum().item()), 0.0, not bool(frame.ne(0).any())))
+            rs.append(_all_ff(tag + ".interior untouched", buf[:, pad:pad + T]))
+    return rs
+
+
+def check_small_counts():
+    """Index / pooling / head kernels and the audio front-end at one row / one batch entry and at odd counts, the front-end also at the
+    smallest length its host validation accepts (T_in = K = 10: one output step) and one output step past its 512-step chunk."""
+    rs = []
+    for B, S in ((1, 1), (1, 77), (5, 3)):
+        rs += [(f"{n}[B{B},S{S}]", e, t, ok) for n, e, t, ok in check_pool_head_ce(B=B, S=S)]
+    for rows in (1, 257):
+        ops.clear_workspaces()                                        # the partial slab at exactly tav_embed_add_bwd_parts(rows) * ntable * W
+        rs += [(f"{n}[rows{rows}]", e, t, ok) for n, e, t, ok in check_embed_add(rows=rows)]
+    for pad_id in (1, -1):
+        for B, S in ((1, 1), (1, 65), (3, 7)):
+            rs += [(f"{n}[pad{pad_id},B{B},S{S}]", e, t, ok) for n, e, t, ok in check_text_embed(pad_id, B=B, S=S)]
+    for B, nkeep in ((1, 1), (1, 5), (3, 7), (5, 12)):               # (12 = every token of the 4 x 32 x 48 clip kept)
+        rs += [(f"{n}[B{B},nkeep{nkeep}]", e, t, ok) for n, e, t, ok in check_patchify(B=B, nkeep=nkeep)]
+    table = _rnd(7, 132, seed=1400)
+    for idx in ([3], [6, 0, 6, 2, 5]):
+        it = _in(torch.tensor(idx, dtype=torch.int32, device=DEV))
+        rs.append(_res(f"gather_rows[{len(idx)}]", ops.gather_rows(table, it), table[it.long()], 0.0))
+        i64 = _in(torch.tensor(idx, dtype=torch.int64, device=DEV))
+        d = _rnd(len(idx), 132, seed=1401)
+        rs.append(_res(f"scatter_add_rows[{len(idx)}]", ops.scatter_add_rows(d, i64, 7), torch.zeros(7, 132, dtype=torch.float64, device=DEV).index_add_(0, i64, d.double()), 1e-6))
+    m = torch.zeros(1, 5, dtype=torch.bool)
+    m[0, [1, 4]] = True
+    idx, counts = ops.mask_to_index(_in(m.to(DEV)), True, 2)
+    rs.append(_res("mask_to_index[B1,n5]", idx.float(), torch.tensor([[1., 4.]], device=DEV), 0.0))
+    rs.append(_res("mask_to_index.counts[B1,n5]", counts.float(), torch.tensor([2.], device=DEV), 0.0))
+    m = torch.zeros(3, 7, dtype=torch.bool)
+    m[0, [0, 6]] = True
+    m[1, [2, 3, 5]] = True                                            # more than nkeep: truncated
+    m[2, [4]] = True                                                  # fewer: the last kept index repeats
+    idx, counts = ops.mask_to_index(_in(m.to(DEV)), True, 2)
+    rs.append(_res("mask_to_index[B3,n7]", idx.float(), torch.tensor([[0., 6.], [2., 3.], [4., 4.]], device=DEV), 0.0))
+    rs.append(_res("mask_to_index.counts[B3,n7]", counts.float(), torch.tensor([2., 3., 1.], device=DEV), 0.0))
+    return rs
+
+
+def check_fp8_edges(M, N, K, tile_m):
+    """The fp8 GEMM's epilogue like check_gemm_nt_edges: every flavour once into a contiguous output and once with out / C_pre / resid /
+    gelu_in as column slices of wider buffers (ldc > N), the columns outside the slice still 0xFF afterwards.  References in fp64 from the
+    DEQUANTISED operands (as check_fp8: exact up to summation order); tolerances are check_fp8's."""
+    ops.clear_workspaces()
+    x = _rnd(M, K, dtype=torch.bfloat16, seed=970)
+    w = _rnd(N, K, seed=971, scale=0.05)
+    x8, w8 = ops.fp8_quantize(x), ops.fp8_quantize(w)
+    prod = (x8.q.double() * x8.scales[1].double()) @ (w8.q.double() * w8.scales[1].double()).t()
+    bias = _rnd(N, seed=972)
+    r, u = _rnd(M, N, seed=973), _rnd(M, N, dtype=torch.bfloat16, seed=974)
+    rs = []
+    for strided in (False, True):
+        def side(t):
+            return _in(t, 16) if strided else t
+        for flavour in range(5):
+            want_pre = None
+            if flavour == 0:
+                kw, want = dict(bias=bias), prod + bias
+            elif flavour == 1:
+                kw, want = dict(bias=bias, resid=side(r), out_dtype=torch.float32), prod + bias + r.double()
+            elif flavour == 2:
+                kw, want, want_pre = dict(bias=bias, act=3, want_pre=True), F.gelu(prod + bias), _gelu_d(prod + bias)
+            elif flavour == 3:
+                kw, want = dict(gelu_in=side(u), act=4), prod * u.double()
+            else:
+                kw = dict(bias=bias, want_pre=True, gelu_in=side(u), act=4, resid=side(r))
+                want, want_pre = (prod + bias) * u.double() + r.double(), prod + bias
+            odt = kw.get("out_dtype", torch.bfloat16)
+            wide = None
+            if strided:
+                wide = _blank((M, N + 16), odt)
+                kw["out"] = wide[:, 8:8 + N]
+            res = ops.gemm_nt_fp8(x8, w8, tile_m=tile_m, **kw)
+            out, pre = res if isinstance(res, tuple) else (res, None)
+            tol = 1e-2 if odt == torch.bfloat16 else 2e-5
+            tag = f"fp8.edge[M{M},N{N},K{K},tm{tile_m},f{flavour},{'strided' if strided else 'dense'}]"
+            rs.append(_res(tag, out, want, tol))
+            if pre is not None:
+                rs.append(_res(tag + ".pre", pre, want_pre, tol))
+            if strided:
+                assert out.data_ptr() == wide[:, 8:].data_ptr() and (pre is None or pre.stride(0) == N + 16)
+                rs.append(_all_ff(tag + ".gap", wide[:, :8], wide[:, 8 + N:]))
     return rs
 
 
@@ -712,4 +1259,35 @@ def all_checks():
     out += [check_cast_weight, check_colsum, check_text_embed, lambda: check_text_embed(-1), check_patchify,
             check_pool_head_ce, check_embed_add, check_scatter_deterministic, check_index_safety, check_fp8,
             lambda: check_fp8(M=1000, N=768, K=256, tile_m=16), lambda: check_fp8(M=130, N=132, K=128, tile_m=4)]
+    # guard-band edge cases (appended, so the indices of the cases above stay what they were)
+    for dtype in (torch.float32, torch.bfloat16):
+        for hint in (0, 2, 3, 4, 17) + ((8, 16) if dtype == torch.bfloat16 else ()):
+            out.append(lambda d=dtype, h=hint: check_gemm_nt_edges(d, h))
+        out.append(lambda d=dtype: check_gemm_tn_edges(d))
+        out.append(lambda d=dtype: check_gemm_tn_grouped_edges(d))
+        for mode in (0, 1, 2):
+            for S in (1, 63, 64, 65, 127, 129):
+                out.append(lambda d=dtype, m=mode, s=S: check_attention_edges(d, m, s, pre=bool(s % 2)))
+            out.append(lambda d=dtype, m=mode: check_attention_edges(d, m, 65, lens=[0, 65, 33]))
+            out.append(lambda d=dtype, m=mode: check_attention_edges(d, m, 129, lens=[129, 0, 64], pre=True))
+        for S in (1, 65, 200):
+            out.append(lambda d=dtype, s=S: check_attn_probs(d, s))
+        out.append(lambda d=dtype: check_head_scale(d))
+        # audio front-end at the smallest sizes the host validation accepts (one output step, one batch entry; both together at the end of
+        # the list) and one step past a chunk
+        out.append(lambda d=dtype: check_conv0_gn(d, B=2, T_in=10, ref64=True))
+        out.append(lambda d=dtype: check_conv0_gn(d, B=1, T_in=15, ref64=True))
+        out.append(lambda d=dtype: check_conv0_gn(d, B=1, T_in=512 * 5 + 10, ref64=True))
+        out.append(_in64(lambda d=dtype: check_conv_as_gemm(d, B=1, T_in=3)))
+        out.append(_in64(lambda d=dtype: check_posconv(d, B=1, T=1)))
+    out += [check_fp8_quantize_edges, lambda: check_fp8(M=1, N=132, K=128, tile_m=4), lambda: check_fp8(M=129, N=132, K=128, tile_m=4),
+            lambda: check_fp8(M=1, N=768, K=256, tile_m=16), lambda: check_fp8(M=257, N=768, K=256, tile_m=16),
+            check_elementwise_tails, _in64(check_layernorm_edges), check_transpose2d, check_zero_pad_rows, _in64(check_small_counts)]
+    # the fp8 epilogue with strided outputs and side tensors: check_fp8's three shapes plus M = 1 and tile + 1 of both fp8 tiles
+    for M, N, K, tm in ((700, 384, 1024, 0), (1000, 768, 256, 16), (130, 132, 128, 4), (1, 132, 128, 4), (129, 132, 128, 4),
+                        (1, 260, 256, 16), (257, 260, 256, 16)):
+        out.append(lambda a=(M, N, K, tm): check_fp8_edges(*a))
+    # the smallest launch of the audio front-end: one batch entry, one output step (hand-written fp64 group norm: torch's refuses it)
+    for dtype in (torch.float32, torch.bfloat16):
+        out.append(lambda d=dtype: check_conv0_gn(d, B=1, T_in=10, ref64=True))
     return out

@@ -1,14 +1,35 @@
 """GPU: length-aware attention (tav_attn_fwd_len / tav_attn_bwd_len) and mean pool (tav_mean_pool_*_len).
 
 Row b of a length-aware launch over a padded [B, S] layout must be BITWISE equal to the plain kernel run on that row alone with S = L_b,
-padded rows must come out exactly zero, all-full lengths must reproduce the plain kernel, and two runs must agree bit for bit."""
+padded rows must come out exactly zero, all-full lengths must reproduce the plain kernel, and two runs must agree bit for bit.
+
+Every test runs inside the guard-band allocator (tests/guarded.py): outputs start as 0xFF (NaN), so "exactly zero" and "bitwise equal" cannot
+be met by what an earlier launch left in a recycled block, and stores outside a tensor or into an operand are reported by verify()."""
+import functools
+
 import pytest
 import torch
 
+import guarded
 import tav_amd  # noqa: F401
 from tav_amd import ops
 
 pytestmark = pytest.mark.gpu
+
+def _g(t):
+    """An operand inside a watched 0xFF buffer while a guard is active (None stays None)."""
+    return t if t is None or guarded.current() is None else guarded.guarded_input(t)
+
+
+def under_guard(fn):
+    @functools.wraps(fn)
+    def run(*args, **kw):
+        with guarded.active() as g:
+            fn(*args, **kw)
+            assert g.allocs
+            g.verify()
+    return run
+
 
 NH = 2
 H = NH * 64
@@ -27,7 +48,7 @@ def _inputs(dtype, mode, lens, seed=0):
     elif mode == 2:
         mask = torch.where(torch.rand(B, S, generator=g) < 0.2, -1.0, 0.0) + 0.01 * torch.randn(B, S, generator=g)
     dev = "cuda"
-    return qkv.to(dev), dout.to(dev), None if mask is None else mask.float().contiguous().to(dev)
+    return _g(qkv.to(dev)), _g(dout.to(dev)), None if mask is None else _g(mask.float().contiguous().to(dev))
 
 
 def _run(qkv, dout, mask, B, S_, mode, pre, seq_lens=None):
@@ -52,17 +73,18 @@ CASES = [(dt, mode, pre) for dt in (torch.bfloat16, torch.float32) for mode in (
 
 
 @pytest.mark.parametrize("dtype,mode,pre", CASES, ids=[f"{'bf16' if d == torch.bfloat16 else 'f32'}-m{m}-{'pre' if p else 'raw'}" for d, m, p in CASES])
+@under_guard
 def test_attention_rows_bitwise_equal_to_batch1(gpu, dtype, mode, pre):
     B = len(LENS)
     qkv, dout, mask = _inputs(dtype, mode, LENS)
-    sl = torch.tensor(LENS, dtype=torch.int32, device="cuda")
+    sl = _g(torch.tensor(LENS, dtype=torch.int32, device="cuda"))
     rag = _run(qkv, dout, mask, B, S, mode, pre, seq_lens=sl)
     again = _run(qkv, dout, mask, B, S, mode, pre, seq_lens=sl)
     for key in rag:
         assert _same(rag[key], again[key]), f"{key}: two runs differ"
     for b, L in enumerate(LENS):
         r0, r1 = b * S, b * S + L
-        m1 = None if mask is None else mask[b:b + 1, :L].contiguous()
+        m1 = None if mask is None else _g(mask[b:b + 1, :L].contiguous())
         one = _run(qkv[r0:r1], dout[r0:r1], m1, 1, L, mode, pre)
         assert _same(rag["o"][r0:r1], one["o"]), f"row {b} (L={L}): o"
         assert _same(rag["lse"][b, :, :L], one["lse"][0]), f"row {b} (L={L}): lse"
@@ -79,10 +101,11 @@ def test_attention_rows_bitwise_equal_to_batch1(gpu, dtype, mode, pre):
 
 
 @pytest.mark.parametrize("dtype,mode,pre", CASES, ids=[f"{'bf16' if d == torch.bfloat16 else 'f32'}-m{m}-{'pre' if p else 'raw'}" for d, m, p in CASES])
+@under_guard
 def test_attention_full_lengths_equal_plain_kernel(gpu, dtype, mode, pre):
     B = 3
     qkv, dout, mask = _inputs(dtype, mode, [S] * B, seed=1)
-    full = torch.full((B,), S, dtype=torch.int32, device="cuda")
+    full = _g(torch.full((B,), S, dtype=torch.int32, device="cuda"))
     rag = _run(qkv, dout, mask, B, S, mode, pre, seq_lens=full)
     plain = _run(qkv, dout, mask, B, S, mode, pre)
     for key in plain:
@@ -90,12 +113,13 @@ def test_attention_full_lengths_equal_plain_kernel(gpu, dtype, mode, pre):
 
 
 @pytest.mark.parametrize("dtype,mode,pre", CASES, ids=[f"{'bf16' if d == torch.bfloat16 else 'f32'}-m{m}-{'pre' if p else 'raw'}" for d, m, p in CASES])
+@under_guard
 def test_attention_padding_content_and_empty_rows(gpu, dtype, mode, pre):
     """What the padded slots hold does not reach the valid rows; a row of length 0 (and lengths past S, clamped) is handled."""
     lens = [0, 37, S + 50, 129]
     B = len(lens)
     qkv, dout, mask = _inputs(dtype, mode, lens, seed=2)
-    sl = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    sl = _g(torch.tensor(lens, dtype=torch.int32, device="cuda"))
     a = _run(qkv, dout, mask, B, S, mode, pre, seq_lens=sl)
     qkv2, dout2 = qkv.clone(), dout.clone()
     mask2 = None if mask is None else mask.clone()
@@ -105,24 +129,25 @@ def test_attention_padding_content_and_empty_rows(gpu, dtype, mode, pre):
         dout2[b * S + L:(b + 1) * S] = 7
         if mask2 is not None:
             mask2[b, L:] = 123.0
-    c = _run(qkv2, dout2, mask2, B, S, mode, pre, seq_lens=sl)
+    c = _run(_g(qkv2), _g(dout2), _g(mask2), B, S, mode, pre, seq_lens=sl)
     for key in a:
         assert _same(a[key], c[key]), f"mode {mode}: {key} depends on the padded slots"
     assert not a["o"][:S].float().abs().sum().item() and not a["dqkv"][:S].float().abs().sum().item()
     assert not a["lse"][0].abs().sum().item()
     if mode == 2:
         assert not a["corr"][0].abs().sum().item()
-    full = _run(qkv[2 * S:3 * S], dout[2 * S:3 * S], None if mask is None else mask[2:3].contiguous(), 1, S, mode, pre)
+    full = _run(qkv[2 * S:3 * S], dout[2 * S:3 * S], None if mask is None else _g(mask[2:3].contiguous()), 1, S, mode, pre)
     assert _same(a["o"][2 * S:3 * S], full["o"]) and _same(a["dqkv"][2 * S:3 * S], full["dqkv"])
 
 
+@under_guard
 def test_mean_pool_len_bitwise(gpu):
     lens = [0, 1, 15, 16, 17, 100, S]
     B, W = len(lens), 136
     g = torch.Generator().manual_seed(3)
-    x = torch.randn(B * S, W, generator=g).cuda()
-    dy = torch.randn(B, W, generator=g).cuda()
-    sl = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    x = _g(torch.randn(B * S, W, generator=g).cuda())
+    dy = _g(torch.randn(B, W, generator=g).cuda())
+    sl = _g(torch.tensor(lens, dtype=torch.int32, device="cuda"))
     y = ops.mean_pool_fwd(x, B, S, seq_lens=sl)
     assert _same(y, ops.mean_pool_fwd(x, B, S, seq_lens=sl))
     dx, dxlp = ops.mean_pool_bwd(dy, B, S, lp_dtype=torch.bfloat16, seq_lens=sl)
@@ -134,7 +159,7 @@ def test_mean_pool_len_bitwise(gpu):
             ref, reflp = ops.mean_pool_bwd(dy[b:b + 1], 1, L, lp_dtype=torch.bfloat16)
             assert _same(dx[b * S:b * S + L], ref) and _same(dxlp[b * S:b * S + L], reflp), f"row {b} (L={L}): backward"
         assert not dx[b * S + L:(b + 1) * S].abs().sum().item() and not dxlp[b * S + L:(b + 1) * S].float().abs().sum().item()
-    full = torch.full((B,), S, dtype=torch.int32, device="cuda")
+    full = _g(torch.full((B,), S, dtype=torch.int32, device="cuda"))
     assert _same(ops.mean_pool_fwd(x, B, S, seq_lens=full), ops.mean_pool_fwd(x, B, S))
     assert _same(ops.mean_pool_bwd(dy, B, S, seq_lens=full)[0], ops.mean_pool_bwd(dy, B, S)[0])
 
@@ -166,6 +191,7 @@ def _layer_step(policy, params, x, gy, B, S, mode, key_mask, seq_lens):
 
 
 @pytest.mark.parametrize("mode", [0, 2])
+@under_guard
 def test_encoder_layer_ragged_rows(gpu, mode):
     """LayerSpec(seq_lens=...): valid rows match the rows run alone (fp32 policy), the padded slots' content changes nothing (bitwise,
     fp32 and bf16), their gradient is exactly zero, and the parameter gradients are the sums of the per-row ones."""
