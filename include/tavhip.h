@@ -306,6 +306,15 @@ int tav_patchify(const float* video, const int32_t* keep_idx, void* patches, int
  * values in [0, n), so tav_patchify / tav_gather_rows (which also clamp) never read outside their operands. */
 int tav_mask_to_index(const uint8_t* mask, int32_t keep_value, int32_t* keep_idx, int32_t* counts, int64_t B, int64_t n, int64_t nkeep,
                       void* stream);
+/* Ragged rows at a fixed capacity (one launch; additive to ABI v7).  mask [B][ntok] (uint8/bool, True = a token the fusion stack sees).
+ * Per row b, with n_b = number of True entries:  true_cnt[b] = n_b;  vid_lens[b] = min(ntok - n_b, cap_keep);
+ * av_lens[b] = base + min(n_b, cap_true)  (all int32 [B]).  *status (int32, zeroed by the caller) gets TAV_RAGGED_OVER_TRUE OR-ed in when a
+ * row has n_b > cap_true and TAV_RAGGED_OVER_KEEP when a row has ntok - n_b > cap_keep or n_b == 0.  The lengths are clamped, so the
+ * length-aware kernels stay inside rows of cap_keep / base + cap_true tokens whatever the mask holds; the host reads *status at its next
+ * sync.  1 <= cap_true, cap_keep <= ntok, base >= 0. */
+enum { TAV_RAGGED_OVER_TRUE = 1, TAV_RAGGED_OVER_KEEP = 2 };
+int tav_ragged_lens(const uint8_t* mask, int32_t* true_cnt, int32_t* vid_lens, int32_t* av_lens, int32_t* status, int64_t B, int64_t ntok,
+                    int64_t cap_true, int64_t cap_keep, int64_t base, void* stream);
 /* out[r][:] = table[idx[r]][:] f32 -- rows of the fixed sin-cos position table (HF videomae:80-124) for the kept tokens;
  * the result is handed to the patch-embedding GEMM as its `resid` so the add is fused.  idx is clamped into [0, ntable). */
 int tav_gather_rows(const float* table, const int32_t* idx, float* out, int64_t rows, int64_t W, int64_t ntable, void* stream);

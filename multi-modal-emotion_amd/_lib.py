@@ -117,6 +117,7 @@ _SIGS = {
     "tav_gather_rows": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
     "tav_patchify": (C.c_int, [vp, vp, vp, i32, i64, i64, i64, i64, i64, vp]),
     "tav_mask_to_index": (C.c_int, [vp, i32, vp, vp, i64, i64, i64, vp]),
+    "tav_ragged_lens": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
     "tav_mean_pool_fwd": (C.c_int, [vp, vp, i64, i64, i64, vp]),
     "tav_mean_pool_bwd": (C.c_int, [vp, vp, vp, i32, i64, i64, i64, vp]),
     "tav_mean_pool_fwd_len": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),

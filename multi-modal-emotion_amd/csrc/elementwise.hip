@@ -341,6 +341,31 @@ __global__ __launch_bounds__(256) void mask_to_index_kernel(const uint8_t* __res
         for (int k = found + t; k < nkeep; k += 256) keep_idx[(long)b * nkeep + k] = last_kept;
     }
 }
+// ragged rows at a fixed capacity: one workgroup per row of the video mask counts its True tokens and writes the row's lengths, clamped to
+// the capacities the shapes were built for, so whatever mask sits in the buffer the length-aware kernels stay inside their rows.  A row that
+// does not fit ORs its bit into *status (an ordinary device atomic, at most once per row); the caller zeroes the word and reads it at its sync.
+__global__ __launch_bounds__(256) void ragged_lens_kernel(const uint8_t* __restrict__ mask, int32_t* __restrict__ true_cnt, int32_t* __restrict__ vid_lens,
+                                                          int32_t* __restrict__ av_lens, int32_t* __restrict__ status, int ntok, int cap_true, int cap_keep,
+                                                          int base) {
+    __shared__ int red[256];
+    const int b = blockIdx.x, t = threadIdx.x;
+    int cnt = 0;
+    for (int i = t; i < ntok; i += 256) cnt += mask[(long)b * ntok + i] != 0 ? 1 : 0;
+    red[t] = cnt;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) red[t] += red[t + off];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const int n = red[0], kept = ntok - n;
+        true_cnt[b] = n;
+        vid_lens[b] = kept < cap_keep ? kept : cap_keep;
+        av_lens[b] = base + (n < cap_true ? n : cap_true);
+        const int bits = (n > cap_true ? TAV_RAGGED_OVER_TRUE : 0) | ((kept > cap_keep || n == 0) ? TAV_RAGGED_OVER_KEEP : 0);
+        if (bits) atomicOr(status, bits);
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ pooling / head / loss
 // block = 16 float4 columns x 16 row groups: every thread sums rows rg, rg+16, ... of its 4 columns (16-B loads, S/16 iterations)
@@ -832,6 +857,15 @@ extern "C" int tav_mask_to_index(const uint8_t* mask, int32_t keep_value, int32_
     if (!mask || !keep_idx) return TAV_ERR_NULL;
     if (B <= 0 || n <= 0 || nkeep <= 0 || nkeep > n) return TAV_ERR_SHAPE;
     hipLaunchKernelGGL(mask_to_index_kernel, dim3((unsigned)B), dim3(256), 0, ST, mask, keep_value, keep_idx, counts, (int)n, (int)nkeep);
+    return tav_last_error();
+}
+extern "C" int tav_ragged_lens(const uint8_t* mask, int32_t* true_cnt, int32_t* vid_lens, int32_t* av_lens, int32_t* status, int64_t B, int64_t ntok,
+                               int64_t cap_true, int64_t cap_keep, int64_t base, void* stream) {
+    if (!mask || !true_cnt || !vid_lens || !av_lens || !status) return TAV_ERR_NULL;
+    if (B <= 0 || ntok <= 0 || cap_true <= 0 || cap_true > ntok || cap_keep <= 0 || cap_keep > ntok || base < 0) return TAV_ERR_SHAPE;
+    if (ntok > INT32_MAX / 2 || base > INT32_MAX / 2) return TAV_ERR_SHAPE;
+    hipLaunchKernelGGL(ragged_lens_kernel, dim3((unsigned)B), dim3(256), 0, ST, mask, true_cnt, vid_lens, av_lens, status, (int)ntok, (int)cap_true,
+                       (int)cap_keep, (int)base);
     return tav_last_error();
 }
 extern "C" int tav_mean_pool_fwd(const float* x, float* y, int64_t B, int64_t S, int64_t W, void* stream) {

@@ -309,12 +309,17 @@ class VideoEncoder(nn.Module):
         x = E.PatchEmbedFn.apply(video, idx, p.weight, p.bias, self._pos_table, ectx)
         return x, nkeep
 
-    def forward(self, video, bool_masked_pos, nkeep=None, ragged=False):
+    def forward(self, video, bool_masked_pos, nkeep=None, ragged=False, seq_lens=None):
         """VideoMAEModel(pixel_values, bool_masked_pos)[0] with use_mean_pooling=True (no final LayerNorm).
-        ragged=True (see embed): returns (x [B*nkeep, H], nkeep = the largest row, kept int32 [B]); the layers run length-aware."""
+        ragged=True (see embed): returns (x [B*nkeep, H], nkeep = the largest row, kept int32 [B]); the layers run length-aware.
+        seq_lens (ragged, with nkeep a capacity chosen by the caller): the rows' lengths, int32 [B] on the device, already clamped to nkeep
+        (ops.ragged_lens) -- used in place of the counts embed() finds, which are not clamped."""
         ectx, c = runtime.ctx(), self.cfg
         if ragged:
-            x, nkeep, seq_lens = self.embed(video, bool_masked_pos, nkeep, ragged=True)
+            if seq_lens is not None and nkeep is None:
+                raise ValueError("VideoEncoder: seq_lens needs the row capacity nkeep they were clamped to")
+            x, nkeep, counted = self.embed(video, bool_masked_pos, nkeep, ragged=True)
+            seq_lens = counted if seq_lens is None else seq_lens
         else:
             (x, nkeep), seq_lens = self.embed(video, bool_masked_pos, nkeep), None
         spec = E.LayerSpec(video.shape[0], nkeep, c["heads"], c["eps"], pre_ln=True, mask_mode=0, branch="video", seq_lens=seq_lens)

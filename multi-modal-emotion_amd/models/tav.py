@@ -17,7 +17,7 @@ from torch import nn
 
 from .. import config as C
 from .. import engine as E
-from .. import runtime
+from .. import ops, runtime
 from ..encoders import AudioEncoder, TextEncoder, VideoEncoder
 from ..utils.TAVFormer import VideoMAEEncoder
 
@@ -53,6 +53,40 @@ def visual_true_counts(visual_mask, n_visual_true=None):
         raise ValueError(f"visual mask keeps {counts} True tokens per row; every row must keep the same number "
                          "(runtime.set_visual_rows('ragged') trains on unequal rows)")
     return counts
+
+
+def visual_row_counts(visual_mask, n_visual_true=None):
+    """The per-row True counts of visual_mask as a host list of B ints: from n_visual_true (an int, a sequence or a tensor) when given,
+    else one host read of the B counts."""
+    B = visual_mask.shape[0]
+    if n_visual_true is None:
+        return [int(c) for c in visual_mask.sum(1).cpu().tolist()]
+    if isinstance(n_visual_true, (int, np.integer)):
+        return [int(n_visual_true)] * B
+    counts = [int(c) for c in (n_visual_true.tolist() if torch.is_tensor(n_visual_true) else n_visual_true)]
+    if len(counts) != B:
+        raise ValueError(f"n_visual_true has {len(counts)} entries for a batch of {B}")
+    return counts
+
+
+def resolve_visual_caps(visual_mask, n_visual_true=None, caps=None):
+    """(cap_true, cap_keep) when the batch runs at a bucketed capacity (runtime.set_visual_rows("ragged", bucket=g), or `caps` given by the
+    caller, e.g. a captured step), else None.  With a bucket EVERY batch takes the padded path, equal rows included: the shapes then depend
+    on the bucket alone."""
+    ntok = visual_mask.shape[1]
+    if caps is None:
+        g = runtime.visual_bucket()
+        if not g:
+            return None
+        return runtime.visual_capacities(visual_row_counts(visual_mask, n_visual_true), ntok, g)
+    cap_true, cap_keep = (int(c) for c in caps)
+    if not (0 < cap_true <= ntok and 0 < cap_keep <= ntok):
+        raise ValueError(f"visual capacities {(cap_true, cap_keep)} must lie in [1, {ntok}]")
+    return cap_true, cap_keep
+
+
+STATUS_TEXT = {1: "a row keeps more True video tokens than the fusion rows were sized for (cap_true)",
+               2: "a row keeps more visible tokens than the video encoder's rows were sized for (cap_keep), or no True token at all"}
 
 
 class PreFormer(nn.Module):
@@ -132,10 +166,12 @@ class PreFormer(nn.Module):
         return hidden
 
     def forward(self, input_ids=None, audio_features=None, video_embeds=None, text_mask=None, audio_mask=None, visual_mask=None,
-                device="cpu", train=False, n_visual_true=None):
+                device="cpu", train=False, n_visual_true=None, visual_caps=None):
         """n_visual_true (optional): number of True entries per row of visual_mask (an int, or per row in ragged mode); passing it avoids one
         host sync.  Ragged mode with unequal rows: the video segment (last) is max_b n_true_b tokens long, padded at the end of each row
-        (tav_embed 2, attention_mask 0 there)."""
+        (tav_embed 2, attention_mask 0 there).  With a bucket (runtime.set_visual_rows("ragged", bucket=g)) or explicit
+        visual_caps = (cap_true, cap_keep) the segment is cap_true tokens long whatever the rows hold; nothing is read from the host when
+        the capacities are given."""
         dev = _dev(device if str(device) != "cpu" else None)
         ectx = runtime.ctx()
         if audio_features.is_cuda:
@@ -144,15 +180,16 @@ class PreFormer(nn.Module):
         parts = []
         St = 0
         audio_features, video_embeds, visual_mask = audio_features.to(dev, torch.float32), video_embeds.to(dev, torch.float32), visual_mask.to(dev)
-        nt = visual_true_counts(visual_mask, n_visual_true)
-        ragged = isinstance(nt, list)
+        caps = resolve_visual_caps(visual_mask, n_visual_true, visual_caps)
+        nt = visual_true_counts(visual_mask, n_visual_true) if caps is None else None
+        ragged = caps is not None or isinstance(nt, list)
         Sa = self.wav2vec2.conv_out_len(audio_features.shape[1])
         if audio_mask is not None:
             audio_mask = self._get_feature_vector_attention_mask(Sa, audio_mask.to(dev))     # :355 bool [B, Sa]
 
         def video_frontend():
             if ragged:
-                xv, nv, _ = self.videomae.embed(video_embeds, ~visual_mask, max(nt), ragged=True)
+                xv, nv, _ = self.videomae.embed(video_embeds, ~visual_mask, caps[0] if caps is not None else max(nt), ragged=True)
             else:
                 xv, nv = self.videomae.embed(video_embeds, ~visual_mask, nt)          # :368
             if hasattr(self, "vid_2_768"):
@@ -246,6 +283,7 @@ class TAVForMAE(nn.Module):
             self.vid_2_768_2 = nn.Linear(cfg["video"]["hidden"], 768)
             nn.init.xavier_normal_(self.vid_2_768_2.weight)
         self._drop_calls = 0
+        self._visual_status = None       # status word of the last forward at a capacity (check_visual_status)
 
     def randomize_model(self, model):
         """reference :461-471: xavier_uniform Linear/Embedding weights, zero biases, LayerNorm weight = 1 / bias = 0."""
@@ -259,25 +297,57 @@ class TAVForMAE(nn.Module):
                 m.bias.data.zero_()
         return model
 
+    def check_visual_status(self):
+        """The status word of the last forward at a capacity, read from the device (a host sync: call it where the step synchronises anyway,
+        e.g. next to loss.item()).  Non-zero -> ValueError: a row of the batch did not fit the capacities the shapes were built for.  The
+        kernels clamped every index and length, so nothing was read or written out of bounds, but that row's result is not what the model
+        computes for it."""
+        status, self._visual_status = getattr(self, "_visual_status", None), None
+        if status is None:
+            return
+        word = int(status.item())
+        if word:
+            why = "; ".join(text for bit, text in STATUS_TEXT.items() if word & bit)
+            raise ValueError(f"ragged video rows exceed the batch's capacity (status {word}): {why}")
+
     def forward(self, input_ids, text_attention_mask, audio_features, video_embeds, visual_mask, hidden_states, pos_embed, attention_mask,
-                batch_size=2, check="train", n_visual_true=None):
+                batch_size=2, check="train", n_visual_true=None, visual_caps=None):
+        """visual_caps (optional) = (cap_true, cap_keep), as given to PreFormer.forward: the fusion rows hold cap_true video slots and the video
+        encoder runs rows of cap_keep tokens; the per-row lengths come from the mask on the device (ops.ragged_lens) and a row that does
+        not fit is reported by check_visual_status() at the caller's next sync."""
         dev = _dev(hidden_states.device if hidden_states.is_cuda else None)
         B, Sf, _ = hidden_states.shape
         ectx = runtime.ctx()
         audio_features, video_embeds = audio_features.to(dev, torch.float32), video_embeds.to(dev, torch.float32)
         visual_mask, input_ids, text_attention_mask = visual_mask.to(dev), input_ids.to(dev), text_attention_mask.to(dev)
-        nt = visual_true_counts(visual_mask, n_visual_true)
-        ragged = isinstance(nt, list)           # (ragged mode with unequal rows; equal rows take the equal path, bit for bit)
+        caps = resolve_visual_caps(visual_mask, n_visual_true, visual_caps)
+        nt = visual_true_counts(visual_mask, n_visual_true) if caps is None else None
+        ragged = caps is not None or isinstance(nt, list)     # (without a bucket, equal rows take the equal path, bit for bit)
         ntok = visual_mask.shape[1]
-        nkeep = None if nt is None else ntok - (min(nt) if ragged else nt)
-        vid_lens = av_lens = None
-        if ragged:
-            # fusion rows: St + Sa + n_true_b valid tokens of Sf (the video segment is last); formed on the device, no copy
-            av_lens = (visual_mask.sum(1) + (Sf - max(nt))).to(torch.int32)
+        vid_lens = av_lens = lens_ready = None
+        self._visual_status = None
+        if caps is not None:
+            nkeep = caps[1]
+            if Sf < caps[0]:
+                raise ValueError(f"hidden_states has {Sf} tokens per row, fewer than the video segment's capacity {caps[0]}")
+            visual_mask = visual_mask.contiguous()
+        else:
+            nkeep = None if nt is None else ntok - (min(nt) if ragged else nt)
+            if ragged:
+                # fusion rows: St + Sa + n_true_b valid tokens of Sf (the video segment is last); formed on the device, no copy
+                av_lens = (visual_mask.sum(1) + (Sf - max(nt))).to(torch.int32)
+
+        def row_lengths():
+            # at a capacity: every length comes from the mask as it is on the device when this runs (a replay reads the mask the host
+            # copied into the static buffer), clamped to the capacities; rows that do not fit set bits of the status word
+            nonlocal vid_lens, av_lens
+            _, vid_lens, av_lens, self._visual_status = ops.ragged_lens(visual_mask, caps[0], caps[1], Sf - caps[0])
 
         def video_branch():
             nonlocal vid_lens
-            if ragged:
+            if caps is not None:
+                v, sv, _ = self.videomae(video_embeds, visual_mask, nkeep, ragged=True, seq_lens=vid_lens)
+            elif ragged:
                 v, sv, vid_lens = self.videomae(video_embeds, visual_mask, nkeep, ragged=True)      # ntok - n_true_b per row
             else:
                 v, sv = self.videomae(video_embeds, visual_mask, nkeep)                  # :480
@@ -301,6 +371,12 @@ class TAVForMAE(nn.Module):
             runtime.share_with(s_txt, input_ids, text_attention_mask)
             with torch.cuda.stream(s_vid):
                 runtime.stream_wait(s_vid, main, ev)           # (ev was recorded on the caller's stream: here, or by PreFormer.forward)
+                if caps is not None:
+                    # the lengths are counted at the head of the video branch (which only waits for the inputs, not for PreFormer's
+                    # kernels); the fusion stack on the caller's stream takes them over through an event
+                    row_lengths()
+                    lens_ready = torch.cuda.Event()
+                    lens_ready.record(s_vid)
                 vid, Sv = video_branch()
             with torch.cuda.stream(s_aud):
                 runtime.stream_wait(s_aud, main, ev)
@@ -309,9 +385,15 @@ class TAVForMAE(nn.Module):
                 runtime.stream_wait(s_txt, main, ev)
                 _, t = self.bert(input_ids, text_attention_mask)                         # :485
         else:
+            if caps is not None:
+                row_lengths()
             aud, Sa = audio_branch()
             vid, Sv = video_branch()
             _, t = self.bert(input_ids, text_attention_mask)
+        if lens_ready is not None:
+            runtime.stream_wait(main, s_vid, lens_ready)
+            for ten in (av_lens, self._visual_status):
+                ten.record_stream(main)
         av = E.EmbedAddFn.apply(hidden_states.to(dev).reshape(B * Sf, 768), pos_embed.to(dev).reshape(-1).contiguous(), self.embedding.weight)   # :474
         av = self.random_mae_encoder(av.view(B, Sf, 768), attention_mask.to(dev), seq_lens=av_lens)     # :487 (fusion branch stays on the caller's stream)
         if runtime.multistream[0]:
@@ -358,7 +440,7 @@ def _draw_visual_mask(B, ntok):
     return m.bool()
 
 
-def collate_batch(batch, check, visual_rows="equal"):
+def collate_batch(batch, check, visual_rows="equal", bucket=None):
     """Batch assembly contract of reference models/tav.py:174-246 for ALREADY DECODED items
     ([{'input_ids','attention_mask'}, waveform 1-D tensor, video [16,3,224,224] (or [3,16,H,W])], label).
     Reproduces: random video token mask True w.p. 1/15 (:207-209) then flips so every row keeps the same number of False
@@ -366,9 +448,9 @@ def collate_batch(batch, check, visual_rows="equal"):
     0/1 mask (:225-228); labels as float tensor.
     visual_rows="ragged": the video mask is drawn exactly as :207-209 and left as drawn -- every row keeps its own count (train with
     runtime.set_visual_rows("ragged")).  The reference's fix-up of the batch TOTAL (:211-217) only exists to make its reshape(B, -1, C) legal
-    and is not applied."""
-    if visual_rows not in ("equal", "ragged"):
-        raise ValueError(f"visual_rows must be 'equal' or 'ragged', got {visual_rows!r}")
+    and is not applied.  bucket: the bucket the run trains with (runtime.set_visual_rows("ragged", bucket=g)); checked like the runtime
+    switch checks it and otherwise without effect -- the mask is drawn the same, the padded sizes are the step's business."""
+    runtime.check_visual_rows(visual_rows, bucket)
     texts, masks, speech, vids, labels = [], [], [], [], []
     for (inp, label) in batch:
         texts.append(torch.as_tensor(inp[0]["input_ids"]).reshape(-1))
@@ -410,14 +492,14 @@ def sample_video_mask(B, ntok, n_true=None, device="cpu", generator=None):
     return torch.zeros(B, ntok, dtype=torch.bool, device=device).scatter_(1, idx, True)
 
 
-def collate_batch_device(batch, check, device="cuda", n_visual_true=None, generator=None, visual_rows="equal"):
+def collate_batch_device(batch, check, device="cuda", n_visual_true=None, generator=None, visual_rows="equal", bucket=None):
     """collate_batch with the tensor work on `device`: items are decoded utterances as for collate_batch; every
     tensor is shipped once (non-blocking) and padding, the audio length mask (reference :225-228) and the video token mask are built
     there, sync-free: nothing in the step reads them back (PreFormer / TAVForMAE take `n_visual_true` instead of counting).
     visual_rows="ragged": the video mask is drawn on the HOST as in collate_batch(visual_rows="ragged") and shipped; its per-row True
-    counts come back as visual["n_visual_true"] (a list), to be passed on as n_visual_true -- known without a device read."""
-    if visual_rows not in ("equal", "ragged"):
-        raise ValueError(f"visual_rows must be 'equal' or 'ragged', got {visual_rows!r}")
+    counts come back as visual["n_visual_true"] (a list), to be passed on as n_visual_true -- known without a device read (the training
+    loops and graph mode pick them up from there).  bucket: as in collate_batch."""
+    runtime.check_visual_rows(visual_rows, bucket)
     texts, masks, speech, vids, labels = [], [], [], [], []
     for (inp, label) in batch:
         texts.append(torch.as_tensor(inp[0]["input_ids"]).reshape(-1))

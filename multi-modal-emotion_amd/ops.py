@@ -631,6 +631,25 @@ def mask_to_index(mask_bool, keep_value, nkeep):
     return idx, counts
 
 
+RAGGED_OVER_TRUE, RAGGED_OVER_KEEP = 1, 2        # bits of the status word (include/tavhip.h)
+
+
+def ragged_lens(mask_bool, cap_true, cap_keep, base):
+    """Per-row lengths of a ragged batch at fixed capacities, from the video mask [B, ntok] as it is on the device when the kernel runs:
+    -> (true_cnt, vid_lens = min(ntok - true_cnt, cap_keep), av_lens = base + min(true_cnt, cap_true), status), int32 [B] x 3 and int32 [1].
+    status is zeroed here and gets RAGGED_OVER_TRUE / RAGGED_OVER_KEEP OR-ed in by rows that do not fit (tav_ragged_lens)."""
+    B, n = mask_bool.shape
+    m8 = mask_bool.view(torch.uint8) if mask_bool.dtype == torch.bool else mask_bool
+    if not m8.is_contiguous():
+        raise ValueError("ragged_lens: the mask must be contiguous")
+    dev = mask_bool.device
+    true_cnt, vid_lens, av_lens = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib().tav_ragged_lens(ptr(m8), ptr(true_cnt), ptr(vid_lens), ptr(av_lens), ptr(status), B, n, int(cap_true), int(cap_keep), int(base),
+                                stream()), "ragged_lens")
+    return true_cnt, vid_lens, av_lens, status
+
+
 def patchify(video, keep_idx, dtype):
     B, F, Cc, H, W = video.shape
     assert Cc == 3 and video.dtype == torch.float32 and video.is_contiguous()

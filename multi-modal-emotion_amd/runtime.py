@@ -25,17 +25,58 @@ def precision():
 # ---- visual rows: "equal" (every row of a batch keeps the same number of video tokens; unequal rows raise ValueError) or "ragged"
 # (each utterance keeps its own count: the video and fusion stacks run on padded rows with per-row lengths)
 _visual_rows = ["equal"]
+# ragged rows at a bucketed capacity (opt-in): with a bucket g > 0 the two shapes a ragged batch gives the step -- the video segment of the
+# fusion rows and the row length of the video encoder -- are rounded outwards to multiples of g (visual_capacities), so batches whose counts
+# fall into the same bucket share their shapes (and a captured graph, train_model/graphed.py); the counts themselves live on the device.
+_visual_bucket = [0]
 
 
-def set_visual_rows(mode="equal"):
+def check_visual_rows(mode, bucket=None):
+    """Validate a (mode, bucket) pair -> the bucket as an int (0: off).  Shared by set_visual_rows, the collate functions and the CLI."""
     if mode not in ("equal", "ragged"):
         raise ValueError(f"visual rows must be 'equal' or 'ragged', got {mode!r}")
+    if bucket is None:
+        bucket = 0
+    if isinstance(bucket, bool) or not isinstance(bucket, int) or bucket < 0:
+        raise ValueError(f"visual rows: bucket must be a positive int (None or 0: off), got {bucket!r}")
+    if bucket and mode != "ragged":
+        raise ValueError("visual rows: a bucket only applies to 'ragged' rows")
+    return bucket
+
+
+def set_visual_rows(mode="equal", bucket=None):
+    """bucket (ragged only): a positive int rounds the padded sizes to multiples of it; None or 0 = natural sizes (max / min of the batch)."""
+    _visual_bucket[0] = check_visual_rows(mode, bucket)
     _visual_rows[0] = mode
     return mode
 
 
 def visual_rows():
     return _visual_rows[0]
+
+
+def visual_bucket():
+    """The bucket of ragged rows (0: off)."""
+    return _visual_bucket[0] if _visual_rows[0] == "ragged" else 0
+
+
+def visual_capacities(nt, ntok, g):
+    """(cap_true, cap_keep) of a batch whose rows keep `nt` True tokens of `ntok`, for bucket g >= 1:
+      cap_true = min(ntok, ceil(max(nt) / g) * g)    video segment of the fusion rows (PreFormer)
+      cap_keep = ntok - floor(min(nt) / g) * g       row length of the video encoder
+    g = 1 gives the natural sizes max(nt) and ntok - min(nt).  Every row needs at least one True token (the device check of
+    tav_ragged_lens refuses such a row too) and the video encoder at least one token to keep."""
+    nt = [int(c) for c in nt]
+    ntok, g = int(ntok), int(g)
+    if g < 1:
+        raise ValueError(f"visual_capacities: bucket must be >= 1, got {g}")
+    if not nt or min(nt) < 1 or max(nt) > ntok:
+        raise ValueError(f"visual_capacities: every row must keep between 1 and {ntok} True tokens, got {nt}")
+    cap_true = min(ntok, -(-max(nt) // g) * g)
+    cap_keep = ntok - (min(nt) // g) * g
+    if cap_keep < 1:
+        raise ValueError(f"visual_capacities: every row is all True ({ntok} tokens): the video encoder keeps nothing")
+    return cap_true, cap_keep
 
 
 # ---- branch streams: text / audio / video encoders run beside the fusion encoder (reference models/tav.py:476-487 are

@@ -11,6 +11,11 @@ length (grad_accum) as a multiplication by a device scalar, backward and TrainSt
   * metrics and the running loss are taken from the static logits / loss -- one host sync per step, the reference's per-batch loss.item().
 A batch whose signature (input shapes and dtypes, video tokens per row, loss branch, loop kind) has not been seen in this epoch runs the
 eager step -- the same code as graphs=False -- and is then captured (at most `max_graphs` per epoch; later new signatures stay eager).
+Ragged video rows: without a bucket a batch of unequal rows has no signature and stays eager.  With runtime.set_visual_rows("ragged", bucket=g)
+the signature carries ("ragged", cap_true, cap_keep) -- runtime.visual_capacities of the batch's counts -- in place of the per-row count:
+the captured step is built from the two capacities alone and reads every length from the mask in its static buffer (ops.ragged_lens), so all
+batches whose counts fall into the bucket replay one graph.  The host knows the counts before it replays, so a batch that does not fit never
+reaches a graph; the status word the step leaves is read together with the loss all the same.
 Graphs are freed at the end of every epoch and whenever the optimizer's state was reloaded (load_model builds new moment tensors).
 """
 import weakref
@@ -31,9 +36,9 @@ def _recip32(n):
 class _Captured:
     """One captured step and its static tensors."""
 
-    def __init__(self, cap, static_in, static_label, scale, loss, logits, label):
+    def __init__(self, cap, static_in, static_label, scale, loss, logits, label, status=None):
         self.cap, self.static_in, self.static_label, self.scale = cap, static_in, static_label, scale
-        self.loss, self.logits, self.label = loss, logits, label
+        self.loss, self.logits, self.label, self.status = loss, logits, label, status
 
     def feed(self, input, label):
         for d, sd in zip(input, self.static_in):
@@ -50,7 +55,7 @@ class _Captured:
 
     def release(self):
         self.cap.graph.reset()
-        self.cap = self.static_in = self.static_label = self.scale = self.loss = self.logits = self.label = None
+        self.cap = self.static_in = self.static_label = self.scale = self.loss = self.logits = self.label = self.status = None
 
 
 class GraphedSteps:
@@ -70,29 +75,41 @@ class GraphedSteps:
         self._nv_seen = {}
 
     # ---- what makes a batch replayable by a graph
-    def _n_visual(self, input):
-        """Video tokens per row (every row must keep the same number; None if they differ -- the eager step then raises as it always did).
-        A mask on the device costs a host read: remembered per tensor object (weak reference) and version, so batches cycled on the
-        device are counted once."""
+    def _visual_counts(self, input):
+        """True video tokens of every row, a host list: the counts the collate put next to the mask (`n_visual_true`) when it did, else
+        read from the mask.  A mask on the device costs a host read: remembered per tensor object (weak reference) and version, so
+        batches cycled on the device are counted once."""
+        given = input[2].get("n_visual_true")
+        if given is not None:
+            return [int(c) for c in (given.tolist() if torch.is_tensor(given) else given)]
         vm = input[2]["attention_mask"]
         hit = self._nv_seen.get(id(vm))
         if hit is not None and hit[0]() is vm and hit[1] == vm._version:
             return hit[2]
-        c = vm.sum(1).cpu()
-        nv = int(c[0]) if c.numel() and bool((c == c[0]).all()) else None
+        counts = [int(c) for c in vm.sum(1).cpu().tolist()]
         if vm.is_cuda:
             if len(self._nv_seen) >= 64:
                 self._nv_seen.clear()
-            self._nv_seen[id(vm)] = (weakref.ref(vm), vm._version, nv)
-        return nv
+            self._nv_seen[id(vm)] = (weakref.ref(vm), vm._version, counts)
+        return counts
+
+    def _n_visual(self, input):
+        """Video tokens per row (every row must keep the same number; None if they differ -- the eager step then raises as it always did,
+        or, in ragged mode without a bucket, runs the batch at its natural sizes)."""
+        c = self._visual_counts(input)
+        return c[0] if c and all(v == c[0] for v in c) else None
 
     def signature(self, input, label, epoch, accum):
-        nv = self._n_visual(input)
-        if nv is None:
-            return None
+        if runtime.visual_bucket():
+            # ragged rows at a bucketed capacity: the two padded sizes stand for the counts (equal rows included -- one path per bucket)
+            nv = ("ragged",) + runtime.visual_capacities(self._visual_counts(input), input[2]["attention_mask"].shape[1], runtime.visual_bucket())
+        else:
+            nv = self._n_visual(input)
+            if nv is None:
+                return None
         crit = self.stepper.criterion
         branch = (epoch % crit.epoch_switch == 0) if hasattr(crit, "epoch_switch") else None      # NewCrossEntropyLoss: weighted or not
-        shapes = tuple(None if d is None else tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(d.items())) for d in input)
+        shapes = tuple(None if d is None else tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(d.items()) if torch.is_tensor(v)) for d in input)
         return (shapes, (tuple(label.shape), label.dtype), nv, "train", branch, bool(accum))
 
     # ---- one training step
@@ -113,10 +130,13 @@ class GraphedSteps:
     def _eager(self, input, label, epoch, Metric, accum_iter):
         """Exactly the eager loop's step (tav_train.not_grad_accum / grad_accum without a reducer)."""
         st = self.stepper
-        loss = T.get_statistics(input, label, st.model, st.pre, st.criterion, Metric, check="train", epoch=epoch)
+        # (at a bucketed capacity the counts signature() already has go along: the step pads as the eager loop does, without a second host read)
+        kw = {"n_visual_true": self._visual_counts(input)} if runtime.visual_bucket() else {}
+        loss = T.get_statistics(input, label, st.model, st.pre, st.criterion, Metric, check="train", epoch=epoch, **kw)
         if accum_iter is not None:
             loss = loss / accum_iter
         v = loss.item()
+        T.check_visual_rows(st.model)
         loss.backward()
         st.update()
         self.eager_steps += 1
@@ -132,14 +152,23 @@ class GraphedSteps:
         if Metric is not None:
             Metric.update_metrics(torch.argmax(g.logits, dim=1), g.label)
         self.replays += 1
-        return g.loss.item()
+        v = g.loss.item()
+        status = getattr(g, "status", None)
+        if status is not None and int(status.item()):        # (cannot happen: signature() sized the capacities from this batch's counts)
+            raise ValueError(f"replayed ragged step: a row of the batch did not fit the captured capacities (status {int(status.item())})")
+        return v
 
     def _capture(self, input, label, epoch, accum, n_visual_true):
         """Capture the step on the current stream (the one the loop runs on).  Runs right after an eager step of the same signature: the
-        optimizer's moments exist, and the capture itself executes nothing -- no dropout draw, no update is consumed."""
+        optimizer's moments exist, and the capture itself executes nothing -- no dropout draw, no update is consumed.
+        n_visual_true: the signature's entry -- the per-row count, or ("ragged", cap_true, cap_keep): then only the two capacities shape the
+        captured step, nothing derived from this batch's own counts."""
         st = self.stepper
         dev = torch.device("cuda", torch.cuda.current_device())
-        static_in = [None if d is None else {k: v.to(dev, copy=True) for k, v in d.items()} for d in input]
+        kw = {"n_visual_true": n_visual_true}
+        if isinstance(n_visual_true, tuple):
+            kw = {"visual_caps": n_visual_true[1:]}
+        static_in = [None if d is None else {k: v.to(dev, copy=True) for k, v in d.items() if torch.is_tensor(v)} for d in input]
         static_label = label.to(dev, copy=True)
         scale = torch.ones((), dtype=torch.float32, device=dev) if accum else None
         st.opt.sync_lr()                         # (so that the captured AdamW records no learning-rate upload of its own)
@@ -147,13 +176,14 @@ class GraphedSteps:
         graph = torch.cuda.CUDAGraph()
         cap = runtime.capture(graph, torch.cuda.current_stream())
         with cap:
-            loss, logits, lab = T._statistics(static_in, static_label, st.model, st.pre, st.criterion, None, check="train", epoch=epoch,
-                                              n_visual_true=n_visual_true)
+            loss, logits, lab = T._statistics(static_in, static_label, st.model, st.pre, st.criterion, None, check="train", epoch=epoch, **kw)
+            status = getattr(st.model, "_visual_status", None)
             if scale is not None:
                 loss = loss * scale
             loss.backward()
             st.update()
-        return _Captured(cap, static_in, static_label, scale, loss.detach(), logits.detach(), lab)
+        st.model._visual_status = None           # (the word belongs to the graph; an eager check must not read a capture's placeholder)
+        return _Captured(cap, static_in, static_label, scale, loss.detach(), logits.detach(), lab, status)
 
     def invalidate(self):
         """Free every captured step (end of an epoch, reloaded optimizer state)."""

@@ -49,25 +49,37 @@ class CosineWarmRestarts:
             self.opt.lr = sd["_last_lr"][0]
 
 
-def get_statistics(input, label, model, PREFormer, criterion, Metric, check="train", epoch=None, n_visual_true=None):
-    return _statistics(input, label, model, PREFormer, criterion, Metric, check, epoch, n_visual_true)[0]
+def get_statistics(input, label, model, PREFormer, criterion, Metric, check="train", epoch=None, n_visual_true=None, visual_caps=None):
+    return _statistics(input, label, model, PREFormer, criterion, Metric, check, epoch, n_visual_true, visual_caps)[0]
 
 
-def _statistics(input, label, model, PREFormer, criterion, Metric, check="train", epoch=None, n_visual_true=None):
-    """get_statistics -> (batch loss, logits, labels as int64 on the device): the captured step of graphed.py keeps the last two for the metrics."""
+def check_visual_rows(model):
+    """After the step's host sync (loss.item()): a ragged batch run at a bucketed capacity reports rows that did not fit (ValueError)."""
+    chk = getattr(model, "check_visual_status", None)
+    if chk is not None:
+        chk()
+
+
+def _statistics(input, label, model, PREFormer, criterion, Metric, check="train", epoch=None, n_visual_true=None, visual_caps=None):
+    """get_statistics -> (batch loss, logits, labels as int64 on the device): the captured step of graphed.py keeps the last two for the metrics.
+    n_visual_true defaults to the per-row counts the collate put next to the mask (collate_batch_device(visual_rows="ragged")), if any;
+    visual_caps = (cap_true, cap_keep) fixes the padded sizes of a ragged batch (a captured step: nothing is read from the host)."""
     device = "cuda"
     batch_size = len(label)
     text, audio_features, video_embeds = input[0], input[1], input[2]
     text_input_ids, text_attention_mask = text["input_ids"], text["attention_mask"]
     audio_input_ids, audio_attention_mask = audio_features["audio_features"], audio_features["attention_mask"]
     video_input_ids, video_attention_mask = video_embeds["visual_embeds"], video_embeds["attention_mask"]
+    if n_visual_true is None and visual_caps is None:
+        n_visual_true = video_embeds.get("n_visual_true")
+    caps = {} if visual_caps is None else {"visual_caps": visual_caps}
     tav, tav_embed, attention_mask = PREFormer(input_ids=text_input_ids, audio_features=audio_input_ids, video_embeds=video_input_ids,
                                                text_mask=text_attention_mask, audio_mask=audio_attention_mask, visual_mask=video_attention_mask,
-                                               device=device, train=True if check == "train" else False, n_visual_true=n_visual_true)
+                                               device=device, train=True if check == "train" else False, n_visual_true=n_visual_true, **caps)
     output = model(input_ids=text_input_ids.to(device), text_attention_mask=text_attention_mask.to(device), audio_features=audio_input_ids.to(device),
                    video_embeds=video_input_ids.to(device), visual_mask=video_attention_mask.to(device), hidden_states=tav.to(device),
                    pos_embed=tav_embed.to(device), attention_mask=attention_mask.to(device), batch_size=batch_size, check=check,
-                   n_visual_true=n_visual_true)
+                   n_visual_true=n_visual_true, **caps)
     label = label.to(device).long()          # (the reference's .type(torch.LongTensor) would bounce through the host)
     if Metric is not None:
         Metric.update_metrics(torch.argmax(output, dim=1), label.long())
@@ -119,6 +131,7 @@ def validate(val_dataloader, model, PREFormer, criterion, Metric, name="val"):
             loss = get_statistics(val_input, val_label, model, PREFormer, criterion, Metric, name, epoch=None)
             if criterion is not None:
                 total += loss.item()
+            check_visual_rows(model)
         log(Metric, total / len(val_dataloader) if criterion is not None else 0, name)
     return total / len(val_dataloader)
 
@@ -148,6 +161,7 @@ def not_grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, cr
         else:
             loss = get_statistics(train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch)
             total_loss_train += loss.item()
+            check_visual_rows(model)
             loss.backward()
             if stepper.reducer is not None:
                 stepper.reducer.finish()
@@ -185,6 +199,7 @@ def grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criter
         else:
             loss = get_statistics(train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch) / accum_iter
             total_loss_train += loss.item()
+            check_visual_rows(model)
             loss.backward()
             if stepper.reducer is not None:
                 stepper.reducer.finish()

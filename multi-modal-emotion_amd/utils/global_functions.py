@@ -170,6 +170,9 @@ def arg_parse(description, argv=None):
     parser.add_argument("--synthetic", default=64, type=int, help="number of synthetic utterances per split (no dataset files are read)")
     parser.add_argument("--visual-rows", dest="visual_rows", default="equal", choices=["equal", "ragged"],
                         help="ragged: every utterance keeps its own number of visible video tokens (runtime.set_visual_rows)")
+    parser.add_argument("--visual-bucket", dest="visual_bucket", default=0, type=int,
+                        help="with --visual-rows ragged: pad ragged batches to multiples of this many tokens, so that batches of one bucket share "
+                             "their shapes and, with --graph 1, one captured step (0: natural sizes, ragged batches stay eager)")
     parser.add_argument("--graph", default=0, type=int, choices=[0, 1],
                         help="1: replay each training step from a captured hipGraph (tav_nn only; train_tav_network(graphs=True))")
     return parser.parse_args(argv)
