@@ -564,7 +564,7 @@ __global__ void clip_coef_kernel(const float* sumsq, float max_norm, float* coef
     const float norm = sqrtf(sumsq[0]);
     if (norm_out) norm_out[0] = norm;
     float c = max_norm / (norm + 1e-6f);            // torch.nn.utils.clip_grad_norm_
-    coef[0] = c < 1.f ? c : 1.f;
+    coef[0] = c > 1.f ? 1.f : c;                    // clamp(max=1): a NaN norm gives a NaN coefficient (as torch does), never a silent 1
 }
 // step counter lives on the device so that a captured hipGraph replays with the right bias correction
 __global__ void adam_tick_kernel(int* step, float b1, float b2, float* bc) {

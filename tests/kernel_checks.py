@@ -6,10 +6,12 @@ tools/gpu_kernel_check.py (prints a table without stopping at the first failure)
 import contextlib
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
 import guarded
+import step_end_ref as SR
 import tav_amd.ops as ops
 
 DEV = "cuda"
@@ -773,7 +775,8 @@ def check_gemm_nt_edges(dtype, hint):
 
 def check_fp8_quantize_edges():
     """rows not a multiple of the transposing tile (1, 33, 1025: one past the padding unit too), the smallest legal cols (4) and a ragged 132:
-    q against torch's own e4m3 conversion, qt its transpose, qt's padding columns exactly zero; nothing past rows_pad (the guard)."""
+    q against torch's own e4m3 conversion, qt its transpose, qt's padding columns exactly zero; nothing past rows_pad (the guard).  Then ties,
+    e4m3 subnormals and an all-zero tensor (check_fp8_quantize_ties)."""
     rs = []
     for rows, cols in ((1, 4), (33, 4), (33, 132), (1025, 132), (1, 1024)):
         for dtype in (torch.float32, torch.bfloat16):
@@ -787,7 +790,7 @@ def check_fp8_quantize_edges():
             pad = f.qt[:, rows:].contiguous().view(torch.uint8)
             rs.append((tag + ".qt_pad bytes zero", float(pad.ne(0).sum().item()), 0.0, not bool(pad.ne(0).any())))
             rs.append(_res(tag + ".amax", f.scales[2:3], x.float().abs().max().reshape(1), 0.0))
-    return rs
+    return rs + check_fp8_quantize_ties()
 
 
 def check_gemm_tn_edges(dtype):
@@ -1176,6 +1179,594 @@ def check_fp8_edges(M, N, K, tile_m):
     return rs
 
 
+
+# ------------------------------------------------------------------------------------------------ step-end kernels ("Step-end checks")
+# Between one backward pass and the next forward pass: gradient norm, clip coefficient, AdamW, operand casts, fp8 state roll.  The optimizer
+# checks call the C ABI with pointer / size / chunk tables built here; reference and bounds are tests/step_end_ref.py (fp64, per element).
+_GAP = 36                    # floats of 0xFF between two slices of an arena (a multiple of 4: alignment is decided by `mis` alone)
+
+
+def _exact(name, got, ref):
+    """Result tuple of a comparison that has ONE right answer: same shape, same dtype, every element equal (no tolerance)."""
+    if got.shape != ref.shape or got.dtype != ref.dtype:
+        return (name + f" shape/dtype {tuple(got.shape)} {got.dtype} vs {tuple(ref.shape)} {ref.dtype}", float("inf"), 0.0, False)
+    bad = int(got.ne(ref).sum().item()) + int(got.ne(got).sum().item())           # (a NaN -- an unwritten 0xFF element -- never counts as equal)
+    return (name, float(bad), 0.0, bad == 0)
+
+
+def _refill(t):
+    """Every byte of a contiguous buffer back to 0xFF (an output reused by the next launch must not keep the previous launch's values)."""
+    assert t.is_contiguous()
+    t.view(torch.uint8).fill_(0xFF)
+
+
+class _Arena:
+    """The tensors of one role as slices of one 0xFF buffer with 0xFF gaps between them (a 1 MiB flat guard per tensor would cost gigabytes);
+    mis = True starts every slice 4 bytes past a 16-byte boundary."""
+
+    def __init__(self, sizes, mis):
+        self.sizes, self.starts, c = list(sizes), [], _GAP
+        for n in sizes:
+            self.starts.append(c + (1 if mis else 0))
+            c = (self.starts[-1] + n + 3) // 4 * 4 + _GAP
+        self.buf = _blank((c,), torch.float32)
+        assert self.buf.data_ptr() % 16 == 0
+        idx = torch.cat([torch.arange(s, s + n) for s, n in zip(self.starts, sizes)])
+        self.idx = idx.to(DEV)
+        gap = torch.ones(c, dtype=torch.bool)
+        gap[idx] = False
+        self.gap_idx = gap.nonzero().flatten().to(DEV)
+        self.ptrs = [self.buf.data_ptr() + 4 * s for s in self.starts]
+        assert all((p_ % 16 == 4) == bool(mis) and p_ % 16 in (0, 4) for p_ in self.ptrs)
+
+    def put(self, flat):
+        self.buf[self.idx] = torch.as_tensor(flat, dtype=torch.float32).to(DEV)
+
+    def get(self):
+        return self.buf[self.idx].cpu().numpy()
+
+    def gaps(self):
+        return self.buf[self.gap_idx]
+
+    def table(self):
+        return _in(torch.tensor(self.ptrs, dtype=torch.int64).to(DEV))
+
+
+_LAYOUTS = {"aligned": (False, False), "all+4B": (True, True), "grads+4B": (False, True)}        # name -> (params / moments misaligned, gradients misaligned)
+
+
+def _i32(vals):
+    return _in(torch.tensor(vals, dtype=torch.int32).to(DEV))
+
+
+def _i64(vals):
+    return _in(torch.tensor(vals, dtype=torch.int64).to(DEV))
+
+
+def check_optimizer_step(list_name, layout, wd):
+    """tav_adamw_chunked and tav_adamw_multi, three steps from zero moments (SR.step_plan: no clip pointer / coefficient < 1 / coefficient 1 after
+    the device lr word was halved), each step against the fp64 reference restarted from the kernel's own previous state, per-element bounds of
+    step_end_ref.py, err = worst |got - ref| / bound.  The chunked form walks its own trajectory; the multi form takes every step from the
+    chunked form's previous state, so the two can also be compared with each other (within the sum of their bounds; they are not bitwise
+    equal).  After every step: the step word counts the calls, bias_corr = 1 - b^s to 4u, arena gaps still 0xFF, gradients bit-identical."""
+    L = ops.lib()
+    sizes = SR.SIZE_LISTS[list_name]
+    mis_p, mis_g = _LAYOUTS[layout]
+    n_all, nt = sum(sizes), len(sizes)
+    p0, g0 = SR.make_inputs(n_all, seed=len(sizes) + 1000 * list(_LAYOUTS).index(layout))
+    G = _Arena(sizes, mis_g)
+    G.put(g0)
+    g_snapshot = G.buf.clone().view(torch.int32)
+    forms = {}
+    for form in ("chunked", "multi"):
+        A = dict(p=_Arena(sizes, mis_p), m=_Arena(sizes, mis_p), v=_Arena(sizes, mis_p))
+        A["p"].put(p0)
+        A["m"].put(np.zeros(n_all))
+        A["v"].put(np.zeros(n_all))
+        scal = _blank((8,), torch.float32)                            # [1] clip coefficient, [4] lr, [5:7] bias_corr (as optim.FusedAdamW lays them out)
+        step = _blank((1,), torch.int32)
+        step.zero_()
+        scal[4] = SR.LR
+        forms[form] = dict(A=A, scal=scal, step=step, t=[A[k].table() for k in "pmv"])
+    t_g, t_s = G.table(), _i64(sizes)
+    pre, nchunks = SR.chunk_prefix(sizes, int(L.tav_optim_chunk_elems()))
+    t_c = _i32(pre)
+    b1, b2 = SR.BETAS
+    tag0 = f"adamw[{list_name},{layout},wd{wd:g}]"
+    rs = []
+    for (s, lr, cc, with_ptr) in SR.step_plan():
+        C_, M_ = forms["chunked"], forms["multi"]
+        for k in "pmv":                                               # the multi form starts from the chunked form's state (bitwise, gaps included)
+            M_["A"][k].buf.copy_(C_["A"][k].buf)
+        before = {k: C_["A"][k].get() for k in "pmv"}
+        got = {}
+        for form, f in forms.items():
+            if s == 3:
+                f["scal"][4:5].mul_(0.5)                              # halve the device learning-rate word, change nothing else
+            f["scal"][1] = cc
+            coef = ops.ptr(f["scal"][1:2]) if with_ptr else None
+            tp, tm, tv = (ops.ptr(t) for t in f["t"])
+            if form == "chunked":
+                ops.check(L.tav_adamw_chunked(tp, ops.ptr(t_g), tm, tv, ops.ptr(t_s), ops.ptr(t_c), nt, nchunks, coef, ops.ptr(f["scal"][4:5]), b1, b2,
+                                              SR.EPS, wd, ops.ptr(f["step"]), ops.ptr(f["scal"][5:7]), ops.stream()), "adamw_chunked")
+            else:
+                ops.check(L.tav_adamw_multi(tp, ops.ptr(t_g), tm, tv, ops.ptr(t_s), nt, coef, ops.ptr(f["scal"][4:5]), b1, b2, SR.EPS, wd,
+                                            ops.ptr(f["step"]), ops.ptr(f["scal"][5:7]), ops.stream()), "adamw_multi")
+            got[form] = {k: f["A"][k].get() for k in "pmv"}
+        lr_dev = float(C_["scal"][4].item())
+        ref = SR.ref_step(before["p"], g0, before["m"], before["v"], s, lr_dev, wd, cc)
+        for form, f in forms.items():
+            tag = f"{tag0}.step{s}.{form}"
+            for k, r in SR.ratios(ref, got[form]["p"], got[form]["m"], got[form]["v"]).items():
+                rs.append((f"{tag}.{k} ratio to bound", r, 1.0, r <= 1.0))
+            sw = int(f["step"].item())
+            rs.append((tag + ".step word", float(abs(sw - s)), 0.0, sw == s))
+            bc = f["scal"][5:7].cpu().numpy().astype(np.float64)
+            e_bc = float(np.abs(bc - np.array(SR.bias_corr(s))).max() / (4 * SR.U))
+            rs.append((tag + ".bias_corr / 4u", e_bc, 1.0, e_bc <= 1.0))
+            e_lr = abs(float(f["scal"][4].item()) - lr)
+            rs.append((tag + ".lr word", e_lr, 0.0, e_lr == 0.0))
+            rs.append(_all_ff(tag + ".gap", *[f["A"][k].gaps() for k in "pmv"], f["scal"][0:1], f["scal"][2:4], f["scal"][7:8]))
+        for k in "pmv":                                               # chunked against multi, from the same state: the sum of their two bounds
+            r = SR.ratio(got["chunked"][k], got["multi"][k].astype(np.float64), 2 * ref[k + "_bound"])
+            rs.append((f"{tag0}.step{s}.chunked vs multi.{k}", r, 1.0, r <= 1.0))
+        same = torch.equal(G.buf.view(torch.int32), g_snapshot)
+        rs.append((f"{tag0}.step{s}.gradients bit-identical", 0.0 if same else 1.0, 0.0, bool(same)))
+    return rs
+
+
+def _d_final(n):
+    """Longest chain of additions through sum_final_kernel for n partials: accumulator a0 takes one addition per pass of the 4-way loop
+    (n // 1024 passes at most) and up to three in the 256-stride tail loop; (a0 + a1) + (a2 + a3) is two more; the 256-wide LDS tree eight."""
+    return n // 1024 + 3 + 2 + 8
+
+
+def check_grad_norm():
+    """tav_sumsq_chunked, tav_sumsq_multi and tav_sum_partials against the fp64 sum of squares.  Every term is positive, so a relative bound
+    holds: (D + 3) u with D the longest chain of f32 additions any element goes through (each rounds by at most u relative to a partial sum
+    that never exceeds the total); the + 3 covers the square, the subnormal-free tail and the final rounding.
+      sumsq_chunk_kernel   misaligned chunk: a thread adds 16384 / 256 = 64 squares one by one (the 16-byte form: 16 passes of 4 additions);
+                           wave_sum is 6 butterfly steps, red[0] + .. + red[3] three more: D1 = 64 + 6 + 3 = 73
+      sumsq_multi_kernel   96 x 256 threads stride over a tensor: ceil(n / 24576) additions per thread, then the 256-wide tree, 8: D1 = that + 8
+      sum_final_kernel     _d_final(number of partials)
+    With at most 70 chunks / 67 x 96 partials here D stays below 100, (D + 3) u below 2^-16 (asserted)."""
+    L = ops.lib()
+    rs = []
+    for list_name, sizes in SR.SIZE_LISTS.items():
+        for mis in (False, True):
+            nt = len(sizes)
+            _, g0 = SR.make_inputs(sum(sizes), seed=77 + nt)
+            G = _Arena(sizes, mis)
+            G.put(g0)
+            snap = G.buf.clone().view(torch.int32)
+            want = float((g0.astype(np.float64) ** 2).sum())
+            t_g, t_s = G.table(), _i64(sizes)
+            pre, nchunks = SR.chunk_prefix(sizes, int(L.tav_optim_chunk_elems()))
+            outs = _blank((4,), torch.float32)
+            part_c = _blank((nchunks,), torch.float32)
+            ops.check(L.tav_sumsq_chunked(ops.ptr(t_g), ops.ptr(t_s), ops.ptr(_i32(pre)), nt, nchunks, ops.ptr(part_c), ops.ptr(outs[0:1]), ops.stream()), "sumsq_chunked")
+            n_part = int(L.tav_sumsq_partials(nt))
+            part_m = _blank((n_part,), torch.float32)
+            ops.check(L.tav_sumsq_multi(ops.ptr(t_g), ops.ptr(t_s), nt, ops.ptr(part_m), ops.ptr(outs[1:2]), ops.stream()), "sumsq_multi")
+            ops.check(L.tav_sum_partials(ops.ptr(part_c), nchunks, ops.ptr(outs[2:3]), ops.stream()), "sum_partials")
+            d_c = 1 + 73 + _d_final(nchunks)
+            d_m = 1 + -(-max(sizes) // (96 * 256)) + 8 + _d_final(n_part)
+            tag = f"sumsq[{list_name},{'+4B' if mis else 'aligned'}]"
+            for form, d, k in (("chunked", d_c, 0), ("multi", d_m, 1)):
+                bound = (d + 3) * SR.U
+                assert bound <= 2.0 ** -16, (form, d)
+                r = abs(float(outs[k].item()) - want) / want / bound
+                rs.append((f"{tag}.{form} rel err / ((D={d}) + 3)u", r, 1.0, r <= 1.0))
+            same = torch.equal(outs[2:3], outs[0:1])
+            rs.append((tag + ".sum_partials == second stage bitwise", 0.0 if same else 1.0, 0.0, bool(same)))
+            rs.append(_all_ff(tag + ".gap", G.gaps(), outs[3:4]))
+            same = torch.equal(G.buf.view(torch.int32), snap)
+            rs.append((tag + ".gradients bit-identical", 0.0 if same else 1.0, 0.0, bool(same)))
+    # the boundaries of sum_final_kernel's 4-way loop (i + 768 < n, 256 threads): n one-element tensors make n chunks, whose partials are the
+    # squares themselves (a wave sum of one value and zeros is exact)
+    for n in (1, 255, 256, 257, 1023, 1024, 1025, 1279):
+        sizes = [1] * n
+        _, g0 = SR.make_inputs(n, seed=500 + n)
+        g0[g0 == 0] = 3.0
+        G = _Arena(sizes, bool(n % 2))
+        G.put(g0)
+        outs = _blank((3,), torch.float32)
+        part = _blank((n,), torch.float32)
+        ops.check(L.tav_sumsq_chunked(ops.ptr(G.table()), ops.ptr(_i64(sizes)), ops.ptr(_i32(list(range(n)))), n, n, ops.ptr(part), ops.ptr(outs[0:1]), ops.stream()),
+                  "sumsq_chunked")
+        ops.check(L.tav_sum_partials(ops.ptr(part), n, ops.ptr(outs[1:2]), ops.stream()), "sum_partials")
+        sq = torch.as_tensor(g0).to(DEV)
+        sq = sq * sq
+        tag = f"sum_partials[n{n}]"
+        rs.append(_exact(tag + ".partials are the squares", part, sq))
+        want = float(sq.double().sum().item())
+        bound = (_d_final(n) + 3) * SR.U
+        r = abs(float(outs[1].item()) - want) / want / bound
+        rs.append((f"{tag} rel err / ((D={_d_final(n)}) + 3)u", r, 1.0, r <= 1.0))
+        same = torch.equal(outs[0:1], outs[1:2])
+        rs.append((tag + " == second stage of sumsq_chunked bitwise", 0.0 if same else 1.0, 0.0, bool(same)))
+        rs.append(_all_ff(tag + ".gap", G.gaps(), outs[2:3]))
+    return rs
+
+
+def check_clip_coef():
+    """clip_grad_norm_'s coefficient min(1, max_norm / (norm + 1e-6)) at sumsq = 0, finite above / below max_norm, +inf and NaN: a NaN norm gives a
+    NaN coefficient (every parameter goes NaN, loudly), an infinite one 0.  norm within 2u of sqrt(sumsq) (one f32 ulp), a clipping coefficient
+    within 4u relative, a non-clipping one exactly 1.  norm_out = NULL is accepted."""
+    L = ops.lib()
+    inf, nan = float("inf"), float("nan")
+    rs = []
+    for max_norm in (1.0, 0.25):
+        for sumsq in (0.0, 1e-30, 0.5 * max_norm ** 2, max_norm ** 2, 1.0000002 * max_norm ** 2, 4.0, 3.7e9, 3.0e38, inf, nan):
+            for with_norm in (True, False):
+                scal = _blank((4,), torch.float32)
+                scal[0] = sumsq
+                ops.check(L.tav_clip_coef(ops.ptr(scal[0:1]), max_norm, ops.ptr(scal[1:2]), ops.ptr(scal[2:3]) if with_norm else None, ops.stream()), "clip_coef")
+                s32 = float(scal[0].item())
+                coef, norm = float(scal[1].item()), float(scal[2].item())
+                tag = f"clip_coef[max{max_norm:g},sumsq{sumsq:g},{'norm' if with_norm else 'norm NULL'}]"
+                if math.isnan(s32):
+                    ok_n, ok_c, e = math.isnan(norm), math.isnan(coef), 0.0
+                elif math.isinf(s32):
+                    ok_n, ok_c, e = norm == inf, coef == 0.0, 0.0
+                else:
+                    want_n = math.sqrt(s32)
+                    want_c = max_norm / (want_n + float(np.float32(1e-6)))
+                    ok_n = abs(norm - want_n) <= 2 * SR.U * want_n
+                    if want_c > 1.0 + 8 * SR.U:
+                        e, ok_c = abs(coef - 1.0), coef == 1.0
+                    elif want_c >= 1.0 - 8 * SR.U:                       # within rounding of the clamp: either side of it is right
+                        e = abs(coef - min(want_c, 1.0)) / (4 * SR.U)
+                        ok_c = e <= 1.0 and coef <= 1.0
+                    else:
+                        e = abs(coef - want_c) / want_c / (4 * SR.U)
+                        ok_c = e <= 1.0
+                if with_norm:
+                    rs.append((tag + ".norm", 0.0 if ok_n else 1.0, 0.0, bool(ok_n)))
+                    rs.append(_all_ff(tag + ".gap", scal[3:4]))
+                else:
+                    rs.append(_all_ff(tag + ".gap", scal[2:4]))
+                rs.append((tag + ".coef", e if ok_c else max(e, 2.0), 1.0, bool(ok_c)))
+    return rs
+
+
+# ------------------------------------------------------------------------------------------------ operand casts (exact: a cast has one right answer)
+def _sliced(shape, dtype, pad=8):
+    """(wide 0xFF buffer, its column slice [:, pad:pad + cols], the columns either side of the slice)."""
+    wide = _blank((shape[0], shape[1] + 2 * pad), dtype)
+    return wide, wide[:, pad:pad + shape[1]], (wide[:, :pad], wide[:, pad + shape[1]:])
+
+
+def check_cast_weight_edges():
+    """tav_cast_weight around its 32 x 32 tile: one row, one past / one short of a tile in either direction, whole tiles; bf16 and f32; dst only,
+    dst_t only, both; into dense outputs and into column slices of wider 0xFF buffers whose other columns stay 0xFF."""
+    rs = []
+    for R, Cc in ((1, 4), (31, 33), (32, 32), (33, 31), (64, 64), (65, 127)):
+        w = _rnd(R, Cc, seed=1500)
+        for dtype in (torch.bfloat16, torch.float32):
+            ref_n, ref_t = w.to(dtype), w.to(dtype).t().contiguous()
+            for want_n, want_t in ((True, False), (False, True), (True, True)):
+                for sliced in (False, True):
+                    tag = f"cast_weight[{R}x{Cc},{dtype},{'n' if want_n else ''}{'t' if want_t else ''},{'sliced' if sliced else 'dense'}]"
+                    if sliced:
+                        wn, on, gn = _sliced((R, Cc), dtype) if want_n else (None, None, ())
+                        wt, ot, gt = _sliced((Cc, R), dtype) if want_t else (None, None, ())
+                        n, t = ops.cast_weight(w, dtype, want_n=want_n, want_t=want_t, out_n=on, out_t=ot)
+                        rs.append(_all_ff(tag + ".gap", *gn, *gt))
+                    else:
+                        n, t = ops.cast_weight(w, dtype, want_n=want_n, want_t=want_t)
+                    assert (n is not None) == want_n and (t is not None) == want_t
+                    if want_n:
+                        rs.append(_exact(tag + ".n", n.contiguous(), ref_n))
+                    if want_t:
+                        rs.append(_exact(tag + ".t", t.contiguous(), ref_t))
+    return rs
+
+
+def check_cast_weights_multi():
+    """tav_cast_weights_multi, one launch over a mixed descriptor table (ops.make_cast_descs): the layer layout at H = 64, K = 128 (q / k / v into
+    row blocks of one [3H, K] and column blocks of one [K, 3H] buffer, q scaled by ATTN_Q_PRESCALE in dst and NOT in dst_t; the three [1, H] f32
+    bias rows into one [3H] vector), a 128 x 192 entry with both copies (the 64 x 64 fast path), the same shape with dst only and with an ld_t
+    that is no multiple of 4 (both must take the 32 x 32 path), a ragged 65 x 100 and an f32 -> f32 entry.  blocks_per_tensor 1 (one block
+    walks every tile: the LDS tile is reused between iterations), 3, the tile count and 5 more.  Then the same through
+    engine.WeightCache.layer: first build, refresh in place after a weight changed, and no launch at all when nothing did."""
+    import tav_amd.engine as engine
+    H, K = 64, 128
+    bf = torch.bfloat16
+    qs = ops.ATTN_Q_PRESCALE
+    wq, wk, wv = (_rnd(H, K, seed=1600 + j) for j in range(3))
+    bq, bk, bv = (_rnd(1, H, seed=1610 + j) for j in range(3))
+    big, rag, w32 = _rnd(128, 192, seed=1620), _rnd(65, 100, seed=1621), _rnd(40, 72, seed=1622)
+    n_qkv, t_qkv, bias = _blank((3 * H, K), bf), _blank((K, 3 * H), bf), _blank((3 * H,), torch.float32)
+    bufs = [n_qkv, t_qkv, bias]
+
+    def new(shape, dtype):
+        bufs.append(_blank(shape, dtype))
+        return bufs[-1]
+
+    ents, want = [], []                                               # want: (name, tensor the launch wrote, expected)
+    for j, (w, b) in enumerate(((wq, bq), (wk, bk), (wv, bv))):
+        sc = qs if j == 0 else None
+        f = qs if j == 0 else 1.0
+        ents.append((w, n_qkv[j * H:(j + 1) * H], t_qkv[:, j * H:(j + 1) * H], sc))
+        want.append((f"qkv{j}.n", ents[-1][1], (w * f).to(bf)))
+        want.append((f"qkv{j}.t", ents[-1][2], w.to(bf).t()))
+        ents.append((b, bias[j * H:(j + 1) * H].view(1, H), None, sc))
+        want.append((f"bias{j}", ents[-1][1], b * f))
+    ents.append((big, new((128, 192), bf), new((192, 128), bf)))                                   # fast path
+    want += [("fast.n", ents[-1][1], big.to(bf)), ("fast.t", ents[-1][2], big.to(bf).t())]
+    ents.append((big, new((128, 192), bf), None))                                                  # dst only: slow path
+    want.append(("dst_only.n", ents[-1][1], big.to(bf)))
+    wide_t = new((192, 128 + 6), bf)                                                               # ld_t = 134: slow path
+    ents.append((big, new((128, 192), bf), wide_t[:, :128]))
+    assert ents[-1][2].stride(0) % 4 != 0
+    want += [("odd_ld_t.n", ents[-1][1], big.to(bf)), ("odd_ld_t.t", ents[-1][2], big.to(bf).t())]
+    ents.append((rag, new((65, 100), bf), new((100, 65), bf)))
+    want += [("ragged.n", ents[-1][1], rag.to(bf)), ("ragged.t", ents[-1][2], rag.to(bf).t())]
+    ents.append((w32, new((40, 72), torch.float32), new((72, 40), torch.float32)))
+    want += [("f32.n", ents[-1][1], w32), ("f32.t", ents[-1][2], w32.t())]
+    descs, tiles = ops.make_cast_descs(ents, DEV)
+    descs = _in(descs)
+    assert tiles == 4 * 6
+    rs = []
+    for bpt in (1, 3, tiles, tiles + 5):
+        for b_ in bufs:
+            _refill(b_)
+        ops.cast_weights_multi(descs, len(ents), bpt)
+        for name, got, ref in want:
+            rs.append(_exact(f"cast_multi[bpt{bpt}].{name}", got.contiguous(), ref.contiguous()))
+        rs.append(_all_ff(f"cast_multi[bpt{bpt}].gap", wide_t[:, 128:]))
+    # ---- engine.WeightCache.layer at the same sizes (weights that change in place are plain tensors: guarded operands must stay what they were)
+    g = torch.Generator(device="cpu").manual_seed(1630)
+    wo, w1, w2 = (torch.randn(s, generator=g).to(DEV) for s in ((128, 64), (128, 192), (65, 100)))
+    cache = engine.WeightCache(engine.Policy("bf16"))
+    args = (wq, wk, wv, bq.view(H), bk.view(H), bv.view(H), wo, w1, w2)
+
+    def refs():
+        r_n = torch.cat([(wq * qs).to(bf), wk.to(bf), wv.to(bf)])
+        r_t = torch.cat([wq.to(bf).t(), wk.to(bf).t(), wv.to(bf).t()], 1)
+        r_b = torch.cat([bq.view(H) * qs, bk.view(H), bv.view(H)])
+        out = [r_n, r_t, r_b]
+        for w in (wo, w1, w2):
+            out += [w.to(bf), w.to(bf).t().contiguous()]
+        return out
+
+    names = ("Wqkv", "Wqkv_t", "bias_qkv", "Wo", "Wo_t", "W1", "W1_t", "W2", "W2_t")
+    val = cache.layer(*args, q_scale=qs)
+    assert len(val) == 9
+    for name, got, ref in zip(names, val, refs()):
+        rs.append(_exact(f"weight_cache.layer.{name}", got, ref))
+    ptrs = [t.data_ptr() for t in val]
+    w1.mul_(-1.5)
+    engine.bump_weight_epoch()
+    val2 = cache.layer(*args, q_scale=qs)
+    same = [t.data_ptr() for t in val2] == ptrs
+    rs.append(("weight_cache.layer refresh keeps its buffers", 0.0 if same else 1.0, 0.0, bool(same)))
+    for name, got, ref in zip(names, val2, refs()):
+        rs.append(_exact(f"weight_cache.layer.refreshed.{name}", got, ref))
+    val2[5].fill_(7.0)                                                # a sentinel in W1: a call with nothing changed must not launch the refresh
+    val3 = cache.layer(*args, q_scale=qs)
+    same = [t.data_ptr() for t in val3] == ptrs
+    rs.append(("weight_cache.layer unchanged call keeps its buffers", 0.0 if same else 1.0, 0.0, bool(same)))
+    expect = refs()
+    expect[5] = torch.full_like(expect[5], 7.0)
+    for name, got, ref in zip(names, val3, expect):
+        rs.append(_exact(f"weight_cache.layer.unchanged.{name}", got, ref))
+    return rs
+
+
+def check_cast_conv_weight():
+    """tav_cast_conv_weight: dst [co][k][ci], dst_t [k * ci][co] and every per-phase block, each built here element by element from the formula
+    in include/tavhip.h (ph_r[ci][q' co + c] = W[c][ci][r + (Q_r - 1 - q') s], Q_r = ceil((k - r) / s), blocks back to back); every output is
+    co ci k elements inside a longer 0xFF buffer whose tail stays 0xFF (so the phase buffer is fully written and nothing lands past it)."""
+    L = ops.lib()
+    rs = []
+    for co, ci, k, s in ((8, 4, 3, 2), (8, 4, 2, 2), (5, 3, 3, 1), (6, 2, 5, 3), (4, 4, 1, 1), (8, 4, 10, 5)):
+        g = torch.Generator(device="cpu").manual_seed(1700 + co * ci * k + s)
+        W = torch.randn(co, ci, k, generator=g)
+        n = co * ci * k
+        e_n, e_t, e_ph = [0.0] * n, [0.0] * n, []
+        for c in range(co):
+            for i in range(ci):
+                for j in range(k):
+                    e_n[(c * k + j) * ci + i] = W[c, i, j].item()
+                    e_t[(j * ci + i) * co + c] = W[c, i, j].item()
+        for r in range(s):
+            Q = (k - r + s - 1) // s
+            for i in range(ci):
+                for q_ in range(Q):
+                    for c in range(co):
+                        e_ph.append(W[c, i, r + (Q - 1 - q_) * s].item())
+        assert len(e_ph) == n
+        w_dev = _in(W.to(DEV))
+        for dtype in (torch.bfloat16, torch.float32):
+            outs = [_blank((n + 64,), dtype) for _ in range(3)]
+            ops.check(L.tav_cast_conv_weight(ops.ptr(w_dev), co, ci, k, ops.ptr(outs[0]), ops.ptr(outs[1]), ops.ptr(outs[2]), s, ops.dt(dtype), ops.stream()),
+                      "cast_conv_weight")
+            tag = f"cast_conv_weight[co{co},ci{ci},k{k},s{s},{dtype}]"
+            for name, got, e in zip(("dst", "dst_t", "dst_phase"), outs, (e_n, e_t, e_ph)):
+                rs.append(_exact(f"{tag}.{name}", got[:n], torch.tensor(e, dtype=torch.float32).to(DEV).to(dtype)))
+            rs.append(_all_ff(tag + ".tail", *[o[n:] for o in outs]))
+            only = _blank((n + 64,), dtype)                           # the phase operand alone (dst = dst_t = NULL)
+            ops.check(L.tav_cast_conv_weight(ops.ptr(w_dev), co, ci, k, None, None, ops.ptr(only), s, ops.dt(dtype), ops.stream()), "cast_conv_weight")
+            rs.append(_exact(tag + ".dst_phase alone", only[:n], outs[2][:n]))
+            rs.append(_all_ff(tag + ".dst_phase alone.tail", only[n:]))
+    return rs
+
+
+# ------------------------------------------------------------------------------------------------ fp8 states
+def _e4m3_bytes(x_f32):
+    return x_f32.to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def _fp8_state(a0):
+    """{448 / a0, a0 / 448, a0, 0} divided in f32, in a 0xFF buffer of 6 floats (the two after the state must stay 0xFF)."""
+    buf = _blank((6,), torch.float32)
+    a = torch.tensor(float(a0), dtype=torch.float32)
+    buf[:4] = torch.stack([torch.tensor(448.0) / a, a / torch.tensor(448.0), a, torch.tensor(0.0)]).to(DEV)
+    return buf
+
+
+def _quantize_delayed(x, state, want_q, want_t):
+    rows, cols = x.shape
+    rows_pad = (rows + ops.FP8_KPAD - 1) // ops.FP8_KPAD * ops.FP8_KPAD
+    q = _blank((rows, cols), torch.uint8) if want_q else None
+    qt = _blank((cols, rows_pad), torch.uint8) if want_t else None
+    ops.check(ops.lib().tav_fp8_quantize_delayed(ops.ptr(x), ops.dt(x), rows, cols, x.stride(0), ops.ptr(state), ops.ptr(q), cols, ops.ptr(qt), rows_pad, rows_pad,
+                                                 ops.stream()), "fp8_quantize_delayed")
+    return q, qt
+
+
+def _tie_values(dtype):
+    """(inputs, the e4m3 values round-to-nearest-even gives them), both f32: the midpoints 17 (16 | 18), 19 (18 | 20), 2^-10 (0 | 2^-9, the smallest
+    subnormal), 3 * 2^-10 (2^-9 | 2^-8), 432 (416 | 448), both signs, and for f32 inputs their neighbours one f32 ulp either side (those are no
+    bf16 values); padded with zeros to a multiple of 8 (32 values for f32, 16 for bf16)."""
+    xs, es = [], []
+    for mid, lo, hi, even in ((17.0, 16.0, 18.0, 16.0), (19.0, 18.0, 20.0, 20.0), (2.0 ** -10, 0.0, 2.0 ** -9, 0.0),
+                              (3 * 2.0 ** -10, 2.0 ** -9, 2.0 ** -8, 2.0 ** -8), (432.0, 416.0, 448.0, 448.0)):
+        m32 = np.float32(mid)
+        for sign in (1.0, -1.0):
+            if dtype == torch.float32:
+                xs += [sign * float(np.nextafter(m32, np.float32(0))), sign * mid, sign * float(np.nextafter(m32, np.float32(1e9)))]
+                es += [sign * lo, sign * even, sign * hi]
+            else:
+                xs.append(sign * mid)
+                es.append(sign * even)
+    pad = -len(xs) % 8
+    return torch.tensor(xs + [0.0] * pad, dtype=torch.float32), torch.tensor(es + [0.0] * pad, dtype=torch.float32)
+
+
+def check_fp8_delayed(dtype):
+    """tav_fp8_quantize_delayed on a hand-made state {448 / a0, a0 / 448, a0, 0} with a0 = 2 amax(x) and a0 = amax(x) / 2 (half the range
+    saturates): q == clamp(x state[0], +-448) in e4m3 as bytes, qt its transpose zero padded to rows_pad, state[0..2] untouched, state[3] ==
+    amax(x) bit for bit, unchanged by a second tensor of smaller magnitude, 0 for an all-zero tensor.  q only takes the streaming kernel
+    where cols % 8 == 0 and the tiled one otherwise, q + qt the tiled one; x dense and with a wider row pitch.  Then ties and e4m3 subnormals
+    at a scale of exactly 1."""
+    rs = []
+    for rows, cols in ((1, 4), (1, 8), (33, 136), (129, 1032), (1025, 132)):
+        for pitch in (0, 16):
+            gen = torch.Generator(device="cpu").manual_seed(1800 + rows + cols)
+            x = _in(torch.randn(rows, cols, generator=gen).to(DEV).to(dtype), pitch)
+            amax = x.float().abs().max()
+            for fac in (2.0, 0.5):
+                for want_t in (False, True):
+                    state = _fp8_state(float(amax.item()) * fac)
+                    s0 = state.clone()
+                    q, qt = _quantize_delayed(x, state, True, want_t)
+                    ref = _e4m3_bytes((x.float() * state[0]).clamp(-448.0, 448.0))
+                    tag = f"fp8.delayed[{dtype},{rows}x{cols},pitch+{pitch},a0={fac:g}amax,{'q+qt' if want_t else 'q'}]"
+                    rs.append(_exact(tag + ".q", q, ref))
+                    if fac < 1.0:                                   # (the largest element itself lands at twice the range)
+                        sat = int((ref & 0x7F).eq(0x7E).sum().item())   # 0x7e = 448: the clip really is exercised
+                        rs.append((tag + ".saturated elements present", float(sat), 0.0, sat > 0))
+                    if want_t:
+                        rs.append(_exact(tag + ".qt", qt[:, :rows].contiguous(), ref.t().contiguous()))
+                        pad = int(qt[:, rows:].ne(0).sum().item())
+                        rs.append((tag + ".qt_pad bytes zero", float(pad), 0.0, pad == 0))
+                    rs.append(_exact(tag + ".state[0:3] unchanged", _bits(state[:3]), _bits(s0[:3])))
+                    rs.append(_exact(tag + ".state[3] == amax", _bits(state[3:4]), _bits(amax.reshape(1))))
+                    rs.append(_all_ff(tag + ".gap", state[4:]))
+                    if want_t:
+                        continue
+                    small = _in((x.float() * 0.5).to(dtype), pitch)
+                    _quantize_delayed(small, state, True, False)
+                    rs.append(_exact(tag + ".state[3] kept by a smaller tensor", _bits(state[3:4]), _bits(amax.reshape(1))))
+        zero = _in(torch.zeros(rows, cols, dtype=dtype, device=DEV))
+        for want_t in (False, True):
+            state = _fp8_state(1.0)
+            q, qt = _quantize_delayed(zero, state, True, want_t)
+            tag = f"fp8.delayed[{dtype},{rows}x{cols},zeros,{'q+qt' if want_t else 'q'}]"
+            z = int(q.ne(0).sum().item()) + (int(qt.ne(0).sum().item()) if want_t else 0)
+            rs.append((tag + ".bytes zero", float(z), 0.0, z == 0))
+            rs.append(_exact(tag + ".state[3] stays 0", _bits(state[3:4]), _bits(torch.zeros(1, device=DEV))))
+    xs, es = _tie_values(dtype)
+    for shape, want_t in (((1, xs.numel()), False), ((xs.numel() // 4, 4), False), ((xs.numel() // 4, 4), True)):
+        x = _in(xs.view(shape).to(DEV).to(dtype))
+        assert torch.equal(x.float().cpu(), xs.view(shape))
+        state = _fp8_state(448.0)
+        assert float(state[0].item()) == 1.0
+        q, qt = _quantize_delayed(x, state, True, want_t)
+        tag = f"fp8.delayed.ties[{dtype},{shape[0]}x{shape[1]},{'q+qt' if want_t else 'q'}]"
+        rs.append(_exact(tag + ".q", q, _e4m3_bytes(es.view(shape).to(DEV))))
+        if want_t:
+            rs.append(_exact(tag + ".qt", qt[:, :shape[0]].contiguous(), _e4m3_bytes(es.view(shape).to(DEV)).t().contiguous()))
+    return rs
+
+
+def check_fp8_quantize_ties():
+    """The plain quantiser (tav_fp8_quantize) at a scale of exactly 1 on the same midpoints, neighbours and subnormals, streaming and tiled kernel;
+    ops.fp8_quantize of an all-zero tensor: scales (1, 1, 0), every byte zero."""
+    L = ops.lib()
+    rs = []
+    for dtype in (torch.float32, torch.bfloat16):
+        xd, ed = _tie_values(dtype)
+        for shape, want_t in (((1, xd.numel()), False), ((xd.numel() // 4, 4), False), ((xd.numel() // 4, 4), True)):
+            x = _in(xd.view(shape).to(DEV).to(dtype))
+            rows, cols = shape
+            rows_pad = ops.FP8_KPAD
+            scales = _in(torch.tensor([1.0, 1.0, 448.0], device=DEV))
+            q = _blank(shape, torch.uint8)
+            qt = _blank((cols, rows_pad), torch.uint8) if want_t else None
+            ops.check(L.tav_fp8_quantize(ops.ptr(x), ops.dt(x), rows, cols, x.stride(0), ops.ptr(scales), ops.ptr(q), cols, ops.ptr(qt), rows_pad, rows_pad,
+                                         ops.stream()), "fp8_quantize")
+            tag = f"fp8.ties[{dtype},{rows}x{cols},{'q+qt' if want_t else 'q'}]"
+            ref = _e4m3_bytes(ed.view(shape).to(DEV))
+            rs.append(_exact(tag + ".q", q, ref))
+            rs.append(_exact(tag + ".torch's own conversion agrees", _e4m3_bytes(x.float()), ref))
+            if want_t:
+                rs.append(_exact(tag + ".qt", qt[:, :rows].contiguous(), ref.t().contiguous()))
+        f = ops.fp8_quantize(_in(torch.zeros(33, 132, dtype=dtype, device=DEV)), want_t=True)
+        tag = f"fp8.zeros[{dtype}]"
+        rs.append(_exact(tag + ".scales (1, 1, 0)", f.scales[:3], torch.tensor([1.0, 1.0, 0.0], device=DEV)))
+        z = int(f.q.view(torch.uint8).ne(0).sum().item()) + int(f.qt.view(torch.uint8).ne(0).sum().item())
+        rs.append((tag + ".bytes zero", float(z), 0.0, z == 0))
+    return rs
+
+
+def check_fp8_roll_states():
+    """tav_fp8_roll_states over n in {1, 255, 257} states: a state whose running maximum m = state[3] moved (0 < m < 3e38) becomes
+    {448 / m, m / 448, m, 0}, divided in f32; one at 0, +inf or NaN keeps its first three words; every state[3] is 0 afterwards; the 0xFF
+    bytes after the last state are untouched."""
+    L = ops.lib()
+    inf, nan = float("inf"), float("nan")
+    rs = []
+    for n, kinds in ((1, "m"), (1, "0"), (1, "i"), (1, "n"), (255, None), (257, None)):
+        g = torch.Generator(device="cpu").manual_seed(1900 + n)
+        st = torch.rand(n, 4, generator=g) * 10 + 0.01
+        m = 10.0 ** (torch.rand(n, generator=g) * 12 - 6)
+        kind = list(kinds) if kinds else ["0" if i % 3 == 0 else "m" for i in range(n)]
+        if kinds is None:
+            kind[7], kind[n - 1], kind[n - 2] = "i", "n", "m"
+        for i, k_ in enumerate(kind):
+            st[i, 3] = {"m": float(m[i]), "0": 0.0, "i": inf, "n": nan}[k_]
+        buf = _blank((n + 2, 4), torch.float32)
+        buf[:n] = st.to(DEV)
+        ops.check(L.tav_fp8_roll_states(ops.ptr(buf), n, ops.stream()), "fp8_roll_states")
+        want = st.clone()
+        moved = torch.tensor([k_ == "m" for k_ in kind])
+        mm = st[:, 3]
+        want[moved, 0] = torch.tensor(448.0) / mm[moved]
+        want[moved, 1] = mm[moved] / torch.tensor(448.0)
+        want[moved, 2] = mm[moved]
+        want[:, 3] = 0.0
+        tag = f"fp8.roll_states[n{n}{',' + kinds if kinds else ''}]"
+        rs.append(_exact(tag, _bits(buf[:n]), _bits(want.to(DEV))))
+        rs.append(_all_ff(tag + ".tail", buf[n:]))
+    return rs
+
+
+def step_end_checks():
+    """The step-end cases, in the order all_checks() appends them."""
+    out = []
+    for list_name in SR.SIZE_LISTS:
+        for layout in _LAYOUTS:
+            for wd in (SR.WD, 0.0):
+                out.append(lambda a=(list_name, layout, wd): check_optimizer_step(*a))
+    out += [check_grad_norm, check_clip_coef, check_cast_weight_edges, check_cast_weights_multi, check_cast_conv_weight,
+            lambda: check_fp8_delayed(torch.float32), lambda: check_fp8_delayed(torch.bfloat16), check_fp8_roll_states]
+    return out
+
+
 def all_checks():
     out = []
     for dtype in (torch.float32, torch.bfloat16):
@@ -1290,4 +1881,6 @@ def all_checks():
     # the smallest launch of the audio front-end: one batch entry, one output step (hand-written fp64 group norm: torch's refuses it)
     for dtype in (torch.float32, torch.bfloat16):
         out.append(lambda d=dtype: check_conv0_gn(d, B=1, T_in=10, ref64=True))
+    # step-end kernels: gradient norm, clip coefficient, AdamW, operand casts, fp8 states
+    out += step_end_checks()
     return out
