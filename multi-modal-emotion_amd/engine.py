@@ -292,6 +292,19 @@ def _arena_into(wq, wk, wv, bq, bk, bv, wo, bo, w1, b1, w2, b2):
     return [(g(w2), g(b2)), (g(w1), g(b1)), (g(wo), g(bo)), (fused((wq, wk, wv)), fused((bq, bk, bv)))]
 
 
+def _fp8_layer(pol, spec):
+    """Whether this layer's four linears are on the e4m3 policy: data of the policy and the layer's stack, not a class of its own."""
+    return bool(pol.fp8 and spec.branch in pol.fp8_stacks)
+
+
+def _fp8_sites(ectx, spec, wq):
+    """-> (fp8, fm, bm, w8, st) of one layer: Policy.fp8_fwd / fp8_bwd / fp8_wgrad8 for an fp8 layer, (0, 0, False) for a plain one;
+    st(tag) names the delayed-scaling state of one quantisation site of this layer (ops.fp8_quantize)."""
+    pol, fp8 = ectx.pol, _fp8_layer(ectx.pol, spec)
+    st = lambda tag: ectx.cache.fp8_state(wq, tag)           # noqa: E731
+    return (True, pol.fp8_fwd, pol.fp8_bwd, pol.fp8_wgrad8, st) if fp8 else (False, 0, 0, False, st)
+
+
 class EncoderLayerFn(torch.autograd.Function):
     """One transformer layer.  params = (ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2).
 
@@ -300,7 +313,13 @@ class EncoderLayerFn(torch.autograd.Function):
     post_ln (BERT / RoBERTa / wav2vec2-base; HF roberta:211-398, wav2vec2:575-608):
         x1 = LN1(x + Wo.attn(x));  x2 = LN2(x1 + W2.gelu(W1.x1))
     Returns (x2 f32, x2_lp): the low-precision copy is a by-product for the next layer's GEMMs (not differentiable).
-    """
+
+    An fp8 layer (_fp8_layer: Policy("fp8*"), BASELINE config 5) is this same layer with e4m3 operands in the linears its masks select: bit 0
+    qkv, 1 out-proj, 2 FFN1, 3 FFN2, forward (fm) and dgrad (bm).  Each selected GEMM input (LayerNorm output, attention output, GELU output,
+    and in the backward the incoming gradient) is quantised once per use with its own per-tensor scale (ops.fp8_quantize); forward and
+    dgrad read the row-major copies.  Attention, LayerNorm, residual adds and all statistics are those of the bf16 policy.  The weight
+    gradients are the bf16 ones, unless w8: then they are NT GEMMs of the transposed e4m3 copies (ops.wgrad_fp8), and what is saved for the
+    backward are those transposed activations (and their scales) instead of the bf16 a / c / h."""
 
     @staticmethod
     def forward(ctx, x, x_lp, key_mask, ectx, spec, *params):
@@ -308,17 +327,29 @@ class EncoderLayerFn(torch.autograd.Function):
         (ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2) = params
         B, S, nh = spec.B, spec.S, spec.nheads
         H = nh * 64
-        from . import runtime as _rt
-        _rt.note_layer_group(wq, wk, wv, bq, bk, bv, wo, bo, w1, b1, w2, b2)          # (data-parallel gradient arena: which gradients one grouped launch produces)
+        fp8, fm, _, w8, st = _fp8_sites(ectx, spec, wq)
+        if not fp8:                                   # (data-parallel gradient arena: which gradients one grouped launch produces; plain layers only so far)
+            from . import runtime as _rt
+            _rt.note_layer_group(wq, wk, wv, bq, bk, bv, wo, bo, w1, b1, w2, b2)
         # the q third of qkv comes out of the projection already multiplied by scale * log2(e) (folded into the weight copy)
         wqkv, _, bqkv, wo_n, _, w1_n, _, w2_n, _ = cache.layer(wq, wk, wv, bq, bk, bv, wo, w1, w2, q_scale=QSC)
+        wqkv8, _, wo8, w18, w28 = cache.layer_fp8(wq, wk, wv, bq, bk, bv, wo, w1, w2, q_scale=QSC) if fp8 else (None,) * 5
+
+        def lin(bit, inp, w_n, w_8, tag, **kw):       # one forward linear -> (output, the Fp8 copy of its input or None)
+            if not fm & bit:
+                return ops.gemm_nt(inp, w_n, **kw), None
+            if _MX_EMULATE and bit != 1:
+                return ops.gemm_nt(_mx_roundtrip(inp), _mx_roundtrip(w_n), **kw), None
+            inp8 = ops.fp8_quantize(inp, want_t=w8, state=st(tag))
+            return ops.gemm_nt_fp8(inp8, w_8, **kw), inp8
+
         x = _c(x)
         if spec.pre_ln:
             _, a, mean1, rstd1 = _ln_fwd(pol, x, ln1_w, ln1_b, spec.eps, need_f32=False)
         else:
             a = x_lp if x_lp is not None else _to_lp(pol, x)
             mean1 = rstd1 = None
-        qkv = ops.gemm_nt(a, wqkv, bias=bqkv)
+        qkv, a8 = lin(1, a, wqkv, wqkv8, "a", bias=bqkv)
         o, lse, aux = ops.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=QSC is not None,
                                    seq_lens=spec.seq_lens)
         hs, o_ctx = spec.head_scale, o
@@ -332,26 +363,29 @@ class EncoderLayerFn(torch.autograd.Function):
         if spec.probs_out is not None:
             spec.probs_out.append(ops.attn_probs(qkv[:, :H], qkv[:, H:2 * H], lse, B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode,
                                                  q_prescaled=QSC is not None, head_scale=hs))
-        y1 = ops.gemm_nt(o_ctx, wo_n, bias=bo, resid=x, out_dtype=torch.float32)
+        y1, o8 = lin(2, o_ctx, wo_n, wo8, "o", bias=bo, resid=x, out_dtype=torch.float32)
         if spec.pre_ln:
             x1 = y1
             _, c, mean2, rstd2 = _ln_fwd(pol, x1, ln2_w, ln2_b, spec.eps, need_f32=False)
         else:
             x1, c, mean1, rstd1 = _ln_fwd(pol, y1, ln1_w, ln1_b, spec.eps, need_f32=True)
-        h, u = ops.gemm_nt(c, w1_n, bias=b1, act=3, want_pre=True)          # u = gelu'(W1 c + b1): what the backward multiplies by
-        y2 = ops.gemm_nt(h, w2_n, bias=b2, resid=x1, out_dtype=torch.float32)
+        (h, u), c8 = lin(4, c, w1_n, w18, "c", bias=b1, act=3, want_pre=True)          # u = gelu'(W1 c + b1): what the backward multiplies by
+        y2, h8 = lin(8, h, w2_n, w28, "h", bias=b2, resid=x1, out_dtype=torch.float32)
         if spec.pre_ln:
             x2, x2_lp = y2, None
-            mean_o = rstd_o = None
         else:
-            x2, x2_lp, mean_o, rstd_o = _ln_fwd(pol, y2, ln2_w, ln2_b, spec.eps, need_f32=True)
-            mean2, rstd2 = mean_o, rstd_o
+            x2, x2_lp, mean2, rstd2 = _ln_fwd(pol, y2, ln2_w, ln2_b, spec.eps, need_f32=True)
         ctx.ectx, ctx.spec = ectx, spec
         ctx.set_materialize_grads(False)          # no zero-filled gradient tensor for the non-differentiable lp by-product
         ctx.has = [p is not None for p in params]
         corr, o_soft = aux
+        if w8:                                    # the weight gradients read the transposed e4m3 copies: the bf16 a / c / h are not held
+            a = c = h = None
+            keep8 = tuple(t for x8 in (a8, o8, c8, h8) for t in (x8.qt, x8.scales))
+        else:
+            keep8 = (None,) * 8
         ctx.save_for_backward(x if spec.pre_ln else None, a, qkv, o, lse, corr, o_soft, y1, c, u, h, y2 if not spec.pre_ln else None,
-                              mean1, rstd1, mean2, rstd2, key_mask, o_ctx if hs is not None else None, hs, *params)
+                              mean1, rstd1, mean2, rstd2, key_mask, o_ctx if hs is not None else None, hs, *keep8, *params)
         if x2_lp is None or pol.f32:
             x2_lp = x2.new_empty(0)
         ctx.mark_non_differentiable(x2_lp)
@@ -362,10 +396,26 @@ class EncoderLayerFn(torch.autograd.Function):
         pol, cache, spec = ctx.ectx.pol, ctx.ectx.cache, ctx.spec
         sv = ctx.saved_tensors
         x, a, qkv, o, lse, corr, o_soft, y1, c, u, h, y2, mean1, rstd1, mean2, rstd2, key_mask, o_ctx, hs = sv[:19]
-        (ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2) = sv[19:]
+        (ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2) = sv[27:]
         B, S, nh = spec.B, spec.S, spec.nheads
-        H = nh * 64
+        H, M = nh * 64, qkv.shape[0]
+        fp8, _, bm, w8, st = _fp8_sites(ctx.ectx, spec, wq)
         _, wqkv_t, _, _, wo_t, _, w1_t, _, w2_t = cache.layer(wq, wk, wv, bq, bk, bv, wo, w1, w2, q_scale=QSC)
+        _, wqkv8, wo8, w18, w28 = cache.layer_fp8(wq, wk, wv, bq, bk, bv, wo, w1, w2, q_scale=QSC) if fp8 else (None,) * 5
+        if w8:
+            a8, o8, c8, h8 = (ops.Fp8(None, t, s, M, t.shape[0]) for t, s in zip(sv[19:27:2], sv[20:27:2]))
+        # dgrad outputs that ONLY feed a LayerNorm backward (pre-LN layers) leave the GEMM in the operand dtype: LN backward takes the
+        # rounded values straight into its f32 row arithmetic and adds the f32 residual gradient there, so the residual stream itself
+        # stays f32 -- and the GEMM epilogue writes, and LN backward reads, half the bytes (TAV_BWD_LP_OUT=0: f32 as in round 2).
+        # An fp8 layer keeps them f32.
+        dgrad_out = torch.float32 if fp8 else _DGRAD_OUT(pol)
+
+        def dgrad(dy_lp, bit, w_8, w_t, **kw):   # dY [M, N] x W [N, K] -> [M, K]: the NT GEMM against the transposed copy W^T [K, N(_pad)]
+            if bm & bit:
+                dy8 = ops.fp8_quantize(dy_lp, want_t=w8, state=st(f"dY{bit}"))
+                return ops.gemm_nt(dy8.q, w_8.qt[:, :w_8.rows], a_dequant=dy8.dequant, b_dequant=w_8.dequant, **kw), dy8
+            return ops.gemm_nt(dy_lp, w_t, **kw), None
+
         g2 = _c(g2)
         if spec.pre_ln:
             hint = None if pol.f32 else _hint_take(g2)
@@ -374,19 +424,16 @@ class EncoderLayerFn(torch.autograd.Function):
         else:
             dy2, dy2_lp, dg2, db2 = _ln_bwd(pol, g2, y2, ln2_w, ln2_b, mean2, rstd2)
         # FFN
-        du = ops.gemm_nt(dy2_lp, w2_t, gelu_in=u, act=4)
+        du, dy28 = dgrad(dy2_lp, 8, w28, w2_t, gelu_in=u, act=4)
         if spec.pre_ln:
-            # dgrad outputs that ONLY feed a LayerNorm backward (pre-LN layers) leave the GEMM in the operand dtype: LN backward takes the
-            # rounded values straight into its f32 row arithmetic and adds the f32 residual gradient there, so the residual stream itself
-            # stays f32 -- and the GEMM epilogue writes, and LN backward reads, half the bytes (TAV_BWD_LP_OUT=0: f32 as in round 2)
-            dc = ops.gemm_nt(du, w1_t, out_dtype=_DGRAD_OUT(pol))
+            dc, du8 = dgrad(du, 4, w18, w1_t, out_dtype=dgrad_out)
             g1, g1_lp, dg2, db2 = _ln_bwd(pol, dc, y1, ln2_w, ln2_b, mean2, rstd2, dx_add=dy2)
             dy1, dy1_lp = g1, g1_lp
         else:
-            g1 = ops.gemm_nt(du, w1_t, resid=dy2, out_dtype=torch.float32)
+            g1, du8 = dgrad(du, 4, w18, w1_t, resid=dy2, out_dtype=torch.float32)
             dy1, dy1_lp, dg1, db1 = _ln_bwd(pol, g1, y1, ln1_w, ln1_b, mean1, rstd1)
         # attention
-        do = ops.gemm_nt(dy1_lp, wo_t)
+        do, dy18 = dgrad(dy1_lp, 2, wo8, wo_t)
         qs, ks, vs, pre = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], QSC is not None
         if hs is None:
             dqkv = ops.attn_bwd(qs, ks, vs, o, do, lse, (corr, o_soft) if spec.mask_mode == 2 else None,
@@ -401,15 +448,19 @@ class EncoderLayerFn(torch.autograd.Function):
         if hs is not None:
             o = o_ctx                                           # what the out-projection multiplied (its weight gradient below)
         if spec.pre_ln:
-            da = ops.gemm_nt(dqkv, wqkv_t, out_dtype=_DGRAD_OUT(pol))
+            da, dqkv8 = dgrad(dqkv, 1, wqkv8, wqkv_t, out_dtype=dgrad_out)
             g0, g0_lp, dg1, db1 = _ln_bwd(pol, da, x, ln1_w, ln1_b, mean1, rstd1, dx_add=dy1, need_lp=_LP_HINT_ON and not pol.f32)
             if not pol.f32:
                 _hint_set(g0, g0_lp)
         else:
-            g0 = ops.gemm_nt(dqkv, wqkv_t, resid=dy1, out_dtype=torch.float32)
-        # the four weight (+bias) gradients of the layer: leaves nobody reads before the optimizer, issued last as ONE grouped launch
-        (dW2, dB2), (dW1, dB1), (dWo, dBo), (dWqkv, dBqkv) = _layer_wgrads([(dy2_lp, h), (du, c), (dy1_lp, o), (dqkv, a)],
-                                                                           _arena_into(wq, wk, wv, bq, bk, bv, wo, bo, w1, b1, w2, b2))
+            g0, dqkv8 = dgrad(dqkv, 1, wqkv8, wqkv_t, resid=dy1, out_dtype=torch.float32)
+        # the four weight (+bias) gradients of the layer: leaves nobody reads before the optimizer, issued last
+        if w8:
+            dW2, dW1, dWo, dWqkv = ops.wgrad_fp8(dy28, h8), ops.wgrad_fp8(du8, c8), ops.wgrad_fp8(dy18, o8), ops.wgrad_fp8(dqkv8, a8)
+            dB2, dB1, dBo, dBqkv = ops.colsum(dy2_lp), ops.colsum(du), ops.colsum(dy1_lp), ops.colsum(dqkv)
+        else:                                    # ONE grouped launch, bias sums fused; the gradient arena serves plain layers only so far
+            into = None if fp8 else _arena_into(wq, wk, wv, bq, bk, bv, wo, bo, w1, b1, w2, b2)
+            (dW2, dB2), (dW1, dB1), (dWo, dBo), (dWqkv, dBqkv) = _layer_wgrads([(dy2_lp, h), (du, c), (dy1_lp, o), (dqkv, a)], into)
         grads = [dg1, db1, dWqkv[:H], dBqkv[:H], dWqkv[H:2 * H], dBqkv[H:2 * H], dWqkv[2 * H:], dBqkv[2 * H:], dWo, dBo, dg2, db2, dW1, dB1, dW2, dB2]
         grads = [g if has else None for g, has in zip(grads, ctx.has)]
         return (g0, None, None, None, None, *grads)
@@ -429,139 +480,6 @@ def _mx_roundtrip(x, block=32):
     return ((xb * sc).to(torch.float8_e4m3fn).float() / sc).reshape(M, K).to(x.dtype)
 
 
-class EncoderLayerFp8Fn(torch.autograd.Function):
-    """EncoderLayerFn with the four linear layers on e4m3 operands (Policy("fp8"), BASELINE config 5).  Each GEMM input (LayerNorm output,
-    attention output, GELU output, and in the backward the four incoming gradients) is quantised once per use with its own per-tensor
-    scale (ops.fp8_quantize: amax -> scale on the device -> e4m3 copy + transposed copy); forward and dgrad read the row-major copies, the
-    weight gradients are NT GEMMs of the transposed copies (ops.wgrad_fp8).  Attention, LayerNorm, residual adds and all statistics are
-    exactly those of the bf16 policy.  What is saved for the backward are the fp8 transposed activations, not their bf16 originals."""
-
-    @staticmethod
-    def forward(ctx, x, x_lp, key_mask, ectx, spec, *params):
-        pol, cache = ectx.pol, ectx.cache
-        (ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2) = params
-        B, S, nh = spec.B, spec.S, spec.nheads
-        H = nh * 64
-        wqkv, _, bqkv, wo_n, _, w1_n, _, w2_n, _ = cache.layer(wq, wk, wv, bq, bk, bv, wo, w1, w2, q_scale=QSC)
-        wqkv8, _, wo8, w18, w28 = cache.layer_fp8(wq, wk, wv, bq, bk, bv, wo, w1, w2, q_scale=QSC)
-        fm = pol.fp8_fwd
-        a8 = o8 = c8 = h8 = None
-        st = lambda tag: cache.fp8_state(wq, tag)           # noqa: E731  (one delayed-scaling state per quantisation site of this layer)
-        x = _c(x)
-        if spec.pre_ln:
-            _, a, mean1, rstd1 = _ln_fwd(pol, x, ln1_w, ln1_b, spec.eps, need_f32=False)
-        else:
-            a = x_lp if x_lp is not None else _to_lp(pol, x)
-            mean1 = rstd1 = None
-        if fm & 1:
-            a8 = ops.fp8_quantize(a, want_t=pol.fp8_wgrad8, state=st("a"))
-            qkv = ops.gemm_nt_fp8(a8, wqkv8, bias=bqkv)
-        else:
-            qkv = ops.gemm_nt(a, wqkv, bias=bqkv)
-        o, lse, aux = ops.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=QSC is not None)
-        if (fm & 2) and _MX_EMULATE:
-            y1 = ops.gemm_nt(_mx_roundtrip(o), _mx_roundtrip(wo_n), bias=bo, resid=x, out_dtype=torch.float32)
-        elif fm & 2:
-            o8 = ops.fp8_quantize(o, want_t=pol.fp8_wgrad8, state=st("o"))
-            y1 = ops.gemm_nt_fp8(o8, wo8, bias=bo, resid=x, out_dtype=torch.float32)
-        else:
-            y1 = ops.gemm_nt(o, wo_n, bias=bo, resid=x, out_dtype=torch.float32)
-        if spec.pre_ln:
-            x1 = y1
-            _, c, mean2, rstd2 = _ln_fwd(pol, x1, ln2_w, ln2_b, spec.eps, need_f32=False)
-        else:
-            x1, c, mean1, rstd1 = _ln_fwd(pol, y1, ln1_w, ln1_b, spec.eps, need_f32=True)
-        if (fm & 4) and _MX_EMULATE:
-            h, u = ops.gemm_nt(_mx_roundtrip(c), _mx_roundtrip(w1_n), bias=b1, act=3, want_pre=True)
-        elif fm & 4:
-            c8 = ops.fp8_quantize(c, want_t=pol.fp8_wgrad8, state=st("c"))
-            h, u = ops.gemm_nt_fp8(c8, w18, bias=b1, act=3, want_pre=True)
-        else:
-            h, u = ops.gemm_nt(c, w1_n, bias=b1, act=3, want_pre=True)
-        if (fm & 8) and _MX_EMULATE:
-            y2 = ops.gemm_nt(_mx_roundtrip(h), _mx_roundtrip(w2_n), bias=b2, resid=x1, out_dtype=torch.float32)
-        elif fm & 8:
-            h8 = ops.fp8_quantize(h, want_t=pol.fp8_wgrad8, state=st("h"))
-            y2 = ops.gemm_nt_fp8(h8, w28, bias=b2, resid=x1, out_dtype=torch.float32)
-        else:
-            y2 = ops.gemm_nt(h, w2_n, bias=b2, resid=x1, out_dtype=torch.float32)
-        if spec.pre_ln:
-            x2, x2_lp = y2, None
-        else:
-            x2, x2_lp, mean2, rstd2 = _ln_fwd(pol, y2, ln2_w, ln2_b, spec.eps, need_f32=True)
-        ctx.ectx, ctx.spec = ectx, spec
-        ctx.set_materialize_grads(False)
-        ctx.has = [p is not None for p in params]
-        ctx.rows = a.shape[0]
-        corr, o_soft = aux
-        if pol.fp8_wgrad8:
-            keep = (a8.qt, a8.scales, o8.qt, o8.scales, c8.qt, c8.scales, h8.qt, h8.scales)
-        else:                                    # the bf16 operands of the weight-gradient GEMMs (o is saved for attention anyway)
-            keep = (a, None, None, None, c, None, h, None)
-        ctx.save_for_backward(x if spec.pre_ln else None, qkv, o, lse, corr, o_soft, y1, u, y2 if not spec.pre_ln else None, mean1, rstd1, mean2, rstd2, key_mask,
-                              *keep, *params)
-        if x2_lp is None:
-            x2_lp = x2.new_empty(0)
-        ctx.mark_non_differentiable(x2_lp)
-        return x2, x2_lp
-
-    @staticmethod
-    def backward(ctx, g2, _g_lp):
-        pol, cache, spec = ctx.ectx.pol, ctx.ectx.cache, ctx.spec
-        sv = ctx.saved_tensors
-        x, qkv, o, lse, corr, o_soft, y1, u, y2, mean1, rstd1, mean2, rstd2, key_mask = sv[:14]
-        a_t, a_s, o_t, o_s, c_t, c_s, h_t, h_s = sv[14:22]
-        (ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2) = sv[22:]
-        B, S, nh = spec.B, spec.S, spec.nheads
-        H, F, M = nh * 64, w1.shape[0], ctx.rows
-        _, wqkv8, wo8, w18, w28 = cache.layer_fp8(wq, wk, wv, bq, bk, bv, wo, w1, w2, q_scale=QSC)
-        _, wqkv_t, _, _, wo_t, _, w1_t, _, w2_t = cache.layer(wq, wk, wv, bq, bk, bv, wo, w1, w2, q_scale=QSC)
-        w8 = pol.fp8_wgrad8
-        bm = pol.fp8_bwd
-        pre = QSC is not None
-        if w8:
-            a8, o8, c8, h8 = (ops.Fp8(None, t, s, M, t.shape[0]) for t, s in ((a_t, a_s), (o_t, o_s), (c_t, c_s), (h_t, h_s)))
-
-        def dgrad(dy_lp, bit, wq8, w_t, **kw):   # dY [M, N] x W [N, K] -> [M, K]: the NT GEMM against the transposed copy W^T [K, N(_pad)]
-            if bm & bit:
-                dy8 = ops.fp8_quantize(dy_lp, want_t=w8, state=cache.fp8_state(wq, f"dY{bit}"))
-                return ops.gemm_nt(dy8.q, wq8.qt[:, :wq8.rows], a_dequant=dy8.dequant, b_dequant=wq8.dequant, **kw), dy8
-            return ops.gemm_nt(dy_lp, w_t, **kw), None
-
-        g2 = _c(g2)
-        if spec.pre_ln:
-            hint = _hint_take(g2)
-            dy2, dy2_lp = g2, (hint if hint is not None else _to_lp(pol, g2))
-            dg2 = db2 = None
-        else:
-            dy2, dy2_lp, dg2, db2 = _ln_bwd(pol, g2, y2, ln2_w, ln2_b, mean2, rstd2)
-        du, dy28 = dgrad(dy2_lp, 8, w28, w2_t, gelu_in=u, act=4)
-        if spec.pre_ln:
-            dc, du8 = dgrad(du, 4, w18, w1_t, out_dtype=torch.float32)
-            g1, g1_lp, dg2, db2 = _ln_bwd(pol, dc, y1, ln2_w, ln2_b, mean2, rstd2, dx_add=dy2)
-            dy1, dy1_lp = g1, g1_lp
-        else:
-            g1, du8 = dgrad(du, 4, w18, w1_t, resid=dy2, out_dtype=torch.float32)
-            dy1, dy1_lp, dg1, db1 = _ln_bwd(pol, g1, y1, ln1_w, ln1_b, mean1, rstd1)
-        do, dy18 = dgrad(dy1_lp, 2, wo8, wo_t)
-        dqkv = ops.attn_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], o, do, lse, (corr, o_soft) if spec.mask_mode == 2 else None,
-                            B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=pre)
-        if spec.pre_ln:
-            da, dqkv8 = dgrad(dqkv, 1, wqkv8, wqkv_t, out_dtype=torch.float32)
-            g0, g0_lp, dg1, db1 = _ln_bwd(pol, da, x, ln1_w, ln1_b, mean1, rstd1, dx_add=dy1, need_lp=_LP_HINT_ON)
-            _hint_set(g0, g0_lp)
-        else:
-            g0, dqkv8 = dgrad(dqkv, 1, wqkv8, wqkv_t, resid=dy1, out_dtype=torch.float32)
-        if w8:
-            dW2, dW1, dWo, dWqkv = ops.wgrad_fp8(dy28, h8), ops.wgrad_fp8(du8, c8), ops.wgrad_fp8(dy18, o8), ops.wgrad_fp8(dqkv8, a8)
-            dB2, dB1, dBo, dBqkv = ops.colsum(dy2_lp), ops.colsum(du), ops.colsum(dy1_lp), ops.colsum(dqkv)
-        else:                                    # one grouped bf16 launch, bias sums fused (a_t / c_t / h_t hold the bf16 activations here)
-            (dWqkv, dBqkv), (dWo, dBo), (dW1, dB1), (dW2, dB2) = ops.gemm_tn_grouped([(dqkv, a_t), (dy1_lp, o), (du, c_t), (dy2_lp, h_t)], want_bias=True)
-        grads = [dg1, db1, dWqkv[:H], dBqkv[:H], dWqkv[H:2 * H], dBqkv[H:2 * H], dWqkv[2 * H:], dBqkv[2 * H:], dWo, dBo, dg2, db2, dW1, dB1, dW2, dB2]
-        grads = [g if has else None for g, has in zip(grads, ctx.has)]
-        return (g0, None, None, None, None, *grads)
-
-
 _F32_BRANCHES = tuple(b for b in os.environ.get("TAV_F32_BRANCHES", "").split(",") if b)      # error attribution only (tools/gpu_bf16_attrib.py)
 _f32_ctx = []
 
@@ -573,15 +491,14 @@ def encoder_layer(ectx, spec, x, x_lp, key_mask, params):
             _f32_ctx.append(Ctx("fp32"))
         x2, _ = EncoderLayerFn.apply(x, None, key_mask, _f32_ctx[0], spec, *params)
         return x2, None
-    fn = EncoderLayerFp8Fn if (ectx.pol.fp8 and spec.branch in ectx.pol.fp8_stacks) else EncoderLayerFn
-    if fn is EncoderLayerFp8Fn and (spec.head_scale is not None or spec.probs_out is not None):
+    fp8, slow = _fp8_layer(ectx.pol, spec), spec.head_scale is not None or spec.probs_out is not None
+    if fp8 and slow:
         raise NotImplementedError("head_mask / output_attentions are built for the bf16 and fp32 policies only")
-    if spec.seq_lens is not None:
-        if fn is EncoderLayerFp8Fn:
-            raise ValueError("per-row sequence lengths (seq_lens) are built for the bf16 and fp32 policies only, not fp8")
-        if spec.head_scale is not None or spec.probs_out is not None:
-            raise NotImplementedError("head_mask / output_attentions are not built for per-row sequence lengths (seq_lens)")
-    x2, x2_lp = fn.apply(x, x_lp, key_mask, ectx, spec, *params)
+    if fp8 and spec.seq_lens is not None:
+        raise ValueError("per-row sequence lengths (seq_lens) are built for the bf16 and fp32 policies only, not fp8")
+    if slow and spec.seq_lens is not None:
+        raise NotImplementedError("head_mask / output_attentions are not built for per-row sequence lengths (seq_lens)")
+    x2, x2_lp = EncoderLayerFn.apply(x, x_lp, key_mask, ectx, spec, *params)
     return x2, (x2_lp if x2_lp.numel() else None)
 
 
