@@ -350,6 +350,36 @@ int tav_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t n, float p,
 int tav_dropout_fwd_dev(const float* x, float* y, uint8_t* mask, int64_t n, float p, const uint64_t* seed_state, uint64_t offset, void* stream);
 int tav_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, int64_t n, float p, void* stream);
 
+/* SpecAugment (models/tav.py:269-306).  The three calls take masks from anywhere; tav_specaug_draw makes them from the dropout seed words.
+ *
+ * tav_specaug_draw: mask[B][L] (uint8, every byte written) = the union of n spans of `length` positions per row, one workgroup per row:
+ *   len  = non-zero bytes of valid[row][0..L)                           (valid NULL: len = L)
+ *   eps  = (mix64(seed ^ mix64(tag + 2^40)) >> 40) * 2^-24              one value per call, shared by all rows
+ *   n0   = floor(prob * len / length + eps)                             f32, each operation rounded to nearest, in this order
+ *   n    = min(max(n0, min_masks), max(len - (length - 1), 0), L / length)
+ *   the starts are the n positions s in [0, len - length] with the smallest key mix64(seed ^ mix64(tag + row * L + s)), ties to the
+ *   smaller s (a uniform draw without replacement); mix64 is the dropout kernels' mixer.  nspans (optional, int32 [B]) receives n.
+ * A tag owns the indices [tag, tag + 2^40] of its seed's stream: B * L <= 2^40, and the two tags below stay clear of each other and of the
+ * dropout offsets (0, 1 << 40, 2 << 40 plus an element index).  TAV_ERR_SHAPE when a row could take more than 128 spans:
+ * min(max(min_masks, floor(prob * L / length + 1)), L / length) > 128.  The _dev form reads the seed from a device word, as
+ * tav_dropout_fwd_dev does. */
+#define TAV_SPECAUG_TAG_TIME 0x5350010000000000ull
+#define TAV_SPECAUG_TAG_FEATURE 0x5350030000000000ull
+int tav_specaug_draw(const uint8_t* valid, uint8_t* mask, int32_t* nspans, int64_t B, int64_t L, float prob, int64_t length, int64_t min_masks,
+                     uint64_t seed, uint64_t tag, void* stream);
+int tav_specaug_draw_dev(const uint8_t* valid, uint8_t* mask, int32_t* nspans, int64_t B, int64_t L, float prob, int64_t length,
+                         int64_t min_masks, const uint64_t* seed_state, uint64_t tag, void* stream);
+/* y[r][c] = fmask[r / T][c] ? 0 : (tmask[r] ? embed[c] : x[r][c]) for x, y f32 [B*T][H], tmask uint8 [B*T] (optional), fmask uint8 [B][H]
+ * (optional), embed f32 [H] (required with tmask).  Out of place, every element of y written; H % 4 == 0. */
+int tav_specaug_fwd(const float* x, const uint8_t* tmask, const uint8_t* fmask, const float* embed, float* y, int64_t B, int64_t T, int64_t H,
+                    void* stream);
+/* dx[r][c] = (tmask[r] | fmask[r / T][c]) ? 0 : dy[r][c]; with dembed (f32 [H], overwritten): dembed[c] = sum over the rows with tmask[r] of
+ * (fmask[r / T][c] ? 0 : dy[r][c]) -- per-part column sums in row order into the workspace (tav_specaug_bwd_ws_bytes(B*T, H) bytes), then
+ * the parts in order: no atomics, bitwise reproducible.  Without dembed the workspace may be NULL. */
+int64_t tav_specaug_bwd_ws_bytes(int64_t rows, int64_t H);
+int tav_specaug_bwd(const float* dy, const uint8_t* tmask, const uint8_t* fmask, float* dx, float* dembed, void* workspace,
+                    int64_t workspace_bytes, int64_t B, int64_t T, int64_t H, void* stream);
+
 /* wav2vec2 feature encoder pieces (HF wav2vec2/modeling_wav2vec2.py:275-323,382-419) -- activations are kept
  * channels-last [B][T][C] so every later conv is a GEMM over overlapping rows.
  * conv0: Conv1d(1, C, k=10, s=5) direct: y[b][t][c] = sum_j x[b][5t+j] w[c][j] (+ bias[c]) */

@@ -130,6 +130,11 @@ _SIGS = {
     "tav_dropout_fwd": (C.c_int, [vp, vp, vp, i64, f32, C.c_uint64, C.c_uint64, vp]),
     "tav_dropout_fwd_dev": (C.c_int, [vp, vp, vp, i64, f32, vp, C.c_uint64, vp]),
     "tav_dropout_bwd": (C.c_int, [vp, vp, vp, i64, f32, vp]),
+    "tav_specaug_draw": (C.c_int, [vp, vp, vp, i64, i64, f32, i64, i64, C.c_uint64, C.c_uint64, vp]),
+    "tav_specaug_draw_dev": (C.c_int, [vp, vp, vp, i64, i64, f32, i64, i64, vp, C.c_uint64, vp]),
+    "tav_specaug_fwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, vp]),
+    "tav_specaug_bwd_ws_bytes": (C.c_int64, [i64, i64]),
+    "tav_specaug_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
     "tav_conv0_fwd": (C.c_int, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, vp]),
     "tav_conv0_bwd_w": (C.c_int, [vp, vp, i32, vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, vp]),
     "tav_conv0_bwd_partials": (C.c_int, [i64, i64, i64, i64]),

@@ -215,6 +215,14 @@ TAV_DEV void settle(uint4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z
 TAV_DEV void settle(float& v) { asm volatile("" : "+v"(v)); }
 TAV_DEV void wait_vmcnt0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// ---- counter-based RNG (dropout, SpecAugment): splitmix64's finaliser.  A draw is mix64(seed ^ mix64(stream offset + index)).
+TAV_DEV uint64_t mix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
 // ---- wave reductions ----------------------------------------------------------------------------
 TAV_DEV float wave_sum(float v) {
 #pragma unroll

@@ -502,12 +502,6 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
         }
 }
 
-TAV_DEV uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 TAV_DEV void dropout_one(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, long i, float p, uint64_t seed, uint64_t offset) {
     const uint64_t r = mix64(seed ^ mix64(offset + (uint64_t)i));
     const float u = (float)(r >> 40) * (1.f / 16777216.f);

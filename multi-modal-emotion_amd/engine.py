@@ -962,6 +962,24 @@ class HeadFn(torch.autograd.Function):
         return dx, None, None, dW, db
 
 
+class SpecAugFn(torch.autograd.Function):
+    """SpecAugment's masked copy (models/tav.py:281-304) of the f32 hidden states [B*T, H]: frames selected by tmask [B, T] are replaced by
+    `embed` (masked_spec_embed, a trained parameter), then channels selected by fmask [B, H] are zeroed on every frame of the row.  The masks
+    are bool / uint8 tensors from any sampler (ops.specaug_draw, or the host in "reference" mode); either may be None."""
+
+    @staticmethod
+    def forward(ctx, x, embed, tmask, fmask, B, T):
+        ctx.save_for_backward(tmask, fmask)
+        ctx.B, ctx.T = B, T
+        return ops.specaug_fwd(_c(x), tmask, fmask, embed.detach(), B, T)
+
+    @staticmethod
+    def backward(ctx, g):
+        tmask, fmask = ctx.saved_tensors
+        dx, dembed = ops.specaug_bwd(_c(g), tmask, fmask, ctx.B, ctx.T, want_dembed=ctx.needs_input_grad[1])
+        return dx, dembed, None, None, None, None
+
+
 class PoolNormCatFn(torch.autograd.Function):
     """cat_j LN_j(pool_j(x_j)) for a list of branches, each either already pooled [B, 768] or a sequence [B*S_j, 768] that is
     mean-pooled over its S_j tokens first (models/tav.py:478-495 without the fusion branch).  seq_lens[j] may also be a pair

@@ -107,6 +107,7 @@ class PreFormer(nn.Module):
             self.vid_2_768 = nn.Linear(cfg["video"]["hidden"], 768)
             nn.init.xavier_normal_(self.vid_2_768.weight)
         self.check_shapes = 1
+        self._spec_calls = 0             # SpecAugment draws taken in "device" mode (runtime.dropout_seeds)
 
     # -- reference helpers, same names (models/tav.py:308-342) --
     def _get_feat_extract_output_lengths(self, input_lengths, add_adapter=None):
@@ -151,6 +152,8 @@ class PreFormer(nn.Module):
         f_prob, f_len, f_min = ac.get("mask_feature_prob", 0.0), ac.get("mask_feature_length", 10), ac.get("mask_feature_min_masks", 0)
         if not training or T < mask_len:                                                       # (:277-278)
             return hidden
+        if runtime.specaugment() != "torch":
+            return self._mask_hidden_states_kernels(hidden, B, T, attention_mask)
         dev = hidden.device
         if mask_prob > 0:
             if attention_mask is not None:
@@ -164,6 +167,55 @@ class PreFormer(nn.Module):
             fsel = self._span_mask(B, Hh, torch.full((B,), float(Hh), device=dev), f_prob, f_len, f_min, dev)      # [B, H]: no attention mask on this axis (:296-301)
             hidden = torch.where(fsel[:, None, :].expand(B, T, Hh).reshape(B * T, Hh), torch.zeros((), dtype=hidden.dtype, device=dev), hidden)
         return hidden
+
+    def _spec_cfg(self):
+        """(time, feature) x (prob, length, min_masks): the keys and Wav2Vec2Config defaults _mask_hidden_states reads."""
+        ac = self.cfg["audio"] if hasattr(self, "cfg") else {}
+        return ((ac.get("mask_time_prob", 0.05), ac.get("mask_time_length", 10), ac.get("mask_time_min_masks", 2)),
+                (ac.get("mask_feature_prob", 0.0), ac.get("mask_feature_length", 10), ac.get("mask_feature_min_masks", 0)))
+
+    def reference_spec_masks(self, B, T, H, attention_mask=None):
+        """The masks the reference draws (models/tav.py:283-301): HF `_compute_mask_indices` on the host, from numpy's global generator, with the
+        reference's arguments in the reference's order -- the time axis first, with the frame attention mask and min_masks = mask_time_min_masks,
+        then the feature axis without a mask.  -> (bool [B, T] or None, bool [B, H] or None), CPU tensors; an axis whose probability is 0 is
+        None and consumes no numpy draw.  Pure host code: runs without a GPU."""
+        from transformers.models.wav2vec2.modeling_wav2vec2 import _compute_mask_indices
+        (t_prob, t_len, t_min), (f_prob, f_len, f_min) = self._spec_cfg()
+        tmask = fmask = None
+        if T < t_len:                                                                          # (:277-278)
+            return None, None
+        if t_prob > 0:
+            am = attention_mask.detach().to("cpu", torch.long) if attention_mask is not None else None
+            tmask = torch.from_numpy(_compute_mask_indices((B, T), mask_prob=t_prob, mask_length=t_len, attention_mask=am, min_masks=t_min))
+        if f_prob > 0:
+            fmask = torch.from_numpy(_compute_mask_indices((B, H), mask_prob=f_prob, mask_length=f_len, min_masks=f_min))
+        return tmask, fmask
+
+    def _mask_hidden_states_kernels(self, hidden, B, T, attention_mask):
+        """SpecAugment through libtavhip (runtime.specaugment() "device" / "reference"): the masks come from tav_specaug_draw on this module's
+        seed stream, or from the host as the reference draws them; engine.SpecAugFn applies them and owns the backward (dx, and the gradient
+        of masked_spec_embed)."""
+        (t_prob, t_len, t_min), (f_prob, f_len, f_min) = self._spec_cfg()
+        if t_prob <= 0 and f_prob <= 0:
+            return hidden
+        H = hidden.shape[1]
+        if runtime.specaugment() == "reference":
+            if runtime.capture_active():
+                raise RuntimeError('SpecAugment mode "reference" draws its masks on the host (numpy, HF _compute_mask_indices) and cannot be '
+                                   'captured into a hipGraph; use runtime.set_specaugment("device") or run the step eagerly')
+            tmask, fmask = self.reference_spec_masks(B, T, H, attention_mask)
+            tmask = tmask.to(hidden.device) if tmask is not None else None
+            fmask = fmask.to(hidden.device) if fmask is not None else None
+        else:
+            # one seed per forward that draws, for both axes (their tags keep the two streams apart); a device word under a capture
+            seed, = runtime.dropout_seeds(self, "_spec_calls", 1)
+            tmask = fmask = None
+            if t_prob > 0:
+                valid = attention_mask.to(hidden.device) if attention_mask is not None else None
+                tmask = ops.specaug_draw(valid, B, T, t_prob, t_len, t_min, seed, ops.SPECAUG_TAG_TIME, device=hidden.device)
+            if f_prob > 0:
+                fmask = ops.specaug_draw(None, B, H, f_prob, f_len, f_min, seed, ops.SPECAUG_TAG_FEATURE, device=hidden.device)
+        return E.SpecAugFn.apply(hidden, self.masked_spec_embed, tmask, fmask, B, T)
 
     def forward(self, input_ids=None, audio_features=None, video_embeds=None, text_mask=None, audio_mask=None, visual_mask=None,
                 device="cpu", train=False, n_visual_true=None, visual_caps=None):

@@ -741,6 +741,62 @@ def dropout_bwd(dy, mask, p):
     return dx
 
 
+# ---------------------------------------------------------------------------------------------- SpecAugment
+SPECAUG_TAG_TIME = 0x5350010000000000          # include/tavhip.h TAV_SPECAUG_TAG_*
+SPECAUG_TAG_FEATURE = 0x5350030000000000
+
+
+def _mask_bytes(m, shape, what):
+    """A bool / uint8 mask as the uint8 tensor the kernels read (a bool tensor is one byte per element: a view, no copy)."""
+    if m is None:
+        return None
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8)
+    if m.dtype != torch.uint8 or m.numel() != shape[0] * shape[1]:
+        raise ValueError(f"{what}: expected a bool / uint8 mask of {shape[0]} x {shape[1]} elements, got {m.dtype} {tuple(m.shape)}")
+    return m.contiguous()
+
+
+def specaug_draw(valid, B, L, prob, length, min_masks, seed, tag, *, device=None, want_nspans=False):
+    """uint8 [B, L] span mask (tav_specaug_draw).  valid: bool / uint8 [B, L] or None; seed: an int (by value) or a one-word int64 device
+    tensor read when the kernel runs (runtime.dropout_seeds under a capture), as in dropout_fwd."""
+    valid = _mask_bytes(valid, (B, L), "specaug_draw")
+    dev = valid.device if valid is not None else (seed.device if isinstance(seed, torch.Tensor) else device)
+    mask = torch.empty(B, L, dtype=torch.uint8, device=dev)
+    nspans = torch.empty(B, dtype=torch.int32, device=dev) if want_nspans else None
+    if isinstance(seed, torch.Tensor):
+        if not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() != 1:
+            raise ValueError(f"specaug_draw: a device seed is one int64 word on the GPU, got {seed.dtype} x {seed.numel()} on {seed.device}")
+        check(lib().tav_specaug_draw_dev(ptr(valid), ptr(mask), ptr(nspans), B, L, prob, length, min_masks, ptr(seed), tag, stream()), "specaug_draw_dev")
+    else:
+        check(lib().tav_specaug_draw(ptr(valid), ptr(mask), ptr(nspans), B, L, prob, length, min_masks, seed, tag, stream()), "specaug_draw")
+    return (mask, nspans) if want_nspans else mask
+
+
+def specaug_fwd(x, tmask, fmask, embed, B, T):
+    """y = fmask ? 0 : (tmask ? embed : x) for x f32 [B*T, H]; tmask [B, T] / fmask [B, H] bool or uint8, either may be None."""
+    H = x.shape[-1]
+    tmask, fmask = _mask_bytes(tmask, (B, T), "specaug_fwd"), _mask_bytes(fmask, (B, H), "specaug_fwd")
+    y = torch.empty_like(x)
+    check(lib().tav_specaug_fwd(ptr(x), ptr(tmask), ptr(fmask), ptr(embed), ptr(y), B, T, H, stream()), "specaug_fwd")
+    return y
+
+
+def specaug_bwd(dy, tmask, fmask, B, T, want_dembed=True):
+    """-> (dx, dembed or None): dx = (tmask | fmask) ? 0 : dy, dembed = column sums of the unmasked channels of dy over the time-masked rows."""
+    H = dy.shape[-1]
+    tmask, fmask = _mask_bytes(tmask, (B, T), "specaug_bwd"), _mask_bytes(fmask, (B, H), "specaug_bwd")
+    dx = torch.empty_like(dy)
+    dembed = part = None
+    nbytes = 0
+    if want_dembed:
+        dembed = torch.empty(H, dtype=torch.float32, device=dy.device)
+        nbytes = lib().tav_specaug_bwd_ws_bytes(B * T, H)
+        part = workspace("specaug_part", nbytes // 4, dy.device)
+    check(lib().tav_specaug_bwd(ptr(dy), ptr(tmask), ptr(fmask), ptr(dx), ptr(dembed), ptr(part), nbytes, B, T, H, stream()), "specaug_bwd")
+    return dx, dembed
+
+
 # ---------------------------------------------------------------------------------------------- audio front-end
 def conv0_fwd(wave, w, bias, T_out, stride, dtype):
     B, T_in = wave.shape

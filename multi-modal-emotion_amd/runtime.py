@@ -79,6 +79,31 @@ def visual_capacities(nt, ntok, g):
     return cap_true, cap_keep
 
 
+# ---- SpecAugment sampler (PreFormer._mask_hidden_states, train=True only):
+#   "torch"      spans drawn with torch ops on the device from torch's generator (the default; also runs on CPU tensors)
+#   "device"     spans drawn by tav_specaug_draw from the dropout seed words (dropout_seeds): the k-th training forward of a PreFormer draws the
+#                same masks whether it ran eagerly or as a graph replay; applied and differentiated by engine.SpecAugFn
+#   "reference"  spans drawn on the host from numpy's global generator by HF _compute_mask_indices, as the reference does; same SpecAugFn.
+#                Reads the host, so it cannot be captured into a hipGraph
+SPECAUGMENT_MODES = ("torch", "device", "reference")
+_specaugment = ["torch"]
+
+
+def check_specaugment(mode):
+    if mode not in SPECAUGMENT_MODES:
+        raise ValueError(f"specaugment must be one of {SPECAUGMENT_MODES}, got {mode!r}")
+    return mode
+
+
+def set_specaugment(mode="torch"):
+    _specaugment[0] = check_specaugment(mode)
+    return mode
+
+
+def specaugment():
+    return _specaugment[0]
+
+
 # ---- branch streams: text / audio / video encoders run beside the fusion encoder (reference models/tav.py:476-487 are
 # four independent sub-graphs that meet only at the concat, :495).  Autograd replays each branch's backward on the stream its
 # forward used, so the backward overlaps the same way; under hipGraph capture the fork/join becomes parallel graph branches.

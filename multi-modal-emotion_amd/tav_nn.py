@@ -62,6 +62,7 @@ def main(argv=None):
     C.set_default_preset(args.preset)
     runtime.set_precision(args.dtype)
     runtime.set_visual_rows(args.visual_rows, bucket=args.visual_bucket)
+    runtime.set_specaugment(args.specaugment)
     cfg = C.default_config()
     weights = torch.linspace(0.6, 0.95, args.output_dim)            # reference: 1 - class frequency (tav_nn.py:171)
     id2label = {i: f"class{i}" for i in range(args.output_dim)}

@@ -16,6 +16,9 @@ the signature carries ("ragged", cap_true, cap_keep) -- runtime.visual_capacitie
 the captured step is built from the two capacities alone and reads every length from the mask in its static buffer (ops.ragged_lens), so all
 batches whose counts fall into the bucket replay one graph.  The host knows the counts before it replays, so a batch that does not fit never
 reaches a graph; the status word the step leaves is read together with the loss all the same.
+SpecAugment: in "device" mode the PreFormer's draw is a dropout site like the others (its seed word is rewritten before each replay), so the
+replayed step masks what the eager step would have; in "reference" mode the masks come from the host, no batch has a signature and every
+training step runs eagerly.
 Graphs are freed at the end of every epoch and whenever the optimizer's state was reloaded (load_model builds new moment tensors).
 """
 import weakref
@@ -100,6 +103,8 @@ class GraphedSteps:
         return c[0] if c and all(v == c[0] for v in c) else None
 
     def signature(self, input, label, epoch, accum):
+        if runtime.specaugment() == "reference":
+            return None                          # the masks are drawn on the host (numpy): training batches run the eager step
         if runtime.visual_bucket():
             # ragged rows at a bucketed capacity: the two padded sizes stand for the counts (equal rows included -- one path per bucket)
             nv = ("ragged",) + runtime.visual_capacities(self._visual_counts(input), input[2]["attention_mask"].shape[1], runtime.visual_bucket())
@@ -110,7 +115,7 @@ class GraphedSteps:
         crit = self.stepper.criterion
         branch = (epoch % crit.epoch_switch == 0) if hasattr(crit, "epoch_switch") else None      # NewCrossEntropyLoss: weighted or not
         shapes = tuple(None if d is None else tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(d.items()) if torch.is_tensor(v)) for d in input)
-        return (shapes, (tuple(label.shape), label.dtype), nv, "train", branch, bool(accum))
+        return (shapes, (tuple(label.shape), label.dtype), nv, "train", branch, bool(accum), runtime.specaugment())
 
     # ---- one training step
     def step(self, input, label, epoch, Metric, accum_iter=None):

@@ -173,6 +173,10 @@ def arg_parse(description, argv=None):
     parser.add_argument("--visual-bucket", dest="visual_bucket", default=0, type=int,
                         help="with --visual-rows ragged: pad ragged batches to multiples of this many tokens, so that batches of one bucket share "
                              "their shapes and, with --graph 1, one captured step (0: natural sizes, ragged batches stay eager)")
+    parser.add_argument("--specaugment", default="torch", choices=["torch", "device", "reference"],
+                        help="SpecAugment sampler of training forwards (runtime.set_specaugment): torch = torch ops on torch's generator; device = "
+                             "HIP kernels on the dropout seed words, eager calls and graph replays draw the same masks; reference = HF "
+                             "_compute_mask_indices on the host from numpy's generator, as the reference (training batches stay eager under --graph 1)")
     parser.add_argument("--graph", default=0, type=int, choices=[0, 1],
                         help="1: replay each training step from a captured hipGraph (tav_nn only; train_tav_network(graphs=True))")
     return parser.parse_args(argv)

@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--preset", default="B")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--cycle", type=int, default=2, help="distinct device-resident batches, used in turn")
+    ap.add_argument("--specaugment", default="torch", choices=["torch", "device", "reference"], help="runtime.set_specaugment")
     args = ap.parse_args()
 
     import torch
@@ -42,6 +43,7 @@ def main():
     torch.cuda.set_stream(work)
     cfg = C.preset(args.preset)
     runtime.set_precision(args.dtype)
+    runtime.set_specaugment(args.specaugment)
     torch.manual_seed(0)
     pre, model = PreFormer(cfg), TAVForMAE(dict(output_dim=7, dropout=0.5, learn_PosEmbeddings=True, num_layers=12), cfg)
     synthetic.seeded_init_(pre, 1)
@@ -77,6 +79,7 @@ def main():
     el = time.perf_counter() - t0
     ms = el / args.steps * 1e3
     out = {"tool": "gpu_train_loop_speed", "mode": args.mode, "preset": args.preset, "dtype": args.dtype, "global_batch": b, "check": "train",
+           "specaugment": args.specaugment,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "utt_per_s": round(b / (el / args.steps), 2),
            "last_loss": round(losses[-1], 5), "finite": all(v == v and abs(v) != float("inf") for v in losses),
            "peak_mem_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
