@@ -4,12 +4,14 @@ Each check returns (name, max_abs_err, tolerance, ok).  Used by tests/test_kerne
 tools/gpu_kernel_check.py (prints a table without stopping at the first failure).
 """
 import contextlib
+import functools
 import math
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+import gemm_ref as GR
 import guarded
 import step_end_ref as SR
 import tav_amd.ops as ops
@@ -1767,6 +1769,320 @@ def step_end_checks():
     return out
 
 
+# ------------------------------------------------------------------------------------------------ GEMM family against fp64 ("GEMM checks")
+# Two instruments on top of the _res cases above, which stay as they are.  (1) Per-element bounds: operands with spread magnitudes, the fp64
+# reference of the documented epilogue and a bound per output element from tests/gemm_ref.py; err = worst |got - ref| / bound, tol = 1.  (2) Exact
+# integers: operands in {-7 .. 7}, every partial sum an integer below 2^24 in any order, so the result has ONE right answer (_exact).
+_GDT = {torch.bfloat16: "bf16", torch.float32: "f32"}
+_TDT = {"bf16": torch.bfloat16, "f32": torch.float32}
+
+
+def _up(x, dtype):
+    """A numpy array of values the dtype holds exactly -> a (guarded) device tensor of that dtype."""
+    return _in(torch.from_numpy(np.ascontiguousarray(x)).to(DEV).to(dtype))
+
+
+def _bounded(name, got, ref, bound):
+    r = GR.ratio(got.detach().double().cpu().numpy(), ref, bound)
+    return (name, r, 1.0, bool(r <= 1.0))
+
+
+@functools.lru_cache(maxsize=None)
+def _nt_problem(dname, M, N, K, seed=0):
+    return GR.nt_inputs(M, N, K, dname, seed=seed + 7 * M + 3 * N + K)
+
+
+@functools.lru_cache(maxsize=None)
+def _nt_reference(dname, M, N, K, flavour):
+    return GR.nt_ref(_nt_problem(dname, M, N, K), **GR.FLAVOURS[flavour])
+
+
+_NT_FEW = ("bias", "bias+resid->f32", "act3", "gelu_in.act4", "accumulate->f32", "act1+pre->f32")
+
+
+def _nt_flavours(dtype, names):
+    """f32 operands store f32 only: their "->f32" twins would be the same launch twice."""
+    return [n for n in names if dtype != torch.float32 or not n.endswith("->f32")]
+
+
+def check_gemm_nt_bounded(dtype, hint, M=333, N=384, K=256, flavours=None):
+    """tav_gemm_nt, every epilogue flavour of gemm_ref.FLAVOURS, each output element (C and C_pre) within its own bound."""
+    dname = _GDT[dtype]
+    x = _nt_problem(dname, M, N, K)
+    a, b = _up(x["a"], dtype), _up(x["b"], dtype)
+    rs = []
+    for name in _nt_flavours(dtype, flavours or tuple(GR.FLAVOURS)):
+        kw = GR.FLAVOURS[name]
+        ref = _nt_reference(dname, M, N, K, name)
+        odt = torch.float32 if (dtype == torch.float32 or kw.get("out_dtype") == "f32") else torch.bfloat16
+        args = dict(tile_m=hint, out_dtype=odt, act=kw.get("act", 0), want_pre=kw.get("want_pre", False), alpha=kw.get("alpha", 1.0))
+        if kw.get("bias"):
+            args["bias"] = _up(x["bias"], torch.float32)
+        if kw.get("resid"):
+            args["resid"] = _up(x["resid"], torch.float32)
+        if kw.get("gelu_in"):
+            args["gelu_in"] = _up(x[kw["gelu_in"]], dtype)
+        if kw.get("accumulate"):
+            out = _blank((M, N), odt)
+            out.copy_(torch.from_numpy(x["cprev_" + ("f32" if odt == torch.float32 else "bf16")]).to(DEV).to(odt))
+            args.update(out=out, accumulate=True)
+        res = ops.gemm_nt(a, b, **args)
+        out, pre = res if isinstance(res, tuple) else (res, None)
+        tag = f"gemm_nt.bound[{dname},tm{hint},M{M},N{N},K{K},{name}]"
+        rs.append(_bounded(tag, out, ref["out"], ref["out_bound"]))
+        if pre is not None:
+            rs.append(_bounded(tag + ".pre", pre, ref["pre"], ref["pre_bound"]))
+    return rs
+
+
+def check_gemm_nt_bounded_shapes(dtype):
+    """The shapes around the main loop and the tile edges: every prologue / tail length of the 256 x 256 tile's 3 + 2 image ring (1, 2, 3 and 5
+    K-tiles), the longest K of the per-element cases, and M = 1, tile - 1, tile + 1 (bf16: hints 8 and 16; f32 has the 128-wide tiles only)."""
+    rs = []
+    if dtype == torch.bfloat16:
+        for K in (64, 128, 192, 320):
+            rs += check_gemm_nt_bounded(dtype, 16, M=300, N=260, K=K, flavours=_NT_FEW)
+        for hint in (8, 16):
+            rs += check_gemm_nt_bounded(dtype, hint, M=513, N=132, K=1536, flavours=_NT_FEW)
+        for M in (1, 255, 257):
+            rs += check_gemm_nt_bounded(dtype, 16, M=M, N=260, K=128, flavours=_NT_FEW)
+    else:
+        rs += check_gemm_nt_bounded(dtype, 0, M=513, N=132, K=1536, flavours=_NT_FEW)
+        for M in (1, 127, 129):
+            rs += check_gemm_nt_bounded(dtype, 4, M=M, N=260, K=128, flavours=_NT_FEW)
+    return rs
+
+
+def check_gemm_nt_bounded_batched(dtype, nzb=2, nzg=3, M=70, N=132, K=128):
+    """One call with nzb x nzg slices: A and C stride over both, B and the bias over the group only."""
+    dname = _GDT[dtype]
+    probs = [[_nt_problem(dname, M, N, K, seed=100 + 10 * zb + zg) for zg in range(nzg)] for zb in range(nzb)]
+    a = _up(np.stack([np.stack([probs[zb][zg]["a"] for zg in range(nzg)]) for zb in range(nzb)]), dtype)
+    b = _up(np.stack([probs[0][zg]["b"] for zg in range(nzg)]), dtype)
+    bias = _up(np.stack([probs[0][zg]["bias"] for zg in range(nzg)]), torch.float32)
+    out = ops.gemm_nt(a, b, bias=bias, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, nzb=nzb, nzg=nzg, a_zb=nzg * M * K, a_zg=M * K, b_zg=N * K,
+                      c_zb=nzg * M * N, c_zg=M * N, bias_zg=N, out_shape=(nzb, nzg, M, N))
+    rs = []
+    for zb in range(nzb):
+        for zg in range(nzg):
+            x = dict(probs[zb][zg], b=probs[0][zg]["b"], bias=probs[0][zg]["bias"])
+            ref = GR.nt_ref(x, bias=True)
+            rs.append(_bounded(f"gemm_nt.bound.batched[{dname},zb{zb},zg{zg}]", out[zb, zg], ref["out"], ref["out_bound"]))
+    return rs
+
+
+def _int_dev(shape, seed, dtype=torch.float32):
+    return _in(torch.from_numpy(GR.int_tensor(shape, seed)).to(DEV).to(dtype))
+
+
+def _exact_both(tag, run, want):
+    """run(out_dtype) against the exact integer result `want` (fp64): f32 bit for bit, bf16 its round-to-nearest-even."""
+    return [_exact(tag + "->f32", run(torch.float32), want.float()), _exact(tag + "->bf16", run(torch.bfloat16), want.float().to(torch.bfloat16))]
+
+
+def check_gemm_nt_int(dtype, hint, M=333, N=384, K=256):
+    """Exact integer operands (bf16 / f32) with an integer bias: no tolerance."""
+    assert GR.int_exact_ok(K)
+    a, b, bias = _int_dev((M, K), 1000 + K, dtype), _int_dev((N, K), 2000 + K, dtype), _int_dev((N,), 3000 + K)
+    want = a.double() @ b.double().t() + bias.double()
+    tag = f"gemm_nt.int[{_GDT[dtype]},tm{hint},M{M},N{N},K{K}]"
+    if dtype == torch.float32:
+        return [_exact(tag, ops.gemm_nt(a, b, bias=bias, tile_m=hint), want.float())]
+    return _exact_both(tag, lambda odt: ops.gemm_nt(a, b, bias=bias, tile_m=hint, out_dtype=odt), want)
+
+
+def check_gemm_nt_int_all(dtype):
+    """Every tile hint at the shape of the per-element cases, the ring and edge shapes of the 256 x 256 tile, and one case at K = 3072."""
+    rs = []
+    for hint in (0, 2, 3, 4, 17) + ((8, 16) if dtype == torch.bfloat16 else ()):
+        rs += check_gemm_nt_int(dtype, hint)
+    if dtype == torch.bfloat16:
+        for K in (64, 128, 192, 320):
+            rs += check_gemm_nt_int(dtype, 16, M=300, N=260, K=K)
+        for hint in (8, 16):
+            rs += check_gemm_nt_int(dtype, hint, M=513, N=132, K=3072)
+    else:
+        rs += check_gemm_nt_int(dtype, 0, M=513, N=132, K=3072)
+    return rs
+
+
+def check_gemm_nt_int_mixed_schedule(M=46848 + 37, N=768, K=768):
+    """The two-launch schedule of check_gemm_nt_mixed_schedule against the TRUTH, not only against the single-tile launch."""
+    assert GR.int_exact_ok(K)
+    a, b, bias = _int_dev((M, K), 41, torch.bfloat16), _int_dev((N, K), 42, torch.bfloat16), _int_dev((N,), 43)
+    want = a.double() @ b.double().t() + bias.double()
+    return _exact_both(f"gemm_nt.int.mixed[M{M},N{N},K{K}]", lambda odt: ops.gemm_nt(a, b, bias=bias, out_dtype=odt), want)
+
+
+def check_fp8_int(M, N, K, tile_m):
+    """fp8 operands from integers with amax = 7: the quantisation scale is 64 and the dequantisation factor 2^-6, both exact, so q = 64 x and the
+    GEMM with its dequantisation scales has one right answer."""
+    assert GR.int_exact_ok(K)
+    ops.clear_workspaces()
+    x, w, bias = _int_dev((M, K), 5000 + K, torch.bfloat16), _int_dev((N, K), 6000 + K), _int_dev((N,), 7000 + K)
+    x8, w8 = ops.fp8_quantize(x), ops.fp8_quantize(w)
+    tag = f"fp8.int[M{M},N{N},K{K},tm{tile_m}]"
+    rs = [_exact(tag + ".scales", torch.stack([x8.scales[:3], w8.scales[:3]]), torch.tensor([[64.0, 2.0 ** -6, 7.0]] * 2, device=DEV)),
+          _exact(tag + ".q", x8.q.float(), x.float() * 64.0)]
+    want = x.double() @ w.double().t() + bias.double()
+    return rs + _exact_both(tag, lambda odt: ops.gemm_nt_fp8(x8, w8, bias=bias, out_dtype=odt, tile_m=tile_m), want)
+
+
+def check_wgrad_fp8_int(T=333, N1=132, N2=256):
+    """ops.wgrad_fp8 (the NT GEMM of the zero-padded transposed copies in eight K-slices plus tav_splitk_reduce) on integer operands: exact."""
+    ops.clear_workspaces()
+    rows_pad = (T + ops.FP8_KPAD - 1) // ops.FP8_KPAD * ops.FP8_KPAD
+    assert GR.int_exact_ok(rows_pad)
+    dy, x = _int_dev((T, N1), 8001, torch.bfloat16), _int_dev((T, N2), 8002, torch.bfloat16)
+    dy8, x8 = ops.fp8_quantize(dy, want_q=False, want_t=True), ops.fp8_quantize(x, want_t=True)
+    return [_exact(f"fp8.int.wgrad[T{T},N1{N1},N2{N2}]", ops.wgrad_fp8(dy8, x8), (dy.double().t() @ x.double()).float())]
+
+
+# ---- weight gradients
+def _tn_call(a, b, N1, N2, rows, nbatch, *, chunk_rows=0, scale=1.0, accumulate=False, perm=(0, 0), out=None, dbias=None):
+    """tav_gemm_tn through the C ABI (ops.gemm_tn chooses the split and allocates dbias itself: here the caller may force chunk_rows and hand in
+    the tensors an accumulating call adds to).  -> (out, dbias, nsplit)."""
+    import ctypes as C
+    cr, ns = C.c_int32(), C.c_int32()
+    ops.check(ops.lib().tav_gemm_tn_splits(N1, N2, rows, nbatch, C.byref(cr), C.byref(ns)), "gemm_tn_splits")
+    if chunk_rows:
+        cr.value, ns.value = chunk_rows, nbatch * ((rows + chunk_rows - 1) // chunk_rows)
+    g = ops.L.GemmTNArgs()
+    out = out if out is not None else _blank((N1, N2), torch.float32)
+    dbias = dbias if dbias is not None else _blank((N1,), torch.float32)
+    slabs, bpart = ops.workspace("tn_slabs", ns.value * N1 * N2, a.device), ops.workspace("tn_bias", ns.value * N1, a.device)
+    g.A, g.B, g.slabs, g.out, g.dbias, g.bias_partials = ops.ptr(a), ops.ptr(b), ops.ptr(slabs), ops.ptr(out), ops.ptr(dbias), ops.ptr(bpart)
+    g.N1, g.N2, g.lda, g.ldb, g.rows_per_batch, g.nbatch, g.a_zb, g.b_zb = N1, N2, N1, N2, rows, nbatch, rows * N1, rows * N2
+    g.chunk_rows, g.nsplit, g.perm_inner, g.perm_outer = cr.value, ns.value, perm[0], perm[1]
+    g.dtype, g.accumulate, g.scale = ops.dt(a), int(accumulate), scale
+    ops.check(ops.lib().tav_gemm_tn(C.byref(g), ops.stream()), "gemm_tn")
+    return out, dbias, ns.value
+
+
+@functools.lru_cache(maxsize=None)
+def _tn_problem(dname, T, N1, N2, seed=0):
+    return GR.tn_inputs(T, N1, N2, dname, seed=seed + T + 3 * N1 + 5 * N2)
+
+
+_TN_VARIANTS = [("plain", dict(), 0), ("chunk64,scale", dict(scale=0.37), 64), ("accumulate,scale", dict(scale=-1.7, accumulate=True), 0),
+                ("conv perm", dict(perm=(88, 3)), 0), ("conv perm,chunk64,accumulate", dict(perm=(88, 3), accumulate=True), 64)]
+
+
+def check_gemm_tn_bounded(dtype, rows, nbatch=1, N1=136, N2=264):
+    """tav_gemm_tn: the library's own split and one chunk per 64 rows, scale != 1, accumulate into out AND dbias, the conv-style column
+    permutation (N2 = 3 taps x 88 channels); out and dbias per element."""
+    dname = _GDT[dtype]
+    x = _tn_problem(dname, rows * nbatch, N1, N2)
+    a, b = _up(x["a"], dtype), _up(x["b"], dtype)
+    rs = []
+    for name, kw, chunk in _TN_VARIANTS:
+        ops.clear_workspaces()
+        out = dbias = None
+        if kw.get("accumulate"):
+            out, dbias = _blank((N1, N2), torch.float32), _blank((N1,), torch.float32)
+            out.copy_(torch.from_numpy(x["prev"]).to(DEV))
+            dbias.copy_(torch.from_numpy(x["prev_b"]).to(DEV))
+        out, dbias, ns = _tn_call(a, b, N1, N2, rows, nbatch, chunk_rows=chunk, out=out, dbias=dbias, **kw)
+        ref = GR.tn_ref(x, nsplit=ns, **kw)
+        tag = f"gemm_tn.bound[{dname},rows{rows},nb{nbatch},{name},splits{ns}]"
+        rs += [_bounded(tag, out, ref["out"], ref["out_bound"]), _bounded(tag + ".dbias", dbias, ref["dbias"], ref["dbias_bound"])]
+    return rs
+
+
+def check_gemm_tn_int(dtype, rows, nbatch=1, N1=136, N2=264):
+    assert GR.int_exact_ok(rows * nbatch)
+    a, b = _int_dev((rows * nbatch, N1), 9001 + rows, dtype), _int_dev((rows * nbatch, N2), 9002 + rows, dtype)
+    want, want_b = (a.double().t() @ b.double()).float(), a.double().sum(0).float()
+    rs = []
+    for name, perm, chunk in (("plain", (0, 0), 0), ("chunk64", (0, 0), 64), ("conv perm", (88, 3), 0)):
+        ops.clear_workspaces()
+        out, dbias, ns = _tn_call(a, b, N1, N2, rows, nbatch, chunk_rows=chunk, perm=perm)
+        p = torch.from_numpy(GR.tn_perm(N2, *perm)).to(DEV)
+        tag = f"gemm_tn.int[{_GDT[dtype]},rows{rows},nb{nbatch},{name},splits{ns}]"
+        rs += [_exact(tag, out[:, p], want), _exact(tag + ".dbias", dbias, want_b)]
+    return rs
+
+
+_GROUP_SHAPES = [(384, 136), (136, 264), (256, 512), (520, 128)]
+
+
+def _grouped_forms(dtype, rows):
+    """(name, flags | None = the workspace-free tav_gemm_tn_grouped, upper limit of slab additions) of every form the library accepts here."""
+    forms = [("plain", None, 1), ("ws", 0, 1), ("ws.flag2", 2, 1)]
+    if dtype == torch.bfloat16:
+        for nsplit in (1, 2, 3):
+            if (nsplit - 1) * (((rows + nsplit - 1) // nsplit + 63) // 64 * 64) < rows:           # (the library refuses an empty split)
+                forms.append((f"ws.flag1.splits{nsplit}", 1 | (nsplit << 8), nsplit))
+    return forms
+
+
+def _grouped_run(pairs, flags):
+    if flags is not None:
+        return ops.gemm_tn_grouped(pairs, want_bias=True, flags=flags)
+    n = len(pairs)
+    probs, outs = (ops.L.GemmTNProblem * n)(), []
+    for k, (a, b) in enumerate(pairs):
+        dW, db = _blank((a.shape[1], b.shape[1]), torch.float32), _blank((a.shape[1],), torch.float32)
+        pr = probs[k]
+        pr.A, pr.B, pr.out, pr.dbias = ops.ptr(a), ops.ptr(b), ops.ptr(dW), ops.ptr(db)
+        pr.N1, pr.N2, pr.lda, pr.ldb = a.shape[1], b.shape[1], a.stride(0), b.stride(0)
+        outs.append((dW, db))
+    ops.check(ops.lib().tav_gemm_tn_grouped(probs, n, pairs[0][0].shape[0], ops.dt(pairs[0][0]), ops.stream()), "gemm_tn_grouped")
+    return outs
+
+
+def check_gemm_tn_grouped_bounded(dtype, rows):
+    """tav_gemm_tn_grouped and tav_gemm_tn_grouped_ws (flags 0, 1 with one to three splits, 2): four problems of ragged widths, dW and db of each
+    per element.  The bias of a bias-spread launch is summed from splits x tiles_2 partials: that count enters its chain."""
+    dname = _GDT[dtype]
+    xs = [_tn_problem(dname, rows, n1, n2, seed=50 + k) for k, (n1, n2) in enumerate(_GROUP_SHAPES)]
+    pairs = [(_up(x["a"], dtype), _up(x["b"], dtype)) for x in xs]
+    rs = []
+    for name, flags, nsplit in _grouped_forms(dtype, rows):
+        outs = _grouped_run(pairs, flags)
+        for k, (x, (dW, db)) in enumerate(zip(xs, outs)):
+            ref = GR.tn_ref(x, nsplit=nsplit)
+            tag = f"gemm_tn_grouped.bound[{dname},rows{rows},{name}]"
+            rs += [_bounded(f"{tag}.dW{k}", dW, ref["out"], ref["out_bound"]), _bounded(f"{tag}.db{k}", db, ref["dbias"], ref["dbias_bound"])]
+    return rs
+
+
+def check_gemm_tn_grouped_int(dtype, rows):
+    assert GR.int_exact_ok(rows)
+    pairs = [(_int_dev((rows, n1), 9100 + k, dtype), _int_dev((rows, n2), 9200 + k, dtype)) for k, (n1, n2) in enumerate(_GROUP_SHAPES)]
+    wants = [((a.double().t() @ b.double()).float(), a.double().sum(0).float()) for a, b in pairs]
+    rs = []
+    for name, flags, _ in _grouped_forms(dtype, rows):
+        for k, ((dW, db), (wW, wb)) in enumerate(zip(_grouped_run(pairs, flags), wants)):
+            tag = f"gemm_tn_grouped.int[{_GDT[dtype]},rows{rows},{name}]"
+            rs += [_exact(f"{tag}.dW{k}", dW, wW), _exact(f"{tag}.db{k}", db, wb)]
+    return rs
+
+
+def gemm_fp64_checks():
+    """The GEMM cases against fp64, in the order all_checks() appends them."""
+    out = []
+    for dtype in (torch.float32, torch.bfloat16):
+        for hint in (0, 2, 3, 4, 17) + ((8, 16) if dtype == torch.bfloat16 else ()):
+            out.append(lambda d=dtype, h=hint: check_gemm_nt_bounded(d, h))
+        out.append(lambda d=dtype: check_gemm_nt_bounded_shapes(d))
+        out.append(lambda d=dtype: check_gemm_nt_bounded_batched(d))
+        out.append(lambda d=dtype: check_gemm_nt_int_all(d))
+        for rows, nb in ((64, 1), (130, 1), (777, 1), (249, 3)):
+            out.append(lambda d=dtype, r=rows, n=nb: check_gemm_tn_bounded(d, r, n))
+            out.append(lambda d=dtype, r=rows, n=nb: check_gemm_tn_int(d, r, n))
+        out.append(lambda d=dtype: check_gemm_tn_int(d, 5000))
+        for rows in (64, 130, 777):
+            out.append(lambda d=dtype, r=rows: check_gemm_tn_grouped_bounded(d, r))
+            out.append(lambda d=dtype, r=rows: check_gemm_tn_grouped_int(d, r))
+        out.append(lambda d=dtype: check_gemm_tn_grouped_int(d, 5000))
+    out.append(check_gemm_nt_int_mixed_schedule)
+    for M, N, K, tm in ((333, 384, 256, 0), (333, 384, 256, 16), (130, 132, 128, 4), (257, 260, 3072, 16)):
+        out.append(lambda a=(M, N, K, tm): check_fp8_int(*a))
+    out.append(check_wgrad_fp8_int)
+    return out
+
+
 def all_checks():
     out = []
     for dtype in (torch.float32, torch.bfloat16):
@@ -1883,4 +2199,6 @@ def all_checks():
         out.append(lambda d=dtype: check_conv0_gn(d, B=1, T_in=10, ref64=True))
     # step-end kernels: gradient norm, clip coefficient, AdamW, operand casts, fp8 states
     out += step_end_checks()
+    # the GEMM family against fp64: per-element bounds and exact integer operands
+    out += gemm_fp64_checks()
     return out
