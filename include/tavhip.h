@@ -157,6 +157,11 @@ int tav_colsum(const void* x, int32_t dtype, int64_t M, int64_t N, int64_t ld, f
  *              o = softmax(s) v + (sum_key mask[key] v[key]) for every query row; `corr` [B][nheads][64] f32 receives
  *              that rank-1 term (needed again by the backward).
  * scale is applied to q.k^T (1/8 on the path).  lse [B][nheads][S] f32 = log-sum-exp of the scaled (masked) scores.
+ * OUTSIDE THE CONTRACT: a query row whose EVERY valid key carries a mask_mode 1 value near the most negative float (finfo.min).  The
+ * kernels form key_mask * log2(e) in f32, which overflows to -inf there; every probability of the row is then exp2(-inf - (-inf)) or 0,
+ * the row sum l is 0 or NaN, and o, lse and the gradients of that row are unspecified (NaN or inf).  A caller must leave at least one valid
+ * key of every row unmasked, or mask with a finite value whose product with log2(e) stays finite (-65504 is fine).  Partly masked rows
+ * are exact: the masked keys get probability 0.
  * Replaces utils/TAVFormer.py:357-383, :57-81 and HF eager_attention_forward. */
 typedef struct tav_attn_args {
     const void* q; const void* k; const void* v;

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import attn_ref as AR
 import gemm_ref as GR
 import guarded
 import step_end_ref as SR
@@ -2083,6 +2084,180 @@ def gemm_fp64_checks():
     return out
 
 
+# ================================================================================================= attention against fp64
+# tests/attn_ref.py: per-element bounds at operands of spread magnitude, and selections with ONE right answer.
+_ALENS_EXACT = {64: [64, 1, 33], 65: [0, 65, 64], 129: [65, 1, 128], 257: [257, 65, 200]}
+
+
+def _attn_operands(x, dtype):
+    """The operands of an attn_ref problem on the device: q / k / v as slices of one qkv buffer with a widened pitch, dO widened too."""
+    B, S, nh = x["B"], x["S"], x["nh"]
+    H = nh * 64
+    qkv = _in(torch.from_numpy(np.concatenate([x[n].reshape(B * S, H) for n in ("q", "k", "v")], 1)).to(DEV).to(dtype), 24)
+    do = _in(torch.from_numpy(x["do"].reshape(B * S, H)).to(DEV).to(dtype), 8)
+    mask = None if x["mask"] is None else _in(torch.from_numpy(x["mask"]).to(DEV).float())
+    return qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], do, mask
+
+
+def _attn_fwd(x, ops_in, sl):
+    q, k, v, _, mask = ops_in
+    o, lse, (corr, o_soft) = ops.attn_fwd(q, k, v, x["B"], x["S"], x["nh"], key_mask=mask, mask_mode=x["mode"], q_prescaled=x["pre"], seq_lens=sl)
+    return dict(o=o, lse=lse, corr=corr, o_soft=o_soft if o_soft is not None else o)
+
+
+def _attn_bwd(x, ops_in, sl, o, o_soft, lse, corr, tag):
+    """-> (dict dq, dk, dv [B][S][nh][64] views and delta [B][nh][S] with the rows past each length zeroed (not written by contract), gap check)."""
+    q, k, v, do, mask = ops_in
+    B, S, nh = x["B"], x["S"], x["nh"]
+    H = nh * 64
+    wide = _blank((B * S, 3 * H + 16), q.dtype)
+    dqkv = ops.attn_bwd(q, k, v, o, do, lse, (corr, o_soft) if x["mode"] == 2 else None, B, S, nh, key_mask=mask, mask_mode=x["mode"],
+                        q_prescaled=x["pre"], seq_lens=sl, dqkv=wide[:, 8:8 + 3 * H])
+    delta = ops.workspace("attn_delta", B * nh * S, q.device)[:B * nh * S].view(B, nh, S).clone()
+    for b, L in enumerate(x["lens"]):
+        delta[b, :, L:] = 0.0
+    got = {n: dqkv[:, j * H:(j + 1) * H].reshape(B, S, nh, 64) for j, n in enumerate(("dq", "dk", "dv"))}
+    got["delta"] = delta
+    return got, _all_ff(tag + ".dqkv gap", wide[:, :8], wide[:, 8 + 3 * H:])
+
+
+def _attn_fed(x, fd, dtype):
+    B, S, nh = x["B"], x["S"], x["nh"]
+    up = lambda a, dt_: _in(torch.from_numpy(np.ascontiguousarray(a)).to(DEV).to(dt_))      # noqa: E731
+    return (up(fd["o"].reshape(B * S, nh * 64), dtype), up(fd["o_soft"].reshape(B * S, nh * 64), dtype), up(fd["lse"], torch.float32),
+            up(fd["corr"], torch.float32))
+
+
+def _attn_lens(lens):
+    return None if lens is None else _in(torch.tensor(lens, dtype=torch.int32, device=DEV))
+
+
+def check_attention_bounded(dtype, S, lens=None, chained=False, B=2, nh=3):
+    """tav_attn_fwd / tav_attn_bwd (the _len forms with `lens`), every mask mode, pre-scaled or not: o, o_soft, corr, lse each within its own
+    per-element bound of the fp64 reference; the backward ISOLATED (fed the reference's o, o_soft, lse, corr rounded to the storage types): dq, dk,
+    dv and the delta workspace within theirs.  chained: the backward fed the kernel's own forward, against the composed bounds."""
+    dname = _GDT[dtype]
+    rs = []
+    B = len(lens) if lens is not None else B
+    for mode, pre in ((0, True), (1, False), (2, True)) if chained else [(m, p_) for m in (0, 1, 2) for p_ in (False, True)]:
+        x = AR.make_inputs(B, S, nh, dname, seed=11, **AR.bound_config(S, mode, pre, lens))
+        ref = AR.attn_ref(x)
+        ops_in, sl = _attn_operands(x, dtype), _attn_lens(lens)
+        tag = f"attn.bound[{dname},mode{mode},S{S},B{B},nh{nh},pre{int(pre)},lens{lens}]"
+        f = _attn_fwd(x, ops_in, sl)
+        for n in AR.FWD_OUT:
+            if n == "corr" and mode != 2:
+                continue
+            rs.append(_bounded(f"{tag}.{n}", f[n].reshape(ref[n].shape), ref[n], ref[n + "_bound"]))
+        if chained:
+            got, gap = _attn_bwd(x, ops_in, sl, f["o"], f["o_soft"], f["lse"], f["corr"], tag)
+        else:
+            got, gap = _attn_bwd(x, ops_in, sl, *_attn_fed(x, AR.fed(ref, x), dtype), tag)
+        sfx = "_bound_chained" if chained else "_bound"
+        rs += [_bounded(f"{tag}.{n}{'.chained' if chained else ''}", got[n], ref[n], ref[n + sfx]) for n in AR.BWD_OUT] + [gap]
+    return rs
+
+
+def check_attention_exact(dtype, S, mode, nh=2):
+    """The exact selections of attn_ref.exact_case, plain and with lengths, pre-scaled or not: o, o_soft, corr equal to the one right answer (lse: 0
+    where one key is selected, under its bound elsewhere), padded rows exactly zero; with one key per query and the backward fed lse = 0 and the
+    exact o: delta, dq = dk = 0 and dv exact, and tav_attn_probs exact."""
+    dname = _GDT[dtype]
+    rs = []
+    for pre in (False, True):
+        for lens in (None, _ALENS_EXACT[S]):
+            for single in (False, True):
+                B = 2 if lens is None else len(lens)
+                x = AR.exact_case(B, S, nh, dname, mode, pre, lens=lens, single=single)
+                assert AR.exact_ok(x)
+                w = AR.exact_want(x)
+                ops_in, sl = _attn_operands(x, dtype), _attn_lens(lens)
+                tag = f"attn.exact[{dname},mode{mode},S{S},pre{int(pre)},lens{lens},single{int(single)}]"
+                want = lambda n, dt_=dtype: torch.from_numpy(w[n]).to(DEV).to(dt_)      # noqa: E731
+                f = _attn_fwd(x, ops_in, sl)
+                rs += [_exact(f"{tag}.o", f["o"].reshape(B, S, nh, 64), want("o")), _exact(f"{tag}.o_soft", f["o_soft"].reshape(B, S, nh, 64), want("o_soft"))]
+                if mode == 2:
+                    rs.append(_exact(f"{tag}.corr", f["corr"], want("corr", torch.float32)))
+                one = torch.from_numpy(~np.isnan(w["lse"])).to(DEV)
+                rs.append(_exact(f"{tag}.lse where l = 1", torch.where(one, f["lse"], torch.zeros_like(f["lse"])), torch.zeros_like(f["lse"])))
+                rs.append(_bounded(f"{tag}.lse", f["lse"], w["lse_full"], AR.attn_ref(x)["lse_bound"]))
+                if not single:
+                    continue
+                zero_lse = _in(torch.zeros(B, nh, S, device=DEV))
+                o_fed = _in(want("o").reshape(B * S, nh * 64))
+                os_fed = _in(want("o_soft").reshape(B * S, nh * 64))
+                got, gap = _attn_bwd(x, ops_in, sl, o_fed, os_fed, zero_lse, _in(want("corr", torch.float32)), tag)
+                rs += [_exact(f"{tag}.{n}", got[n], want(n)) for n in ("dq", "dk", "dv")] + [_exact(f"{tag}.delta", got["delta"], want("delta", torch.float32)), gap]
+                if lens is None:
+                    q, k, _, _, mask = ops_in
+                    pr = ops.attn_probs(q, k, zero_lse, B, S, nh, key_mask=mask, mask_mode=mode, q_prescaled=pre)
+                    rs.append(_exact(f"{tag}.probs", pr, want("probs", torch.float32)))
+    return rs
+
+
+def check_attn_probs_bounded(dtype, S, B=2, nh=3):
+    """tav_attn_probs fed the reference's lse: every element within its bound (entries under a mode-1 mask: bound 0, exactly zero), without and
+    with head factors of spread magnitude in both layouts."""
+    dname = _GDT[dtype]
+    rs = []
+    rng = np.random.default_rng(S)
+    for mode in (0, 1, 2):
+        for pre in (False, True):
+            x = AR.make_inputs(B, S, nh, dname, seed=12, **AR.bound_config(S, mode, pre))
+            ref = AR.attn_ref(x)
+            q, k, _, _, mask = _attn_operands(x, dtype)
+            lse = _in(torch.from_numpy(ref["lse"]).to(DEV).float())
+            for name, hs in (("none", None), ("[nh]", rng.standard_normal(nh) * 2.0 ** (3 * np.arange(nh) - 3)),
+                             ("[B,nh]", rng.standard_normal((B, nh)) * 2.0 ** (3 * np.arange(nh) - 3))):
+                hs_t = None if hs is None else _in(torch.from_numpy(hs).to(DEV).float())
+                want, bound = AR.probs_ref(x, ref, None if hs is None else hs_t.double().cpu().numpy())
+                got = ops.attn_probs(q, k, lse, B, S, nh, key_mask=mask, mask_mode=mode, q_prescaled=pre, head_scale=hs_t)
+                rs.append(_bounded(f"attn_probs.bound[{dname},S{S},mode{mode},pre{int(pre)},hs{name}]", got, want, bound))
+    return rs
+
+
+def check_head_scale_bounded(dtype, B=2, S=37, nh=3):
+    """tav_head_scale, out = a + (c0 + hs[b, h]) * b with head factors of spread magnitude: every element within two f32 roundings and the store."""
+    dname = _GDT[dtype]
+    rng = np.random.default_rng(37)
+    H = nh * 64
+    a = GR.round_to(rng.standard_normal((B * S, nh, 64)) * AR.v_scale(), dname)[0]
+    b = GR.round_to(rng.standard_normal((B * S, nh, 64)) * AR.do_scale(), dname)[0]
+    rs = []
+    for name, hs in (("[nh]", rng.standard_normal(nh) * 2.0 ** (3 * np.arange(nh) - 3)), ("[B,nh]", rng.standard_normal((B, nh)) * 2.0 ** (3 * np.arange(nh) - 3))):
+        hs_t = _in(torch.from_numpy(hs).to(DEV).float())
+        for use_a in (False, True):
+            for c0 in (-1.0, 1.0):
+                f = np.broadcast_to((np.float32(c0) + hs_t.cpu().numpy().reshape(-1, nh)).astype(np.float64), (B, nh)).repeat(S, 0)
+                want, bound = AR.head_scale_ref(a if use_a else None, b, f, dname)
+                at = _in(torch.from_numpy(a.reshape(B * S, H)).to(DEV).to(dtype), 8) if use_a else None
+                bt = _in(torch.from_numpy(b.reshape(B * S, H)).to(DEV).to(dtype), 16)
+                wide = _blank((B * S, H + 16), dtype)
+                out = ops.head_scale(at, bt, hs_t, c0, B, S, nh, out=wide[:, 8:8 + H])
+                tag = f"head_scale.bound[{dname},a{int(use_a)},hs{name},c0{c0:g}]"
+                rs += [_bounded(tag, out.reshape(B * S, nh, 64), want, bound), _all_ff(tag + ".gap", wide[:, :8], wide[:, 8 + H:])]
+    return rs
+
+
+def attention_fp64_checks():
+    """The attention cases against fp64, in the order all_checks() appends them."""
+    out = []
+    for dtype in (torch.float32, torch.bfloat16):
+        for S in AR.BOUND_S:
+            out.append(lambda d=dtype, s=S: check_attention_bounded(d, s))
+        for S, lens_list in AR.LEN_CASES.items():
+            for lens in lens_list:
+                out.append(lambda d=dtype, s=S, ln=lens: check_attention_bounded(d, s, lens=list(ln), nh=2))
+        out.append(lambda d=dtype: check_attention_bounded(d, AR.CHAINED_S, chained=True))
+        for S in AR.EXACT_S:
+            for mode in (0, 1, 2):
+                out.append(lambda d=dtype, s=S, m=mode: check_attention_exact(d, s, m))
+        for S in (1, 65, 193):
+            out.append(lambda d=dtype, s=S: check_attn_probs_bounded(d, s))
+        out.append(lambda d=dtype: check_head_scale_bounded(d))
+    return out
+
+
 def all_checks():
     out = []
     for dtype in (torch.float32, torch.bfloat16):
@@ -2201,4 +2376,6 @@ def all_checks():
     out += step_end_checks()
     # the GEMM family against fp64: per-element bounds and exact integer operands
     out += gemm_fp64_checks()
+    # the attention family against fp64: per-element bounds, exact selections, isolated and chained backward, the two helper kernels
+    out += attention_fp64_checks()
     return out
