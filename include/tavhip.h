@@ -347,6 +347,31 @@ int tav_tanh_bwd(const float* y, const float* dy, float* dx, int64_t n, void* st
 int tav_cross_entropy(const float* logits, const int64_t* target, const float* class_weight /*opt*/, float* loss, float* dlogits,
                       int64_t B, int64_t C, float grad_scale, void* stream);
 
+/* Per-step statistics of a training / validation loop, kept on the device so that the host need not read anything back per step.
+ * The loop accumulator: 64 bytes, 8-byte aligned, zero-initialised except first_bad_step = -1.  The layout is part of the ABI. */
+typedef struct tav_loop_acc {
+    double loss_sum;        /* += (double)*loss, one add per call: equals the host's `total += loss.item()` bit for bit */
+    int64_t steps;          /* calls                                                                              */
+    int64_t rows;           /* sum of B                                                                           */
+    int64_t nonfinite;      /* calls whose *loss was NaN or +-inf (the value is added to loss_sum all the same)   */
+    int64_t bad_rows;       /* rows whose target or pred lay outside [0, C)                                       */
+    int32_t status;         /* OR of every *status seen (the word tav_ragged_lens leaves)                         */
+    int32_t first_bad_step; /* value of `steps` (before this call's increment) at the first non-zero *status; -1 until then */
+    int64_t reserved[2];    /* zero                                                                               */
+} tav_loop_acc;
+/* One workgroup.  Exactly one of `logits` (f32 [B, C], row-major, dense) and `preds` (int64 [B]) is given; target is int64 [B];
+ * 1 <= B <= INT32_MAX, 1 <= C <= 64 (tav_cross_entropy's limit).  pred of a logits row = torch.argmax's choice: the first index of the
+ * maximal value, where a NaN counts as greater than everything (so the first NaN wins).
+ *   cm  (optional, int64 [C * C]): cm[target * C + pred] += 1 for every row with both in [0, C); other rows touch no bin and are counted
+ *       in acc->bad_rows.  The bins are built in an LDS histogram and added to cm with plain loads and stores: launches on ONE stream are
+ *       ordered, so no global atomic is needed -- concurrent launches into one cm (or one acc) from different streams are NOT supported.
+ *   acc (optional): updated as described at tav_loop_acc; `loss` (f32 scalar) and `status` (int32 scalar) are optional DEVICE pointers read
+ *       when the kernel runs, and are ignored without acc.
+ * At least one of cm / acc is required.  TAV_ERR_NULL: target missing, neither or both of logits / preds, neither cm nor acc.
+ * TAV_ERR_SHAPE: B or C out of range. */
+int tav_step_stats(const float* logits, const int64_t* preds, const int64_t* target, int64_t* cm, const float* loss, const int32_t* status,
+                   tav_loop_acc* acc, int64_t B, int64_t C, void* stream);
+
 /* dropout with a counter-based RNG (models/tav.py:497-498): y = x * keep / (1-p); mask bytes saved for backward */
 int tav_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream);
 /* v7: tav_dropout_fwd with the seed read from DEVICE memory (*seed_state, one uint64 word) when the kernel runs -- bit-identical to

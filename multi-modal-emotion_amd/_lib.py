@@ -127,6 +127,7 @@ _SIGS = {
     "tav_tanh_fwd": (C.c_int, [vp, vp, i64, vp]),
     "tav_tanh_bwd": (C.c_int, [vp, vp, vp, i64, vp]),
     "tav_cross_entropy": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, f32, vp]),
+    "tav_step_stats": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),
     "tav_dropout_fwd": (C.c_int, [vp, vp, vp, i64, f32, C.c_uint64, C.c_uint64, vp]),
     "tav_dropout_fwd_dev": (C.c_int, [vp, vp, vp, i64, f32, vp, C.c_uint64, vp]),
     "tav_dropout_bwd": (C.c_int, [vp, vp, vp, i64, f32, vp]),

@@ -502,6 +502,64 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
         }
 }
 
+// single workgroup, one lane per row (C <= 64): confusion-matrix bins in an LDS histogram (ds_add_u32), then plain 64-bit adds into cm --
+// launches on one stream are ordered and there is one workgroup, so nothing here needs a global atomic.  Lane 0 updates the loop accumulator.
+__global__ __launch_bounds__(256) void step_stats_kernel(const float* __restrict__ logits, const int64_t* __restrict__ preds,
+                                                         const int64_t* __restrict__ target, int64_t* __restrict__ cm,
+                                                         const float* __restrict__ loss, const int32_t* __restrict__ status,
+                                                         tav_loop_acc* __restrict__ acc, int Bn, int C) {
+    __shared__ unsigned s_bins[64 * 64];
+    __shared__ unsigned s_bad;
+    const int nbins = C * C;
+    if (cm)
+        for (int i = threadIdx.x; i < nbins; i += 256) s_bins[i] = 0u;
+    if (threadIdx.x == 0) s_bad = 0u;
+    __syncthreads();
+    for (long r = threadIdx.x; r < Bn; r += 256) {
+        const long t = (long)target[r];
+        long p;
+        if (logits) {
+            // torch.argmax: first index of the maximum, NaN greater than everything (once the best is a NaN nothing replaces it)
+            const float* z = logits + r * C;
+            float best = z[0];
+            int bi = 0;
+            for (int c = 1; c < C; ++c) {
+                const float v = z[c];
+                if (best == best && (v != v || v > best)) { best = v; bi = c; }
+            }
+            p = bi;
+        } else {
+            p = (long)preds[r];
+        }
+        if (t < 0 || t >= C || p < 0 || p >= C) atomicAdd(&s_bad, 1u);
+        else if (cm) atomicAdd(&s_bins[(int)t * C + (int)p], 1u);
+    }
+    __syncthreads();
+    if (cm)
+        for (int i = threadIdx.x; i < nbins; i += 256) {
+            const unsigned n = s_bins[i];
+            if (n) cm[i] += (int64_t)n;
+        }
+    if (acc && threadIdx.x == 0) {
+        const int64_t step = acc->steps;
+        if (loss) {
+            const float l = loss[0];
+            acc->loss_sum += (double)l;
+            if ((__float_as_uint(l) & 0x7f800000u) == 0x7f800000u) acc->nonfinite += 1;
+        }
+        acc->steps = step + 1;
+        acc->rows += (int64_t)Bn;
+        acc->bad_rows += (int64_t)s_bad;
+        if (status) {
+            const int32_t w = status[0];
+            if (w) {
+                if (acc->first_bad_step < 0) acc->first_bad_step = (int32_t)(step < INT32_MAX ? step : INT32_MAX);
+                acc->status |= w;
+            }
+        }
+    }
+}
+
 TAV_DEV void dropout_one(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, long i, float p, uint64_t seed, uint64_t offset) {
     const uint64_t r = mix64(seed ^ mix64(offset + (uint64_t)i));
     const float u = (float)(r >> 40) * (1.f / 16777216.f);
@@ -923,6 +981,13 @@ extern "C" int tav_cross_entropy(const float* logits, const int64_t* target, con
     if (!logits || !target || (!loss && !dlogits)) return TAV_ERR_NULL;
     if (B <= 0 || C <= 0 || C > 64) return TAV_ERR_SHAPE;
     hipLaunchKernelGGL(cross_entropy_kernel, dim3(1), dim3(256), 0, ST, logits, target, cw, loss, dlogits, (int)B, (int)C, grad_scale);
+    return tav_last_error();
+}
+extern "C" int tav_step_stats(const float* logits, const int64_t* preds, const int64_t* target, int64_t* cm, const float* loss,
+                              const int32_t* status, tav_loop_acc* acc, int64_t B, int64_t C, void* stream) {
+    if (!target || (!logits) == (!preds) || (!cm && !acc)) return TAV_ERR_NULL;
+    if (B <= 0 || B > INT32_MAX || C <= 0 || C > 64) return TAV_ERR_SHAPE;
+    hipLaunchKernelGGL(step_stats_kernel, dim3(1), dim3(256), 0, ST, logits, preds, target, cm, loss, status, acc, (int)B, (int)C);
     return tav_last_error();
 }
 extern "C" int tav_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream) {

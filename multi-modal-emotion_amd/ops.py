@@ -721,6 +721,66 @@ def cross_entropy(logits, target, class_weight=None, grad_scale=1.0, want_grad=T
     return loss, dlog
 
 
+LOOP_ACC_WORDS = 8                               # tav_loop_acc as int64 words
+_ACC_UNSET = -(1 << 32)                          # word 5 = (status = 0, first_bad_step = -1), little endian
+
+
+def _stats_arg(name, t, dtype, numel=None):
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError(f"step_stats: {name} must be a tensor on the GPU (the kernel has no host form)")
+    if t.dtype != dtype or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise ValueError(f"step_stats: {name} must be contiguous {dtype}" + (f" with {numel} element(s)" if numel is not None else "")
+                         + f", got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def step_stats(logits=None, preds=None, target=None, cm=None, loss=None, status=None, acc=None, num_classes=None):
+    """One launch of tav_step_stats on the current stream; nothing is read back.  Exactly one of logits (f32 [B, C]) / preds (int64 [B]);
+    target int64 [B].  cm (int64, C * C elements) gets cm[target, pred] += 1 for the rows inside [0, C); acc (loop_acc_new) gets the loss
+    scalar, the status word, the row and out-of-range counts.  The number of classes comes from logits, else from cm, else num_classes."""
+    if target is None:
+        raise ValueError("step_stats: target is required")
+    _stats_arg("target", target, torch.int64)
+    B = target.numel()
+    if logits is not None:
+        _stats_arg("logits", logits, torch.float32)
+        if logits.dim() != 2 or logits.shape[0] != B:
+            raise ValueError(f"step_stats: logits {tuple(logits.shape)} do not match {B} targets")
+        Cn = logits.shape[1]
+    else:
+        Cn = num_classes if num_classes is not None else (int(round(cm.numel() ** 0.5)) if cm is not None else 0)
+    if preds is not None:
+        _stats_arg("preds", preds, torch.int64, B)
+    _stats_arg("cm", cm, torch.int64, Cn * Cn)
+    _stats_arg("loss", loss, torch.float32, 1)
+    _stats_arg("status", status, torch.int32, 1)
+    _stats_arg("acc", acc, torch.int64, LOOP_ACC_WORDS)
+    check(lib().tav_step_stats(ptr(logits), ptr(preds), ptr(target), ptr(cm), ptr(loss), ptr(status), ptr(acc), B, Cn, stream()), "step_stats")
+
+
+def loop_acc_new(device):
+    """A zeroed tav_loop_acc (first_bad_step = -1) on `device`, as 8 int64 words."""
+    acc = torch.zeros(LOOP_ACC_WORDS, dtype=torch.int64, device=device)
+    acc[5:6].fill_(_ACC_UNSET)
+    return acc
+
+
+def loop_acc_reset(acc):
+    """Back to loop_acc_new's state: two fills on the current stream, no host read."""
+    acc.zero_()
+    acc[5:6].fill_(_ACC_UNSET)
+
+
+def loop_acc_read(acc):
+    """-> dict of the accumulator's fields.  The single device-to-host copy of the sync-free loop, and the only place that synchronises."""
+    words = acc.cpu().numpy()
+    i32 = words.view("int32")
+    return dict(loss_sum=float(words.view("float64")[0]), steps=int(words[1]), rows=int(words[2]), nonfinite=int(words[3]), bad_rows=int(words[4]),
+                status=int(i32[10]), first_bad_step=int(i32[11]))
+
+
 def dropout_fwd(x, p, seed, offset):
     """seed: an int (passed by value), or a one-word int64 device tensor that the kernel reads when it runs (runtime.dropout_seeds under a
     hipGraph capture: the host rewrites the word before every replay)."""

@@ -41,7 +41,8 @@ def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
         criterion = CrossEntropyLoss()
     else:
         criterion = NewCrossEntropyLoss(class_weights=param_dict["weights"].to(device), epoch_switch=param_dict["epoch_switch"])
-    Metric = Metrics(num_classes=model_param["output_dim"], id2label=param_dict["id2label"], rank=device)
+    sync = param_dict.get("loop_sync", "step")
+    Metric = Metrics(num_classes=model_param["output_dim"], id2label=param_dict["id2label"], rank=device, on_device=sync == "log")
     bs, lt, es = param_dict["batch_size"], param_dict["label_task"], param_dict["epoch_switch"]
     dl_train = prepare_dataloader(df_train, bs, lt, es, check="train")
     dl_val = prepare_dataloader(df_val, bs, lt, es, check="val")
@@ -50,8 +51,8 @@ def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
     PREFormer = PreFormer().to(device)
     model, PREFormer = train_tav_network(model, PREFormer, dl_train, dl_val, criterion, param_dict["lr"], param_dict["epoch"], param_dict["weight_decay"],
                                          param_dict["T_max"], Metric, param_dict["patience"], param_dict["clip"], es, None,
-                                         graphs=bool(param_dict.get("graph", 0)))
-    evaluate_tav(model, PREFormer, dl_test, Metric)
+                                         graphs=bool(param_dict.get("graph", 0)), sync=sync)
+    evaluate_tav(model, PREFormer, dl_test, Metric, sync=sync)
     return model, PREFormer
 
 
@@ -69,7 +70,7 @@ def main(argv=None):
     param_dict = {"epoch": args.epoch, "patience": args.patience, "lr": args.learning_rate, "clip": args.clip, "batch_size": args.batch_size,
                   "weight_decay": args.weight_decay, "model": args.model, "T_max": args.T_max, "seed": args.seed, "label_task": args.label_task,
                   "mask": args.mask, "loss": args.loss, "beta": args.beta, "epoch_switch": args.epoch_switch, "weights": weights,
-                  "label2id": {v: k for k, v in id2label.items()}, "id2label": id2label, "graph": args.graph}
+                  "label2id": {v: k for k, v in id2label.items()}, "id2label": id2label, "graph": args.graph, "loop_sync": args.loop_sync}
     model_param = {"output_dim": args.output_dim, "dropout": args.dropout, "early_div": args.early_div, "num_layers": args.num_layers,
                    "learn_PosEmbeddings": args.learn_PosEmbeddings}
     small = cfg["video"]["image"] != 224

@@ -8,7 +8,13 @@ length (grad_accum) as a multiplication by a device scalar, backward and TrainSt
     words (fill kernels: the value is a kernel argument, no host staging buffer can be overwritten before the device read it);
   * the dropout sites advance their call counters and write the seeds of this replay's draws (runtime.capture.replay);
   * the weight-cast cache is told the parameters moved (engine.bump_weight_epoch), so an eager validate() re-casts;
-  * metrics and the running loss are taken from the static logits / loss -- one host sync per step, the reference's per-batch loss.item().
+  * metrics and the running loss are taken from the static logits / loss.  With sync="step" (the default) that is a host sync per step,
+    the reference's per-batch loss.item() (plus the read of the ragged status word and the metrics' copy of predictions and labels).  With
+    sync="log" it is one ordinary ops.step_stats launch after the replay -- not part of the capture -- that adds the loss to the loop's
+    device accumulator, ORs in the status word and counts the predictions into the on-device Metrics' matrix: the host reads nothing
+    until the loop logs, so it may run ahead of the device by as many replays as the runtime queues.  (A batch whose video mask lives on
+    the device and comes without `n_visual_true` still costs _visual_counts one host read, remembered per tensor: hand the counts over
+    with the batch.)
 A batch whose signature (input shapes and dtypes, video tokens per row, loss branch, loop kind) has not been seen in this epoch runs the
 eager step -- the same code as graphs=False -- and is then captured (at most `max_graphs` per epoch; later new signatures stay eager).
 Ragged video rows: without a bucket a batch of unequal rows has no signature and stays eager.  With runtime.set_visual_rows("ragged", bucket=g)
@@ -118,25 +124,35 @@ class GraphedSteps:
         return (shapes, (tuple(label.shape), label.dtype), nv, "train", branch, bool(accum), runtime.specaugment())
 
     # ---- one training step
-    def step(self, input, label, epoch, Metric, accum_iter=None):
-        """-> the batch loss as a float (what the loops add to total_loss_train).  accum_iter: grad_accum's divisor, None in not_grad_accum."""
+    def step(self, input, label, epoch, Metric, accum_iter=None, sync=None):
+        """-> the batch loss as a float (what the loops add to total_loss_train).  accum_iter: grad_accum's divisor, None in not_grad_accum.
+        sync: the loop's tav_train.LogSync -- loss, status word and metrics go to the device accumulator instead, nothing is read and the
+        result is None."""
         if self.stepper.opt.generation != self._generation:
             self.invalidate()                    # optimizer state reloaded: captured pointer tables are stale
         sig = self.signature(input, label, epoch, accum_iter is not None)
         g = self.graphs.get(sig) if sig is not None else None
+        kw = {} if sync is None else {"sync": sync}
         if g is not None:
-            return self._replay(g, input, label, Metric, accum_iter)
-        v = self._eager(input, label, epoch, Metric, accum_iter)
+            return self._replay(g, input, label, Metric, accum_iter, **kw)
+        v = self._eager(input, label, epoch, Metric, accum_iter, **kw)
         if sig is not None and len(self.graphs) < self.max_graphs:
             self.graphs[sig] = self._capture(input, label, epoch, accum_iter is not None, sig[2])
             self.captures += 1
         return v
 
-    def _eager(self, input, label, epoch, Metric, accum_iter):
+    def _eager(self, input, label, epoch, Metric, accum_iter, sync=None):
         """Exactly the eager loop's step (tav_train.not_grad_accum / grad_accum without a reducer)."""
         st = self.stepper
         # (at a bucketed capacity the counts signature() already has go along: the step pads as the eager loop does, without a second host read)
         kw = {"n_visual_true": self._visual_counts(input)} if runtime.visual_bucket() else {}
+        if sync is not None:
+            loss = T.recorded_loss(sync.train, input, label, st.model, st.pre, st.criterion, Metric, check="train", epoch=epoch,
+                                   divide_by=accum_iter, **kw)
+            loss.backward()
+            st.update()
+            self.eager_steps += 1
+            return None
         loss = T.get_statistics(input, label, st.model, st.pre, st.criterion, Metric, check="train", epoch=epoch, **kw)
         if accum_iter is not None:
             loss = loss / accum_iter
@@ -147,13 +163,18 @@ class GraphedSteps:
         self.eager_steps += 1
         return v
 
-    def _replay(self, g, input, label, Metric, accum_iter):
+    def _replay(self, g, input, label, Metric, accum_iter, sync=None):
         g.feed(input, label)
         if accum_iter is not None:
             g.set_scale(_recip32(accum_iter))
         self.stepper.opt.sync_lr()               # the scheduler moved opt.lr after the last step; the replay reads the device copy
         g.replay()                               # (advances the dropout counters and writes this replay's seeds first)
         engine.bump_weight_epoch()               # the replayed AdamW moved the weights behind the cast cache's back
+        if sync is not None:
+            # an ordinary launch behind the replay, on the same stream: g.loss is the captured step's loss (already times the scale)
+            sync.record(sync.train, Metric, g.logits, g.label, g.loss, getattr(g, "status", None))
+            self.replays += 1
+            return None
         if Metric is not None:
             Metric.update_metrics(torch.argmax(g.logits, dim=1), g.label)
         self.replays += 1
@@ -202,7 +223,7 @@ class GraphedSteps:
         self._generation = self.stepper.opt.generation
 
 
-def run_graphed(train_epochs, stepper, model, PREFormer, *args, max_graphs=2):
+def run_graphed(train_epochs, stepper, model, PREFormer, *args, max_graphs=2, sync="step"):
     """train_tav_network's epochs in graph mode: warm-up, captures, replays, eager fallbacks and validate() all run on ONE side stream (autograd
     ties each parameter's gradient accumulation to the stream of its first backward, and a capture cannot use the legacy default stream)."""
     graphs = GraphedSteps(stepper, max_graphs=max_graphs)
@@ -211,7 +232,7 @@ def run_graphed(train_epochs, stepper, model, PREFormer, *args, max_graphs=2):
     work.wait_stream(caller)
     try:
         with torch.cuda.stream(work):
-            return train_epochs(stepper, model, PREFormer, *args, graphs=graphs)
+            return train_epochs(stepper, model, PREFormer, *args, graphs=graphs, sync=sync)
     finally:
         graphs.invalidate()
         caller.wait_stream(work)

@@ -12,6 +12,7 @@ import os
 import torch
 
 from .. import ddp as tav_ddp
+from .. import ops
 from ..optim import FusedAdamW
 from ..utils.global_functions import checkpoint_file, load_model, save_model
 
@@ -82,11 +83,71 @@ def _statistics(input, label, model, PREFormer, criterion, Metric, check="train"
                    n_visual_true=n_visual_true, **caps)
     label = label.to(device).long()          # (the reference's .type(torch.LongTensor) would bounce through the host)
     if Metric is not None:
-        Metric.update_metrics(torch.argmax(output, dim=1), label.long())
+        from_logits = getattr(Metric, "update_from_logits", None)
+        if from_logits is not None:
+            from_logits(output, label)               # (an on-device Metrics takes the argmax inside its counting kernel)
+        else:
+            Metric.update_metrics(torch.argmax(output, dim=1), label.long())
     batch_loss = None
     if criterion is not None:
         batch_loss = criterion(output, label, epoch=epoch if epoch is not None else 1)
     return batch_loss, output, label
+
+
+class LogSync:
+    """State of the loops' sync="log" mode: nothing is read from the device per step.  After every step one ops.step_stats launch on the
+    loop's stream adds the step's loss scalar to a device accumulator (a double: the sum equals the host's `total += loss.item()` bit for
+    bit), ORs in the ragged status word, and counts the step's predictions into the on-device Metrics' confusion matrix.  The loops read
+    the accumulator where they log: `train` lives for an epoch, `val` for one validate() call."""
+
+    def __init__(self, Metric, device=None):
+        if Metric is not None and not getattr(Metric, "on_device", False):
+            raise ValueError('sync="log" needs the confusion matrix on the device: build the metrics with Metrics(..., on_device=True) '
+                             '(a host-resident Metrics costs a device-to-host copy per step), or pass Metric=None')
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.train, self.val = ops.loop_acc_new(dev), ops.loop_acc_new(dev)
+
+    @staticmethod
+    def record(acc, Metric, logits, label, loss, status=None):
+        """The per-step launch: logits f32 [B, C] and label int64 [B] on the device, loss a one-element f32 tensor or None."""
+        ops.step_stats(logits=logits.detach(), target=label, cm=None if Metric is None else Metric.cm,
+                       loss=None if loss is None else loss.detach().reshape(1), status=status, acc=acc)
+
+    @staticmethod
+    def read(acc, what):
+        """The accumulator as a dict (the one host read of a logging window), after the checks the per-step reads made in "step" mode."""
+        r = ops.loop_acc_read(acc)
+        if r["status"]:
+            from ..models.tav import STATUS_TEXT
+            why = "; ".join(text for bit, text in STATUS_TEXT.items() if r["status"] & bit)
+            raise ValueError(f"ragged video rows exceed the batch's capacity (status {r['status']}): {why}; first seen at step "
+                             f"{r['first_bad_step']} of this {what} window")
+        if r["nonfinite"] or r["bad_rows"]:
+            print(f"{what}: {r['nonfinite']} of {r['steps']} steps had a non-finite loss, {r['bad_rows']} of {r['rows']} rows a label or "
+                  "prediction outside the classes", flush=True)
+        return r
+
+
+def _as_sync(sync, Metric):
+    """"step" -> None, "log" -> a new LogSync; a LogSync passes through (the loops hand theirs to validate)."""
+    if sync is None or isinstance(sync, LogSync):
+        return sync
+    if sync not in ("step", "log"):
+        raise ValueError(f'sync must be "step" or "log", got {sync!r}')
+    return LogSync(Metric) if sync == "log" else None
+
+
+def recorded_loss(acc, input, label, model, PREFormer, criterion, Metric, check="train", epoch=None, divide_by=None, **kw):
+    """get_statistics for sync="log": the forward with its loss (divided by `divide_by`, grad_accum's dialogue length), then the step_stats
+    launch in place of loss.item(), check_visual_rows() and the Metric update.  -> the loss tensor (None without a criterion)."""
+    loss, logits, lab = _statistics(input, label, model, PREFormer, criterion, None, check, epoch, **kw)
+    if loss is not None and divide_by is not None:
+        loss = loss / divide_by
+    status = getattr(model, "_visual_status", None)
+    if status is not None:
+        model._visual_status = None              # (consumed, as check_visual_status does)
+    LogSync.record(acc, Metric, logits, lab, loss, status)
+    return loss
 
 
 class TrainStep:
@@ -124,7 +185,17 @@ class TrainStep:
         return loss, self.update()
 
 
-def validate(val_dataloader, model, PREFormer, criterion, Metric, name="val"):
+def validate(val_dataloader, model, PREFormer, criterion, Metric, name="val", sync="step"):
+    """sync="log": no host read per batch; loss sum, status word and counts are read once, after the last batch."""
+    sync = _as_sync(sync, Metric)
+    if sync is not None:
+        ops.loop_acc_reset(sync.val)
+        with torch.no_grad():
+            for val_input, val_label in val_dataloader:
+                recorded_loss(sync.val, val_input, val_label, model, PREFormer, criterion, Metric, name, epoch=None)
+            total = LogSync.read(sync.val, name)["loss_sum"]
+            log(Metric, total / len(val_dataloader) if criterion is not None else 0, name)
+        return total / len(val_dataloader)
     total = 0.0
     with torch.no_grad():
         for val_input, val_label in val_dataloader:
@@ -151,12 +222,24 @@ def _save_if_better(val_loss, prev_val_loss, model, PREFormer, stepper, criterio
 
 
 def not_grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path=None,
-                   graphs=None):
-    """reference :52-83: one optimisation step per batch.  graphs: a graphed.GraphedSteps that takes the step instead (replays of a captured one)."""
+                   graphs=None, sync=None):
+    """reference :52-83: one optimisation step per batch.  graphs: a graphed.GraphedSteps that takes the step instead (replays of a captured one).
+    sync: a LogSync -- the loss sum lives in its `train` accumulator and is read where the loop logs, not after every step."""
     iters = len(train_dataloader)
     total_loss_train = 0.0
+    if sync is not None:
+        ops.loop_acc_reset(sync.train)
     for batch_idx, (train_input, train_label) in enumerate(train_dataloader):
-        if graphs is not None:
+        if sync is not None:
+            if graphs is not None:
+                graphs.step(train_input, train_label, epoch, Metric, sync=sync)
+            else:
+                loss = recorded_loss(sync.train, train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch)
+                loss.backward()
+                if stepper.reducer is not None:
+                    stepper.reducer.finish()
+                stepper.update()
+        elif graphs is not None:
             total_loss_train += graphs.step(train_input, train_label, epoch, Metric)
         else:
             loss = get_statistics(train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch)
@@ -168,8 +251,10 @@ def not_grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, cr
             stepper.update()
         scheduler.step(epoch + batch_idx / iters)
         if ((batch_idx + 1) % log_val == 0) or (batch_idx + 1 == iters):
+            if sync is not None:
+                total_loss_train = LogSync.read(sync.train, "train")["loss_sum"]
             log(Metric, total_loss_train / iters, "train")
-            val_loss = validate(val_dataloader, model, PREFormer, criterion, Metric, name="val")
+            val_loss = validate(val_dataloader, model, PREFormer, criterion, Metric, name="val", sync=sync)
             prev_val_loss, stop = _save_if_better(val_loss, prev_val_loss, model, PREFormer, stepper, criterion, scheduler, epoch, batch_idx, path, log_val, patience)
             if stop:
                 break
@@ -177,7 +262,7 @@ def not_grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, cr
 
 
 def grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path=None,
-               graphs=None):
+               graphs=None, sync=None):
     """reference :87-119, the dialogue-level variant used on epochs with epoch % epoch_switch != 0.  Kept with its quirk: the loss is
     divided by the dialogue length (`dataset.retGradAccum(i)` -> (accum_iter, accum_sum)) but the optimizer still steps -- and the
     gradients are zeroed -- after EVERY batch (:96-100), so the extra, unclipped `optimizer.step()` at a dialogue end (:102-106) runs on zeroed
@@ -189,12 +274,25 @@ def grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criter
         the parameters move along the remaining momentum (`TrainStep(zero_grad_like_torch_1_10=True)` /
         `train_tav_network(..., zero_grad_like_torch_1_10=True)`).
     Both readings are tested (tests/test_abi_and_host.py on the call sequence, tests/test_model_gpu.py against torch.optim.AdamW).
-    graphs: as in not_grad_accum; the division by the dialogue length is then a device scalar the replay reads."""
+    graphs: as in not_grad_accum; the division by the dialogue length is then a device scalar the replay reads.
+    sync: as in not_grad_accum; what is accumulated is the loss already divided by the dialogue length."""
     iters = len(train_dataloader)
     total_loss_train = 0.0
+    if sync is not None:
+        ops.loop_acc_reset(sync.train)
     for batch_idx, (train_input, train_label) in enumerate(train_dataloader):
         accum_iter, accum_sum = train_dataloader.dataset.retGradAccum(i=batch_idx)
-        if graphs is not None:
+        if sync is not None:
+            if graphs is not None:
+                graphs.step(train_input, train_label, epoch, Metric, accum_iter=accum_iter, sync=sync)
+            else:
+                loss = recorded_loss(sync.train, train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch,
+                                     divide_by=accum_iter)
+                loss.backward()
+                if stepper.reducer is not None:
+                    stepper.reducer.finish()
+                stepper.update()
+        elif graphs is not None:
             total_loss_train += graphs.step(train_input, train_label, epoch, Metric, accum_iter=accum_iter)
         else:
             loss = get_statistics(train_input, train_label, model, PREFormer, criterion, Metric, check="train", epoch=epoch) / accum_iter
@@ -209,8 +307,10 @@ def grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criter
             stepper.update(clip=False)           # reference :103: optimizer.step() without clip_grad_norm_; no-op or a momentum / decay step (docstring)
             scheduler.step(epoch + batch_idx / iters)
         if ((batch_idx + 1) % log_val == 0) or (batch_idx + 1 == iters):
+            if sync is not None:
+                total_loss_train = LogSync.read(sync.train, "train")["loss_sum"]
             log(Metric, total_loss_train / iters, "train")
-            val_loss = validate(val_dataloader, model, PREFormer, criterion, Metric, name="val")
+            val_loss = validate(val_dataloader, model, PREFormer, criterion, Metric, name="val", sync=sync)
             prev_val_loss, stop = _save_if_better(val_loss, prev_val_loss, model, PREFormer, stepper, criterion, scheduler, epoch, batch_idx, path, log_val, patience)
             if stop:
                 break
@@ -218,16 +318,18 @@ def grad_accum(epoch, train_dataloader, val_dataloader, model, PREFormer, criter
 
 
 def one_epoch(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, epoch_switch, patience, Metric, prev_val_loss,
-              path=None, log_val=2400, graphs=None):
+              path=None, log_val=2400, graphs=None, sync=None):
     """reference :133-144: alternate the two loops by epoch parity, then reload the best checkpoint of the run (:143).  graphs (graph mode): the
     epoch's captured steps are freed at its end -- the next epoch has the other loop and loss branch, and the reload replaces the optimizer's
     moment tensors that a captured step points at."""
     loop = not_grad_accum if (epoch % epoch_switch == 0 or not hasattr(train_dataloader.dataset, "retGradAccum")) else grad_accum
+    kw = {} if sync is None else {"sync": sync}
     if graphs is None:
-        prev_val_loss = loop(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path)
+        prev_val_loss = loop(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path,
+                             **kw)
     else:
         prev_val_loss = loop(epoch, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, patience, Metric, prev_val_loss, log_val, path,
-                             graphs=graphs)
+                             graphs=graphs, **kw)
         graphs.invalidate()
     if path is not None and os.path.exists(checkpoint_file(path)):
         load_model(model, PREFormer, stepper.opt, criterion, path)
@@ -235,21 +337,29 @@ def one_epoch(epoch, train_dataloader, val_dataloader, model, PREFormer, criteri
 
 
 def train_tav_network(model, PREFormer, train_dataloader, val_dataloader, criterion, learning_rate, epochs, weight_decay, T_max, Metric, patience, clip,
-                      epoch_switch, checkpoint=None, path=None, log_val=2400, zero_grad_like_torch_1_10=False, graphs=False):
+                      epoch_switch, checkpoint=None, path=None, log_val=2400, zero_grad_like_torch_1_10=False, graphs=False, sync="step"):
     """reference :147-164.  `path` (None = keep nothing on disk) replaces the cluster path hard-coded at :137; `checkpoint` is a loaded
     best.pt dict whose optimizer / scheduler state resumes the run (:152-155).  graphs=True: every training batch whose shapes match an
-    earlier one of the epoch replays a captured step (graphed.py; same results bit for bit); the whole run then executes on one side stream."""
+    earlier one of the epoch replays a captured step (graphed.py; same results bit for bit); the whole run then executes on one side stream.
+    sync="log" (needs Metrics(on_device=True) or Metric=None): the host reads nothing per step -- loss sum, ragged status word and confusion
+    matrix stay on the device (LogSync) and are read every log_val batches, at the end of an epoch and at the end of validate(); losses,
+    matrices, patience and best.pt decisions are the same numbers at the same places as with "step"."""
+    if sync not in ("step", "log"):
+        raise ValueError(f'sync must be "step" or "log", got {sync!r}')
+    if sync == "log" and Metric is not None and not getattr(Metric, "on_device", False):
+        LogSync(Metric)                          # raises: says to pass on_device=True
     stepper = TrainStep(model, PREFormer, criterion, lr=learning_rate, weight_decay=weight_decay, clip=clip, zero_grad_like_torch_1_10=zero_grad_like_torch_1_10)
     if graphs:
         from .graphed import run_graphed
         return run_graphed(_train_epochs, stepper, model, PREFormer, train_dataloader, val_dataloader, criterion, epochs, T_max, Metric, patience,
-                           epoch_switch, checkpoint, path, log_val)
+                           epoch_switch, checkpoint, path, log_val, sync=sync)
     return _train_epochs(stepper, model, PREFormer, train_dataloader, val_dataloader, criterion, epochs, T_max, Metric, patience, epoch_switch, checkpoint,
-                         path, log_val)
+                         path, log_val, sync=sync)
 
 
 def _train_epochs(stepper, model, PREFormer, train_dataloader, val_dataloader, criterion, epochs, T_max, Metric, patience, epoch_switch, checkpoint, path,
-                  log_val, graphs=None):
+                  log_val, graphs=None, sync="step"):
+    sync = _as_sync(sync, Metric)                # (built here: in graph mode this already runs on the loop's side stream)
     scheduler = CosineWarmRestarts(stepper.opt, T_0=T_max)
     prev_val_loss = 100
     if checkpoint is not None:
@@ -262,14 +372,14 @@ def _train_epochs(stepper, model, PREFormer, train_dataloader, val_dataloader, c
             wandb.log({"epoch": epoch_num, "learning_rate": scheduler.get_last_lr()[0]})
         stepper.opt.zero_grad()
         prev_val_loss = one_epoch(epoch_num, train_dataloader, val_dataloader, model, PREFormer, criterion, stepper, scheduler, epoch_switch, patience,
-                                  Metric, prev_val_loss, path, log_val, graphs=graphs)
+                                  Metric, prev_val_loss, path, log_val, graphs=graphs, sync=sync)
         if PATIENCE_ITER == patience:
             return model, PREFormer
     return model, PREFormer
 
 
-def evaluate_tav(model, PREFormer, test_dataloader, Metric):
-    validate(test_dataloader, model, PREFormer, None, Metric, name="test")
+def evaluate_tav(model, PREFormer, test_dataloader, Metric, sync="step"):
+    validate(test_dataloader, model, PREFormer, None, Metric, name="test", sync=sync)
 
 
 def log(Metric, loss, check="train"):

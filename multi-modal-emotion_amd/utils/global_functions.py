@@ -9,6 +9,7 @@ from torch import nn
 from torch.utils.data.sampler import Sampler
 
 from .. import engine as E
+from .. import ops
 
 
 class MySampler(Sampler):
@@ -111,21 +112,49 @@ def load_model(model, PREFormer, optimizer, criterion, path, remap=True):
 
 
 class Metrics:
-    """Confusion-matrix metrics (accuracy, macro/weighted F1, recall, precision) without torchmetrics."""
+    """Confusion-matrix metrics (accuracy, macro/weighted F1, recall, precision) without torchmetrics.
+    on_device=True keeps the matrix on `rank` (a GPU) and counts with ops.step_stats: updates and resets read nothing back, and
+    compute_scores copies the matrix to the host once.  Rows whose prediction or label lies outside [0, num_classes) are then left out
+    (the host form's bincount would raise or grow); a loop accumulator passed to ops.step_stats counts them."""
 
-    def __init__(self, num_classes, id2label=None, rank="cuda", **_):
+    def __init__(self, num_classes, id2label=None, rank="cuda", on_device=False, **_):
         self.num_classes = num_classes
         self.id2label = id2label or {i: str(i) for i in range(num_classes)}
-        self.cm = torch.zeros(num_classes, num_classes, dtype=torch.long)
+        self.on_device = bool(on_device)
+        if self.on_device:
+            if torch.device(rank).type != "cuda":
+                raise ValueError(f"Metrics(on_device=True) counts with a HIP kernel and needs a GPU device, got rank={rank!r}; "
+                                 "use on_device=False for a host-resident matrix")
+            if not 1 <= num_classes <= 64:
+                raise ValueError(f"Metrics(on_device=True) supports 1..64 classes, got {num_classes}")
+        self.cm = torch.zeros(num_classes, num_classes, dtype=torch.long, device=rank if self.on_device else None)
 
     def update_metrics(self, preds, target):
+        if self.on_device:
+            dev = self.cm.device
+            ops.step_stats(preds=preds.reshape(-1).to(dev, torch.long).contiguous(), target=target.reshape(-1).to(dev, torch.long).contiguous(),
+                           cm=self.cm)
+            return
         idx = (target.reshape(-1).long().cpu() * self.num_classes + preds.reshape(-1).long().cpu())
         self.cm += torch.bincount(idx, minlength=self.num_classes ** 2).view(self.num_classes, self.num_classes)
+
+    def update_from_logits(self, logits, target):
+        """update_metrics(argmax(logits, 1), target); on the device the argmax is part of the counting kernel."""
+        if self.on_device:
+            dev = self.cm.device
+            ops.step_stats(logits=logits.detach().to(dev, torch.float32).contiguous(), target=target.reshape(-1).to(dev, torch.long).contiguous(),
+                           cm=self.cm)
+            return
+        self.update_metrics(torch.argmax(logits, dim=1), target)
 
     def reset_metrics(self):
         self.cm.zero_()
 
     def compute_scores(self, name):
+        if self.on_device:
+            host = Metrics(self.num_classes, self.id2label)
+            host.cm = self.cm.cpu()              # the one copy; the arithmetic below is the host class's
+            return host.compute_scores(name)
         cm = self.cm.double()
         tp, sup, pred = cm.diag(), cm.sum(1), cm.sum(0)
         rec = tp / sup.clamp(min=1)
@@ -179,4 +208,7 @@ def arg_parse(description, argv=None):
                              "_compute_mask_indices on the host from numpy's generator, as the reference (training batches stay eager under --graph 1)")
     parser.add_argument("--graph", default=0, type=int, choices=[0, 1],
                         help="1: replay each training step from a captured hipGraph (tav_nn only; train_tav_network(graphs=True))")
+    parser.add_argument("--loop-sync", dest="loop_sync", default="step", choices=["step", "log"],
+                        help="step: the host reads the loss and the metrics after every step, as the reference; log: they stay on the device (one "
+                             "ops.step_stats launch per step) and are read where the loops log (tav_nn only; train_tav_network(sync='log'))")
     return parser.parse_args(argv)
