@@ -23,7 +23,8 @@
 extern "C" {
 #endif
 
-enum { TAV_F32 = 0, TAV_BF16 = 1, TAV_FP8 = 2 /* OCP e4m3, GEMM operands of tav_gemm_nt only */ };
+enum { TAV_F32 = 0, TAV_BF16 = 1, TAV_FP8 = 2 /* OCP e4m3, GEMM operands of tav_gemm_nt only */,
+       TAV_U8 = 3 /* decoded video frames, the source of tav_video_clip_transform only */ };
 enum {
     TAV_ERR_NULL = -1,  /* required pointer missing           */
     TAV_ERR_SHAPE = -2, /* size not supported by the kernel   */
@@ -305,6 +306,31 @@ int tav_scatter_add_rows(const float* d, const int64_t* idx, float* dtable, int6
  * only for the token indices keep_idx[B][nkeep] (int32, ascending = the rows `embeddings[~mask]` keeps). */
 int tav_patchify(const float* video, const int32_t* keep_idx, void* patches, int32_t dtype, int64_t B, int64_t F, int64_t H, int64_t W,
                  int64_t nkeep, void* stream);
+/* Video clip transform (additive to ABI v7; models/tav.py:51-121, videoMAE_features): decoded frames -> the clip tav_patchify reads, one launch
+ * per clip.  For output frame i, channel c:
+ *   frame[i] of src -> crop (top, left, h, w) -> bilinear to (mid_h, mid_w) [skipped when both are 0] -> bilinear to (out_h, out_w)
+ *   -> mirrored in x when hflip, in y when vflip -> y = v * scale[c] - shift[c]   (the normalisation, applied last: the weights sum to 1)
+ * Both resizes are torch's F.interpolate(mode="bilinear", align_corners=False) without antialias, with the source coordinate in exact
+ * integers: num = max(0, (2 o + 1) n_in - n_out), i0 = num / (2 n_out), i1 = min(i0 + 1, n_in - 1), lam = float(num - i0 2 n_out) / float(2 n_out);
+ * they are fused (4 x 4 source taps per output element at most), the intermediate image is never stored.  No reduction, no atomic.
+ * The struct is read on the HOST when the call is made and travels as kernel arguments; src and dst are device pointers.
+ * TAV_ERR_NULL: src, dst or x missing.  TAV_ERR_DTYPE: src_dtype neither TAV_U8 nor TAV_F32.  TAV_ERR_SHAPE: H, W, crop_h, crop_w, out_h,
+ * out_w (and mid_h, mid_w unless both are 0) outside 1..16384; T < 1; a negative stride; nf outside 1..32; a frame[i] outside [0, T); a crop
+ * rectangle that leaves the frame; exactly one of mid_h / mid_w zero.  The kernel clamps every index into the frame besides, as tav_patchify
+ * does: with the strides of a buffer that holds [T][H][W][3] elements it reads nothing outside it, and it writes the nf*3*out_h*out_w floats
+ * of dst and nothing else. */
+typedef struct {
+    int32_t src_dtype;                 /* TAV_U8 or TAV_F32 (holding 0..255) */
+    int32_t T, H, W;
+    int64_t sT, sH, sW, sC;            /* element strides: THWC (H*W*3, W*3, 3, 1), CTHW (H*W, W, 1, T*H*W) */
+    int32_t nf, frame[32];             /* source frame of each output frame */
+    int32_t crop_top, crop_left, crop_h, crop_w;   /* no crop: 0, 0, H, W */
+    int32_t mid_h, mid_w;              /* size after the first resize; 0, 0 = there is none */
+    int32_t out_h, out_w, hflip, vflip;
+    float scale[3], shift[3];          /* y = v * scale[c] - shift[c]; host: 1 / (255 std), mean / std in f32 */
+} tav_clip_xform;
+int tav_video_clip_transform(const void* src, float* dst /* [nf][3][out_h][out_w] */, const tav_clip_xform* x, void* stream);
+
 /* per row of mask [B][n] (uint8/bool; keep where mask == keep_value): write ascending indices [B][nkeep];
  * counts[B] receives the number found (host checks == nkeep when it wants to).  A row with fewer than nkeep kept tokens gets its
  * last kept index (0 if none) in the remaining slots and a row with more is truncated: keep_idx is always fully written with

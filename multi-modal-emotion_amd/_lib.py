@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TAV_LIB") or os.path.join(_HERE, "libtavhip.so")      # TAV_LIB: developer knob, A/B of two builds (tools/ab_build.sh)
 
-TAV_F32, TAV_BF16, TAV_FP8 = 0, 1, 2
+TAV_F32, TAV_BF16, TAV_FP8, TAV_U8 = 0, 1, 2, 3
 ABI_VERSION = 7
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -69,6 +69,13 @@ class TextEmbedArgs(C.Structure):
                 ("B", i64), ("S", i64), ("W", i64), ("vocab", i64), ("max_pos", i64), ("pad_id", i32), ("eps", f32)]
 
 
+class ClipXform(C.Structure):
+    _fields_ = [("src_dtype", i32), ("T", i32), ("H", i32), ("W", i32), ("sT", i64), ("sH", i64), ("sW", i64), ("sC", i64),
+                ("nf", i32), ("frame", i32 * 32), ("crop_top", i32), ("crop_left", i32), ("crop_h", i32), ("crop_w", i32),
+                ("mid_h", i32), ("mid_w", i32), ("out_h", i32), ("out_w", i32), ("hflip", i32), ("vflip", i32),
+                ("scale", f32 * 3), ("shift", f32 * 3)]
+
+
 _SIGS = {
     "tav_version": (C.c_int, []),
     "tav_error_string": (C.c_char_p, [C.c_int]),
@@ -116,6 +123,7 @@ _SIGS = {
     "tav_scatter_add_rows": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
     "tav_gather_rows": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
     "tav_patchify": (C.c_int, [vp, vp, vp, i32, i64, i64, i64, i64, i64, vp]),
+    "tav_video_clip_transform": (C.c_int, [vp, vp, C.POINTER(ClipXform), vp]),
     "tav_mask_to_index": (C.c_int, [vp, i32, vp, vp, i64, i64, i64, vp]),
     "tav_ragged_lens": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
     "tav_mean_pool_fwd": (C.c_int, [vp, vp, i64, i64, i64, vp]),

@@ -3,6 +3,7 @@
   PreFormer   reference models/tav.py:249-417   modality front-ends -> fused token sequence + masks
   TAVForMAE   reference models/tav.py:420-504   3 encoders + fusion encoder + 7-way head
   collate_batch  reference models/tav.py:174-246   (mask / pad logic only: file decoding is out of scope)
+  video_features_device  reference models/tav.py:51-121   decoded uint8 frames -> the normalised, resized clip, one HIP launch per clip
 
 Same constructor arguments, forward() signatures and state_dict keys.  `from_pretrained` checkpoints are not
 reachable offline, so sub-models are built from a geometry preset (config.py) and initialised randomly; load a
@@ -485,6 +486,78 @@ def remap_reference_keys(state_dict):
     return out
 
 
+SPEAKER_CROPS = {True: (120, 2, 245, 355), False: (120, 362, 245, 355)}          # (top, left, h, w), reference :86 (IEMOCAP: left / right speaker)
+
+
+def draw_clip_augmentation(speaker, check, generator=None):
+    """The random draws of the reference's video Compose (models/tav.py:76-115), in its order, from torch's global generator or `generator`:
+    torch.rand(1) when speaker is None (the RandomHorizontalFlip(p=0) placeholder draws although it never flips; in validation too), then,
+    for check == "train", randint(256, 321, (1,)) (RandomShortSideScale), rand(1) < 0.5 (horizontal flip) and rand(1) < 0.5 (vertical flip).
+    -> {"size": short-side target or None, "hflip": bool, "vflip": bool}."""
+    if speaker is None:
+        torch.rand(1, generator=generator)
+    if check != "train":
+        return {"size": None, "hflip": False, "vflip": False}
+    size = int(torch.randint(256, 321, (1,), generator=generator).item())
+    hflip = bool(torch.rand(1, generator=generator) < 0.5)
+    vflip = bool(torch.rand(1, generator=generator) < 0.5)
+    return {"size": size, "hflip": hflip, "vflip": vflip}
+
+
+def subsample_indices(T, num_frames):
+    """pytorchvideo's uniform_temporal_subsample, literally: an f32 linspace, truncated."""
+    return torch.clamp(torch.linspace(0, T - 1, num_frames), 0, T - 1).long()
+
+
+def short_side_size(h, w, size):
+    """pytorchvideo's short_side_scale: the shorter side becomes `size`, the longer one floor(long / short * size)."""
+    if w < h:
+        return int(np.floor(float(h) / w * size)), size
+    return size, int(np.floor(float(w) / h * size))
+
+
+def video_features_device(frames, speaker, check, out=None, device="cuda", generator=None, num_frames=16, size=224, layout=None,
+                          augmentation=None):
+    """videoMAE_features (reference models/tav.py:51-121) after the decoder, on the device: frames are uint8 [T, H, W, 3] or uint8 / float32
+    [3, T, H, W] holding 0..255, on the host or on the device.  Temporal subsample, /255, normalise, speaker crop (None: none; truthy /
+    falsy: SPEAKER_CROPS), and for check == "train" RandomShortSideScale(256, 320), Resize((size, size)) and the two random flips, otherwise
+    one Resize -- all in ONE HIP launch (ops.video_clip_transform) that writes `out` (f32 [num_frames, 3, size, size], e.g. a slab of the
+    batch tensor; allocated when None).  Host frames are reduced to the selected frames first and shipped once, from pinned memory,
+    non-blocking.  The draws are draw_clip_augmentation's, or `augmentation` (a dict like the one it returns; nothing is drawn then).  There is
+    no host form: without a GPU this raises."""
+    frames = torch.as_tensor(frames)
+    lay = ops.clip_layout(frames, layout)
+    tdim = 0 if lay == "THWC" else 1
+    T, H, W = frames.shape[:3] if lay == "THWC" else frames.shape[1:]
+    aug = draw_clip_augmentation(speaker, check, generator) if augmentation is None else augmentation
+    crop = None if speaker is None else SPEAKER_CROPS[bool(speaker)]
+    if crop is not None and (crop[0] + crop[2] > H or crop[1] + crop[3] > W):
+        raise ValueError(f"speaker crop (top, left, h, w) = {crop} does not lie inside {H} x {W} frames")
+    ch, cw = (H, W) if crop is None else crop[2:]
+    mid = None if aug["size"] is None else short_side_size(ch, cw, aug["size"])
+    idx = subsample_indices(T, num_frames)
+    if frames.is_cuda:
+        sel, which = frames, idx.tolist()
+    else:
+        dev = _dev(device)
+        shape = list(frames.shape)
+        shape[tdim] = num_frames
+        staged = torch.empty(shape, dtype=frames.dtype, pin_memory=True)
+        torch.index_select(frames, tdim, idx, out=staged)
+        sel, which = staged.to(dev, non_blocking=True), range(num_frames)
+    x = ops.clip_xform(sel, which, layout=lay, crop=crop, mid=mid, out_hw=(size, size), hflip=aug["hflip"], vflip=aug["vflip"])
+    return ops.video_clip_transform(sel, out, x)
+
+
+def _decoded_video(v):
+    """(frames, speaker) when a collate item's video entry is decoded frames -- a uint8 tensor or {"frames": ..., "speaker": ...} -- else None."""
+    if isinstance(v, dict):
+        return v["frames"], v.get("speaker")
+    if (isinstance(v, torch.Tensor) and v.dtype == torch.uint8) or (isinstance(v, np.ndarray) and v.dtype == np.uint8):
+        return v, None
+    return None
+
+
 def _draw_visual_mask(B, ntok):
     """reference :207-209: True w.p. 1/15 per token, drawn on the host (per-row counts Binomial(ntok, 1/15), unequal)."""
     m = torch.randint(-13, 2, (B, ntok))
@@ -508,6 +581,9 @@ def collate_batch(batch, check, visual_rows="equal", bucket=None):
         texts.append(torch.as_tensor(inp[0]["input_ids"]).reshape(-1))
         masks.append(torch.as_tensor(inp[0]["attention_mask"]).reshape(-1).float())
         speech.append(torch.as_tensor(inp[1]).float().reshape(-1))
+        if _decoded_video(inp[2]) is not None:
+            raise ValueError("collate_batch takes finished float clips: decoded uint8 frames are transformed by the HIP kernel only "
+                             "(there is no CPU fallback) -- use collate_batch_device")
         v = torch.as_tensor(inp[2]).float()
         vids.append(v if v.shape[1] == 3 else v.permute(1, 0, 2, 3))
         labels.append(label)
@@ -544,21 +620,30 @@ def sample_video_mask(B, ntok, n_true=None, device="cpu", generator=None):
     return torch.zeros(B, ntok, dtype=torch.bool, device=device).scatter_(1, idx, True)
 
 
-def collate_batch_device(batch, check, device="cuda", n_visual_true=None, generator=None, visual_rows="equal", bucket=None):
+def collate_batch_device(batch, check, device="cuda", n_visual_true=None, generator=None, visual_rows="equal", bucket=None,
+                         clip_generator=None, num_frames=16, size=224):
     """collate_batch with the tensor work on `device`: items are decoded utterances as for collate_batch; every
     tensor is shipped once (non-blocking) and padding, the audio length mask (reference :225-228) and the video token mask are built
     there, sync-free: nothing in the step reads them back (PreFormer / TAVForMAE take `n_visual_true` instead of counting).
     visual_rows="ragged": the video mask is drawn on the HOST as in collate_batch(visual_rows="ragged") and shipped; its per-row True
     counts come back as visual["n_visual_true"] (a list), to be passed on as n_visual_true -- known without a device read (the training
-    loops and graph mode pick them up from there).  bucket: as in collate_batch."""
+    loops and graph mode pick them up from there).  bucket: as in collate_batch.
+    Decoded items: the video entry may be uint8 frames ([T, H, W, 3] or [3, T, H, W]) or {"frames": ..., "speaker": ...} instead of a
+    finished float clip.  The [B, num_frames, 3, size, size] batch is then allocated once and video_features_device(frames, speaker, check)
+    fills each clip's slab with one launch (no stack copy), drawing its augmentation from torch's global CPU generator or clip_generator,
+    item by item in batch order, before any mask is drawn.  A batch is all decoded or all float."""
     runtime.check_visual_rows(visual_rows, bucket)
     texts, masks, speech, vids, labels = [], [], [], [], []
-    for (inp, label) in batch:
+    decoded = [_decoded_video(inp[2]) for (inp, _) in batch]
+    if any(d is not None for d in decoded) and not all(d is not None for d in decoded):
+        raise ValueError("collate_batch_device: a batch holds either decoded frames or finished float clips, not both")
+    for (inp, label), d in zip(batch, decoded):
         texts.append(torch.as_tensor(inp[0]["input_ids"]).reshape(-1))
         masks.append(torch.as_tensor(inp[0]["attention_mask"]).reshape(-1).float())
         speech.append(torch.as_tensor(inp[1]).float().reshape(-1))
-        v = torch.as_tensor(inp[2]).float()
-        vids.append(v if v.shape[1] == 3 else v.permute(1, 0, 2, 3))
+        if d is None:
+            v = torch.as_tensor(inp[2]).float()
+            vids.append(v if v.shape[1] == 3 else v.permute(1, 0, 2, 3))
         labels.append(float(label))
     B = len(labels)
     dev = torch.device(device)
@@ -566,7 +651,16 @@ def collate_batch_device(batch, check, device="cuda", n_visual_true=None, genera
     T = int(lens.max())
     audio = torch.nn.utils.rnn.pad_sequence([s.to(dev, non_blocking=True) for s in speech], batch_first=True)          # zero padding, reference :228
     amask = (torch.arange(T, device=dev)[None, :] < lens.to(dev, non_blocking=True)[:, None]).float()
-    video = torch.stack([v.to(dev, non_blocking=True) for v in vids])
+    if vids:
+        video = torch.stack([v.to(dev, non_blocking=True) for v in vids])
+    else:
+        if dev.type != "cuda":
+            raise ValueError(f"collate_batch_device(device={str(dev)!r}): decoded frames are transformed by the HIP kernel on the GPU only; "
+                             "there is no CPU fallback")
+        video = torch.empty(B, num_frames, 3, size, size, dtype=torch.float32, device=_dev(dev))
+        for b, (frames, speaker) in enumerate(decoded):
+            video_features_device(frames, speaker, check, out=video[b], device=video.device, generator=clip_generator, num_frames=num_frames,
+                                  size=size)
     ntok = (video.shape[1] // 2) * (video.shape[3] // 16) * (video.shape[4] // 16)
     visual = {"visual_embeds": video}
     if visual_rows == "ragged":

@@ -659,6 +659,69 @@ def patchify(video, keep_idx, dtype):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- video clip transform
+CLIP_MEAN, CLIP_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)          # reference models/tav.py:67-68
+
+
+def clip_layout(src, layout=None):
+    """Layout of decoded frames: "THWC" (uint8 [T, H, W, 3], a decoder's output) or "CTHW" ([3, T, H, W], pytorchvideo's get_clip).  f32 frames are CTHW; uint8 frames
+    are THWC unless only the first axis is 3.  `layout` overrides."""
+    if layout is None:
+        layout = "CTHW" if src.dtype != torch.uint8 or (src.shape[0] == 3 and src.shape[-1] != 3) else "THWC"
+    if layout not in ("THWC", "CTHW") or src.dim() != 4 or src.shape[3 if layout == "THWC" else 0] != 3:
+        raise ValueError(f"video frames: need uint8 [T, H, W, 3] or uint8 / float32 [3, T, H, W], got {tuple(src.shape)} {src.dtype} as {layout}")
+    return layout
+
+
+def clip_xform(src, frames, *, layout=None, crop=None, mid=None, out_hw=(224, 224), hflip=False, vflip=False, mean=CLIP_MEAN, std=CLIP_STD):
+    """The tav_clip_xform of one clip: src's sizes and strides, the source frame of every output frame, crop (top, left, h, w) or None, the
+    size after the first resize (mid_h, mid_w) or None, the output size, the flips, and y = v * scale[c] - shift[c] with
+    scale = 1 / (255 std) and shift = mean / std rounded to f32 (mean = 0, std = 1 / 255 leaves the raw value)."""
+    layout = clip_layout(src, layout)
+    if src.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"video frames must be uint8 or float32, got {src.dtype}")
+    x = L.ClipXform()
+    x.src_dtype = L.TAV_U8 if src.dtype == torch.uint8 else L.TAV_F32
+    st = src.stride()
+    if layout == "THWC":
+        (x.T, x.H, x.W), (x.sT, x.sH, x.sW, x.sC) = src.shape[:3], st
+    else:
+        (x.T, x.H, x.W), (x.sC, x.sT, x.sH, x.sW) = src.shape[1:], st
+    frames = [int(f) for f in frames]
+    if not 1 <= len(frames) <= 32:
+        raise ValueError(f"a clip has 1..32 frames, got {len(frames)}")
+    x.nf = len(frames)
+    for i, f in enumerate(frames):
+        x.frame[i] = f
+    x.crop_top, x.crop_left, x.crop_h, x.crop_w = (0, 0, x.H, x.W) if crop is None else [int(v) for v in crop]
+    x.mid_h, x.mid_w = (0, 0) if mid is None else [int(v) for v in mid]
+    x.out_h, x.out_w = [int(v) for v in out_hw]
+    x.hflip, x.vflip = int(bool(hflip)), int(bool(vflip))
+    for c in range(3):
+        x.scale[c] = 1.0 / (255.0 * std[c])
+        x.shift[c] = mean[c] / std[c]
+    return x
+
+
+def video_clip_transform(src, out, xform):
+    """tav_video_clip_transform: src (device, uint8 or f32, any strides; xform from clip_xform(src, ...)) -> out f32 [nf, 3, out_h, out_w],
+    contiguous -- a slab of the batch tensor or, with out=None, a new tensor.  One launch, nothing staged on the host."""
+    if not src.is_cuda:
+        raise ValueError("video_clip_transform runs on the GPU only (libtavhip has no host form): move the frames to the device, or use "
+                         "models.tav.video_features_device, which ships the selected frames once")
+    shape = (xform.nf, 3, xform.out_h, xform.out_w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device:
+        raise ValueError(f"video_clip_transform: out must be a contiguous float32 {shape} tensor on {src.device}, "
+                         f"got {tuple(out.shape)} {out.dtype} on {out.device}")
+    last = (xform.T - 1) * xform.sT + (xform.H - 1) * xform.sH + (xform.W - 1) * xform.sW + 2 * xform.sC
+    if src.storage_offset() + last >= src.untyped_storage().nbytes() // src.element_size():
+        raise ValueError("video_clip_transform: the transform's sizes and strides reach past the source tensor's storage")
+    check(lib().tav_video_clip_transform(ptr(src), ptr(out), C.byref(xform), stream()), "video_clip_transform")
+    return out
+
+
 def mean_pool_fwd(x, B, S, *, seq_lens=None):
     """y[b] = mean over the S rows of batch entry b, or over its first seq_lens[b] (int32 [B] on the device; tav_mean_pool_fwd_len)."""
     W = x.shape[-1]

@@ -43,6 +43,29 @@ def make_batch(cfg, batch_size, *, seed=1234, s_text=128, t_audio=80000, n_visua
     return [text, audio_d, visual], labels.to(device)
 
 
+def make_items(cfg, n, *, raw_video=None, seed=1234, s_text=128, t_audio=80000, speakers=None):
+    """n seeded items in the collate contract, ([{"input_ids", "attention_mask"}, waveform, video], label), with waveforms of unequal length.
+    raw_video=None: video is a finished float clip [frames, 3, image, image].  raw_video=(T, H, W): video is what a decoder yields, uint8
+    [T, H, W, 3] frames -- for models.tav.collate_batch_device / video_features_device, which transform them on the device.  speakers: one
+    entry per item (None, True, False) wraps the frames as {"frames", "speaker"}."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    tc, vc = cfg["text"], cfg["video"]
+    items = []
+    for i in range(n):
+        ids = torch.randint(3, tc["vocab"], (s_text,), generator=g)
+        text = {"input_ids": ids, "attention_mask": torch.ones(s_text)}
+        wave = torch.randn(t_audio - (i * 997) % max(t_audio // 2, 1), generator=g) * 0.1
+        if raw_video is None:
+            video = torch.randn(vc["frames"], 3, vc["image"], vc["image"], generator=g)
+        else:
+            T, H, W = raw_video
+            video = torch.randint(0, 256, (T, H, W, 3), generator=g, dtype=torch.uint8)
+            if speakers is not None:
+                video = {"frames": video, "speaker": speakers[i]}
+        items.append(([text, wave, video], int(torch.randint(0, 7, (1,), generator=g))))
+    return items
+
+
 def seeded_init_(module, seed=0):
     """Re-draw every parameter from a seeded generator with the module's own init scale (std of the current values),
     so the oracle and the product can be given bit-identical random weights without shipping blobs."""
