@@ -212,13 +212,43 @@ static inline int ln_blocks(long rows) {
 }
 
 // ------------------------------------------------------------------------------------------------ group norm over time
-// x [B][T][C] channels-last.  stats pass: partial sums over a T-slice for 64 channels; apply pass element-wise.
+// x [B][T][C] channels-last.  forward: pivot pass (the mean of up to 32 sampled rows per (b, c)), statistics pass (partial sums over a T-slice
+// for GN_CB = 256 channels per workgroup, then a finalize), apply pass element-wise; backward: statistics, finalize, parameter gradients, apply.
 constexpr int GN_SPLIT = 32;
 constexpr int GN_CB = 256;       // channels per workgroup of the statistics pass
+constexpr int GN_PIVOT_ROWS = 32;   // rows the pivot of the forward statistics is averaged over
+
+// piv[b][c] = mean of n = min(T, GN_PIVOT_ROWS) rows of entry b spread evenly over it: rows ((2 i + 1) T) / (2 n), the middles of n equal
+// slices (T <= 32: every row).  A workgroup = 8 channel quads x 32 rows: every thread issues ONE 8-B / 16-B load, the thread of row 0 adds the
+// n values of its quad from LDS in row order (a fixed order: deterministic).  (One thread per quad walking its 32 rows one load after the
+// other added 17 us to the 311 us of the forward at 32 x 15999 x 512: 4096 threads, latency bound.)
+template <typename T>
+__global__ __launch_bounds__(256) void gn_pivot_kernel(const T* __restrict__ x, float* __restrict__ piv, int Tn, int C, int B) {
+    __shared__ float red[GN_PIVOT_ROWS][8][4];
+    const int i = threadIdx.x >> 3, ql = threadIdx.x & 7;
+    const long q = (long)blockIdx.x * 8 + ql;                // channel quad over the whole batch
+    const bool live = q < (long)B * (C >> 2);
+    const int b = live ? (int)(q / (C >> 2)) : 0, c = live ? (int)(q - (long)b * (C >> 2)) * 4 : 0;
+    const int n = Tn < GN_PIVOT_ROWS ? Tn : GN_PIVOT_ROWS;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (live && i < n) {
+        const long t = ((2l * i + 1) * Tn) / (2l * n);
+        v = ld4(x + ((long)b * Tn + t) * C + c);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) red[i][ql][e] = v[e];
+    __syncthreads();
+    if (live && i == 0) {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < n; ++k) s += f32x4{red[k][ql][0], red[k][ql][1], red[k][ql][2], red[k][ql][3]};
+        st4(piv + (long)b * C + c, s * (1.f / (float)n));
+    }
+}
 
 template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, const float* __restrict__ stats, float* part, int Tn, int C) {
+                                                       const float* __restrict__ beta, const float* __restrict__ stats,
+                                                       const float* __restrict__ piv, float* part, int Tn, int C) {
     // thread = 4 channels (one 8-B / 16-B load) x one of 4 row groups; a workgroup covers GN_CB = 256 channels, so a wave instruction reads
     // 512 contiguous bytes of one row.  (One channel per thread and 64 channels per workgroup -- 2-byte loads in 128-B pieces at a 1-KB
     // stride -- ran at 2.1-2.6 TB/s on the 524 MB activation of the wav2vec2 front-end.)
@@ -230,10 +260,14 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
     int t1 = t0 + per; t1 = t1 < Tn ? t1 : Tn;
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
     f32x4 mean = a0, rstd = a0, gam = a0, bet = a0;
-    // forward: sums of (x - pivot) and (x - pivot)^2, pivot = the entry's first row (the same in every split).  E[x^2] - mean^2 on the raw
-    // values loses the variance to cancellation when it is small beside mean^2 (a handful of steps per channel: 3e-4 on the output at T = 2).
+    // forward: sums of (x - pivot) and (x - pivot)^2, the same pivot in every split; gn_finalize_kernel forms s1 / T - m^2 with m = mean - pivot.
+    // That difference cancels (pivot - mean)^2 against the variance: its accumulation error is (1 + kappa) times that of a two-pass
+    // variance, kappa = (pivot - mean)^2 / var.  E[x^2] - mean^2 on the raw values is pivot = 0 (kappa = mean^2 / var, unbounded: 3e-4 on the
+    // output at T = 2); the entry's first row as pivot holds kappa to a few units only while that row is typical -- a loud onset in front of
+    // zero padding, 32 sigma off, costs 1e-4 of rstd at T = 1599.  The pivot is therefore gn_pivot_kernel's mean of up to 32 rows spread over
+    // the entry: kappa stays near 1 / 32 for typical rows and one outlier among them moves it by its offset / 32 only.
     f32x4 pivot = a0;
-    if (!BWD && live) pivot = ld4(x + (long)b * Tn * C + c);
+    if (!BWD && live) pivot = ld4(piv + (long)b * C + c);
     if (BWD && live) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) { mean[k] = stats[((long)b * C + c + k) * 2]; rstd[k] = stats[((long)b * C + c + k) * 2 + 1]; gam[k] = gamma[c + k]; bet[k] = beta[c + k]; }
@@ -273,19 +307,17 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
         }
     }
 }
-// fwd: stats[b][c] = (mean, rstd) from the pivoted sums (x: the activation, for the pivot);   bwd: sums[b][c] = (sum dz, sum dz*xhat), x unused
-template <typename T>
-__global__ void gn_finalize_kernel(const float* __restrict__ part, float* out, const T* __restrict__ x, int Tn, int C, int B, float eps, int fwd) {
+// fwd: stats[b][c] = (mean, rstd) from the pivoted sums (piv: gn_pivot_kernel's output);   bwd: sums[b][c] = (sum dz, sum dz*xhat), piv unused
+__global__ void gn_finalize_kernel(const float* __restrict__ part, float* out, const float* __restrict__ piv, int Tn, int C, int B, float eps, int fwd) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long)B * C) return;
     const int b = (int)(idx / C), c = (int)(idx - (long)b * C);
     float s0 = 0.f, s1 = 0.f;
     for (int sp = 0; sp < GN_SPLIT; ++sp) { s0 += part[(((long)b * GN_SPLIT + sp) * C + c) * 2]; s1 += part[(((long)b * GN_SPLIT + sp) * C + c) * 2 + 1]; }
     if (fwd) {
-        const f32x4 pq = ld4(x + (long)b * Tn * C + (c & ~3));
         const float m = s0 / Tn;                             // mean - pivot
         float var = s1 / Tn - m * m; var = var > 0.f ? var : 0.f;
-        out[idx * 2] = pq[c & 3] + m; out[idx * 2 + 1] = rsqrtf(var + eps);
+        out[idx * 2] = piv[idx] + m; out[idx * 2 + 1] = rsqrtf(var + eps);
     } else { out[idx * 2] = s0; out[idx * 2 + 1] = s1; }
 }
 // Apply passes: thread = 4 channels (one 8-B / 16-B access per row) x GN_AR rows at a stride of 4, so the per-(batch, channel) statistics
@@ -466,7 +498,8 @@ extern "C" int tav_ln_param_reduce_multi(const tav_ln_reduce_item* items, int32_
     return (int)hipGetLastError();
 }
 
-extern "C" int tav_gn_workspace_floats(int64_t B, int64_t C) { return (int)(B * GN_SPLIT * C * 2 + B * C * 2); }
+// [B][GN_SPLIT][C][2] partial sums, [B][C][2] sums of the backward, [B][C] pivots of the forward
+extern "C" int tav_gn_workspace_floats(int64_t B, int64_t C) { return (int)(B * GN_SPLIT * C * 2 + B * C * 2 + B * C); }
 
 extern "C" int tav_gn_gelu_fwd(const void* x, void* y, int32_t dtype, const float* gamma, const float* beta, float* stats, float* workspace,
                                int64_t B, int64_t T, int64_t C, float eps, void* stream) {
@@ -475,11 +508,14 @@ extern "C" int tav_gn_gelu_fwd(const void* x, void* y, int32_t dtype, const floa
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)tav_cdiv(C, GN_CB), GN_SPLIT, (unsigned)B);
     const dim3 agrid((unsigned)tav_cdiv(C, GN_CB), (unsigned)tav_cdiv(T, 4 * GN_AR), (unsigned)B);
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_stats_kernel<bf16, false>), grid, dim3(256), 0, st, (const bf16*)x, (const bf16*)nullptr, gamma, beta, stats, workspace, (int)T, (int)C);
-    else if (dtype == TAV_F32) hipLaunchKernelGGL((gn_stats_kernel<float, false>), grid, dim3(256), 0, st, (const float*)x, (const float*)nullptr, gamma, beta, stats, workspace, (int)T, (int)C);
-    else return TAV_ERR_DTYPE;
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_finalize_kernel<bf16>), dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, stats, (const bf16*)x, (int)T, (int)C, (int)B, eps, 1);
-    else hipLaunchKernelGGL((gn_finalize_kernel<float>), dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, stats, (const float*)x, (int)T, (int)C, (int)B, eps, 1);
+    if (dtype != TAV_BF16 && dtype != TAV_F32) return TAV_ERR_DTYPE;
+    float* piv = workspace + B * GN_SPLIT * C * 2 + B * C * 2;
+    const dim3 pgrid((unsigned)tav_cdiv(B * (C / 4), 8));
+    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_pivot_kernel<bf16>), pgrid, dim3(256), 0, st, (const bf16*)x, piv, (int)T, (int)C, (int)B);
+    else hipLaunchKernelGGL((gn_pivot_kernel<float>), pgrid, dim3(256), 0, st, (const float*)x, piv, (int)T, (int)C, (int)B);
+    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_stats_kernel<bf16, false>), grid, dim3(256), 0, st, (const bf16*)x, (const bf16*)nullptr, gamma, beta, stats, piv, workspace, (int)T, (int)C);
+    else hipLaunchKernelGGL((gn_stats_kernel<float, false>), grid, dim3(256), 0, st, (const float*)x, (const float*)nullptr, gamma, beta, stats, piv, workspace, (int)T, (int)C);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, stats, piv, (int)T, (int)C, (int)B, eps, 1);
     if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_apply_fwd_kernel<bf16>), agrid, dim3(256), 0, st, (const bf16*)x, (bf16*)y, gamma, beta, stats, (int)T, (int)C);
     else hipLaunchKernelGGL((gn_apply_fwd_kernel<float>), agrid, dim3(256), 0, st, (const float*)x, (float*)y, gamma, beta, stats, (int)T, (int)C);
     return (int)hipGetLastError();
@@ -493,10 +529,10 @@ extern "C" int tav_gn_gelu_bwd(const void* x, const void* dy, void* dx, int32_t 
     dim3 grid((unsigned)tav_cdiv(C, GN_CB), GN_SPLIT, (unsigned)B);
     const dim3 agrid((unsigned)tav_cdiv(C, GN_CB), (unsigned)tav_cdiv(T, 4 * GN_AR), (unsigned)B);
     float* sums = workspace + B * GN_SPLIT * C * 2;
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_stats_kernel<bf16, true>), grid, dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, gamma, beta, stats, workspace, (int)T, (int)C);
-    else if (dtype == TAV_F32) hipLaunchKernelGGL((gn_stats_kernel<float, true>), grid, dim3(256), 0, st, (const float*)x, (const float*)dy, gamma, beta, stats, workspace, (int)T, (int)C);
+    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_stats_kernel<bf16, true>), grid, dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, gamma, beta, stats, (const float*)nullptr, workspace, (int)T, (int)C);
+    else if (dtype == TAV_F32) hipLaunchKernelGGL((gn_stats_kernel<float, true>), grid, dim3(256), 0, st, (const float*)x, (const float*)dy, gamma, beta, stats, (const float*)nullptr, workspace, (int)T, (int)C);
     else return TAV_ERR_DTYPE;
-    hipLaunchKernelGGL((gn_finalize_kernel<float>), dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, sums, (const float*)nullptr, (int)T, (int)C, (int)B, 0.f, 0);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, sums, (const float*)nullptr, (int)T, (int)C, (int)B, 0.f, 0);
     hipLaunchKernelGGL(gn_param_grad_kernel, dim3(tav_cdiv(C, 256)), dim3(256), 0, st, sums, dgamma, dbeta, (int)B, (int)C, accumulate);
     if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_apply_bwd_kernel<bf16>), agrid, dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, (bf16*)dx, gamma, beta, stats, sums, (int)T, (int)C);
     else hipLaunchKernelGGL((gn_apply_bwd_kernel<float>), agrid, dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, gamma, beta, stats, sums, (int)T, (int)C);

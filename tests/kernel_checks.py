@@ -14,6 +14,7 @@ import torch.nn.functional as F
 import attn_ref as AR
 import gemm_ref as GR
 import guarded
+import norm_ref as NR
 import step_end_ref as SR
 import tav_amd.ops as ops
 
@@ -2258,6 +2259,332 @@ def attention_fp64_checks():
     return out
 
 
+# ================================================================================================= normalisation against fp64
+# tests/norm_ref.py: per-element bounds at operands of spread magnitude, integer cases with ONE right answer, an atypical first row in front of
+# the group norm's statistics.  The library is called through the C ABI: pitched outputs, accumulation, a bf16 dy, hand-fed mean / rstd / stats
+# and workspaces at exactly the advertised size are things the ops wrappers (rightly) cannot express.
+def _dev(a, dtype, pitch=0):
+    return _in(torch.from_numpy(np.ascontiguousarray(a)).to(DEV).to(dtype), pitch)
+
+
+def _wide(rows, W, dtype, pitch):
+    """An all-0xFF [rows][W + pitch] buffer and the [rows][W] view the kernel is to fill."""
+    w = _blank((rows, W + pitch), dtype)
+    return w, w[:, :W]
+
+
+def _filled(a):
+    t = _blank(tuple(a.shape), torch.float32)
+    t.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(DEV).float())
+    return t
+
+
+def _ln_dev(p, pitch=0):
+    return _dev(p["x"], _TDT[p["xdt"]], pitch), _dev(p["gamma"], torch.float32), _dev(p["beta"], torch.float32)
+
+
+def _ln_base(p, dev, act):
+    a = ops.L.LnArgs()
+    xt, gam, bet = dev
+    a.x, a.x_dtype, a.gamma, a.beta = ops.ptr(xt), ops.dt(xt), ops.ptr(gam), ops.ptr(bet)
+    a.rows, a.W, a.ld_x, a.eps, a.act = p["rows"], p["W"], xt.stride(0), 1e-5, act
+    return a
+
+
+def _ln_fwd_abi(p, dev, *, act=0, want32=True, lp=True, pitch=0, stats=True):
+    """tav_ln_fwd -> (dict y_f32, y_lp, mean, rstd (None where not asked for), the pitch gaps of the outputs)."""
+    rows, W = p["rows"], p["W"]
+    a = _ln_base(p, dev, act)
+    y32w, y32 = _wide(rows, W, torch.float32, pitch) if want32 else (None, None)
+    ylw, yl = _wide(rows, W, torch.bfloat16, pitch) if lp else (None, None)
+    mean, rstd = (_blank((rows,), torch.float32), _blank((rows,), torch.float32)) if stats else (None, None)
+    a.y_f32, a.y_lp, a.lp_dtype, a.mean, a.rstd, a.ld_y = ops.ptr(y32), ops.ptr(yl), ops.dt(torch.bfloat16) if lp else 0, ops.ptr(mean), ops.ptr(rstd), W + pitch
+    ops.check(ops.lib().tav_ln_fwd(ops.C.byref(a), ops.stream()), "ln_fwd")
+    return dict(y_f32=y32, y_lp=yl, mean=mean, rstd=rstd), [w[:, W:] for w in (y32w, ylw) if w is not None]
+
+
+def _ln_bwd_abi(p, dev, dyt, mean, rstd, *, act=0, want32=True, lp=True, pitch=0, add=None, grads=True, prev=None, defer=False):
+    """tav_ln_bwd -> (dict dx_f32, dx_lp, dgamma, dbeta, partials, nb; gaps).  prev: (dgamma, dbeta) contents to accumulate onto."""
+    rows, W = p["rows"], p["W"]
+    a = _ln_base(p, dev, act)
+    nb = ops.lib().tav_ln_bwd_partials(rows)
+    d32w, d32 = _wide(rows, W, torch.float32, pitch) if want32 else (None, None)
+    dlw, dl = _wide(rows, W, torch.bfloat16, pitch) if lp else (None, None)
+    dg = db = part = None
+    if grads:
+        dg, db = (_filled(prev[0]), _filled(prev[1])) if prev is not None else (_blank((W,), torch.float32), _blank((W,), torch.float32))
+        part = _blank((nb * 2 * W,), torch.float32)
+    a.mean, a.rstd, a.dy, a.dy_dtype, a.dx_add, a.ld_dy = ops.ptr(mean), ops.ptr(rstd), ops.ptr(dyt), ops.dt(dyt), ops.ptr(add), dyt.stride(0)
+    a.dx_f32, a.dx_lp, a.lp_dtype, a.ld_dx = ops.ptr(d32), ops.ptr(dl), ops.dt(torch.bfloat16) if lp else 0, W + pitch
+    a.dgamma, a.dbeta, a.partials, a.accumulate_params, a.defer_param_reduce = ops.ptr(dg), ops.ptr(db), ops.ptr(part), int(prev is not None), int(defer)
+    ops.check(ops.lib().tav_ln_bwd(ops.C.byref(a), ops.stream()), "ln_bwd")
+    return dict(dx_f32=d32, dx_lp=dl, dgamma=dg, dbeta=db, partials=part, nb=nb), [w[:, W:] for w in (d32w, dlw) if w is not None]
+
+
+def _ln_reduce_multi(items):
+    """items: (partials, dgamma, dbeta, nblocks, W, accumulate) -> one tav_ln_param_reduce_multi launch."""
+    arr = (ops.L.LnReduceItem * len(items))()
+    for j, (part, dg, db, nb, W, acc) in enumerate(items):
+        arr[j].partials, arr[j].dgamma, arr[j].dbeta, arr[j].nblocks, arr[j].W, arr[j].accumulate = ops.ptr(part), ops.ptr(dg), ops.ptr(db), nb, W, acc
+    ops.check(ops.lib().tav_ln_param_reduce_multi(arr, len(items), ops.stream()), "ln_param_reduce_multi")
+
+
+@functools.lru_cache(maxsize=4)
+def _ln_fwd_reference(rows, W, xdt, act, lp):
+    return NR.ln_ref_fwd(NR.ln_inputs(rows, W, xdt, "f32"), act, lp)                # (x, gamma and beta do not depend on the dtype of dy)
+
+
+def _some(rs, got, ref, tag, names):
+    for n in names:
+        if got.get(n) is not None:
+            rs.append(_bounded(f"{tag}.{n}", got[n], ref[n], ref[n + "_b"]))
+
+
+def _ln_bounded_one(rs, rows, W, xdt, dydt, *, act, lp, both, pitch, add, accumulate, chained=False, fwd=True):
+    """One forward and one backward launch of the spread-magnitude problem, every output within its bound, every pitch gap still 0xFF."""
+    p = NR.ln_inputs(rows, W, xdt, dydt)
+    dev = _ln_dev(p, 4 if pitch else 0)
+    tag = f"ln.bound[x {xdt},dy {dydt},lp{int(lp)},W{W},rows{rows},act{act},pitch{pitch},add{int(add)},acc{int(accumulate)}]"
+    want32 = both or not lp
+    ref = _ln_fwd_reference(rows, W, xdt, act, lp)
+    f = None
+    if fwd or chained:
+        f, gaps = _ln_fwd_abi(p, dev, act=act, want32=want32, lp=lp, pitch=pitch)
+        _some(rs, f, ref, tag, NR.LN_FWD_OUT)
+        rs.append(_all_ff(tag + ".y gaps", *gaps))
+    if chained:
+        mean, rstd, mv, rv, sfx = f["mean"], f["rstd"], ref["_mean"], ref["_rstd"], ".chained"
+    else:
+        (mv, m32), (rv, r32) = NR.fed(ref["mean"]), NR.fed(ref["rstd"])
+        mean, rstd, sfx = _dev(m32, torch.float32), _dev(r32, torch.float32), ""
+    kw = dict(act=act, lp=lp, add=add, accumulate=accumulate)
+    b, gaps = _ln_bwd_abi(p, dev, _dev(p["dy"], _TDT[dydt], 8 if pitch else 0), mean, rstd, act=act, want32=want32, lp=lp, pitch=pitch,
+                          add=_dev(p["add"], torch.float32, pitch) if add else None, prev=(p["prev_g"], p["prev_b"]) if accumulate else None)
+    _some(rs, b, NR.ln_ref_bwd(p, mv, rv, **kw), tag + sfx, NR.LN_BWD_OUT)
+    rs.append(_all_ff(tag + ".dx gaps", *gaps))
+
+
+def check_layernorm_bounded(xdt, W):
+    """tav_ln_fwd / tav_ln_bwd at one width, rows 1, 5, 17, 333: x f32 | bf16 (per group) x dy f32 | bf16 x low-precision output none | bf16 --
+    with this group's twin all eight backward instantiations --; the backward isolated, at W = 768 also chained.  The forward does not read dy,
+    so it is launched with the f32 dy only (di = 0).  The options of a case follow from ri (index of rows), di (0: dy f32, 1: bf16), li (0: no
+    bf16 output, 1: one) and k = ri + di + li + W / 4:
+
+        act          k odd                                 pitched rows     k / 2 odd   (x + 4, dy + 8, outputs and dx_add + 8 elements)
+        dx_add       ri + li even                          accumulate       ri + di + li divisible by 3
+        outputs      li = 0: f32 only;   li = 1: f32 and bf16 where ri + di is even, bf16 only where it is odd
+
+    W / 4 is odd for W = 4, 252 and 260 and even for the other widths, so each (rows, dy, output) cell meets both values of act across the
+    widths, and k / 2 takes both parities within every group (k runs over four consecutive values)."""
+    rs = []
+    for ri, rows in enumerate(NR.LN_ROWS):
+        for di, dydt in enumerate(("f32", "bf16")):
+            for li, lp in enumerate((False, True)):
+                k = ri + di + li + W // 4
+                _ln_bounded_one(rs, rows, W, xdt, dydt, act=k % 2, lp=lp, both=(ri + di) % 2 == 0, pitch=8 * ((k // 2) % 2), add=(ri + li) % 2 == 0,
+                                accumulate=(ri + di + li) % 3 == 0, fwd=di == 0)
+    if W == 768:
+        for act in (0, 1):
+            _ln_bounded_one(rs, 333, W, xdt, xdt, act=act, lp=True, both=True, pitch=0, add=True, accumulate=False, chained=True)
+    return rs
+
+
+def check_layernorm_bounded_big(xdt, W, act):
+    """8192 + 37 rows: past the grid caps of both kernels, so the row loops and the backward's prefetch pipeline run more than once per wave."""
+    rs = []
+    _ln_bounded_one(rs, NR.LN_ROWS_BIG, W, xdt, xdt, act=act, lp=xdt == "bf16", both=True, pitch=8 if W == 64 else 0, add=True, accumulate=W == 64)
+    return rs
+
+
+def check_layernorm_options():
+    """The corners of the argument struct: mean = rstd = NULL in a forward, param_grads off (partials = NULL, the early return), and the deferred
+    reduce through tav_ln_param_reduce_multi with 1, 3 and 64 items of mixed W and nblocks (1, 63, 65 and 512 among them), accumulating on some:
+    bit-equal to the immediate form, inside the bound against fp64, and nothing stored into dgamma / dbeta before the reduce."""
+    rs = []
+    p = NR.ln_inputs(333, 260, "f32", "f32")
+    dev = _ln_dev(p)
+    ref = _ln_fwd_reference(333, 260, "f32", 0, True)
+    f, gaps = _ln_fwd_abi(p, dev, lp=True, pitch=8, stats=False)
+    _some(rs, f, ref, "ln.fwd without mean / rstd", ("y_f32", "y_lp"))
+    rs.append(_all_ff("ln.fwd without mean / rstd.gaps", *gaps))
+    (mv, m32), (rv, r32) = NR.fed(ref["mean"]), NR.fed(ref["rstd"])
+    b, gaps = _ln_bwd_abi(p, dev, _dev(p["dy"], torch.float32), _dev(m32, torch.float32), _dev(r32, torch.float32), grads=False)
+    _some(rs, b, NR.ln_ref_bwd(p, mv, rv, add=False), "ln.bwd without param grads", ("dx_f32", "dx_lp"))
+    shapes = [(333, 260), (5, 4), (16 * 63, 64), (16 * 65 - 3, 252), (NR.LN_ROWS_BIG, 64)] + [(1 + 7 * i % 40, NR.LN_W[i % 7]) for i in range(59)]
+    runs = []
+    for i, (rows, W) in enumerate(shapes):
+        xdt = ("f32", "bf16")[i % 2]
+        q = NR.ln_inputs(rows, W, xdt, xdt)
+        qd = _ln_dev(q)
+        qref = _ln_fwd_reference(rows, W, xdt, 0, False)
+        (qm, m32), (qr, r32) = NR.fed(qref["mean"]), NR.fed(qref["rstd"])
+        mt, rt, dyt = _dev(m32, torch.float32), _dev(r32, torch.float32), _dev(q["dy"], _TDT[xdt])
+        acc = i % 3 == 1
+        prev = (q["prev_g"], q["prev_b"]) if acc else None
+        imm, _ = _ln_bwd_abi(q, qd, dyt, mt, rt, lp=False, prev=prev)
+        dfr, _ = _ln_bwd_abi(q, qd, dyt, mt, rt, lp=False, prev=prev, defer=True)
+        if not acc:
+            rs.append(_all_ff(f"ln.deferred[{i}] dgamma / dbeta untouched by the backward", dfr["dgamma"], dfr["dbeta"]))
+        if i < 5:
+            _some(rs, imm, NR.ln_ref_bwd(q, qm, qr, lp=False, add=False, accumulate=acc), f"ln.immediate[rows{rows},W{W},nb{imm['nb']},acc{int(acc)}]", ("dgamma", "dbeta"))
+        runs.append((imm, dfr, q["W"], acc))
+    assert {r[0]["nb"] for r in runs} >= {1, 63, 65, 512}
+    for lo, hi in ((0, 1), (1, 4), (0, 64)):
+        fresh = []
+        for k, (imm, dfr, W, acc) in enumerate(runs[lo:hi]):
+            i = lo + k
+            q = NR.ln_inputs(shapes[i][0], W, ("f32", "bf16")[i % 2], ("f32", "bf16")[i % 2])
+            dg, db = (_filled(q["prev_g"]), _filled(q["prev_b"])) if acc else (_blank((W,), torch.float32), _blank((W,), torch.float32))
+            fresh.append((dfr["partials"], dg, db, dfr["nb"], W, int(acc)))
+        _ln_reduce_multi(fresh)
+        bad_g = sum(int((it[1] != run[0]["dgamma"]).sum()) + int(it[1].isnan().sum()) for it, run in zip(fresh, runs[lo:hi]))
+        bad_b = sum(int((it[2] != run[0]["dbeta"]).sum()) + int(it[2].isnan().sum()) for it, run in zip(fresh, runs[lo:hi]))
+        rs += [(f"ln.reduce_multi x{hi - lo} dgamma bitwise", float(bad_g), 0.0, bad_g == 0), (f"ln.reduce_multi x{hi - lo} dbeta bitwise", float(bad_b), 0.0, bad_b == 0)]
+    return rs
+
+
+def _want(a, dtype):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV).to(dtype)
+
+
+def check_layernorm_exact(xdt, dydt):
+    """The integer construction of norm_ref.ln_exact_case fed mean = 0, rstd = 1: dx_f32 equal to the fp64 value bit for bit, dx_lp to its
+    round-to-nearest-even, dgamma / dbeta to the fp64 sums -- accumulated onto integer contents, through the immediate and the deferred reduce,
+    pitched, with and without the saturated GELU, at 333 rows and past the grid caps."""
+    rs = []
+    for rows, W, pitch in ((333, 64, 8), (333, 512, 0), (17, 1024, 8), (NR.LN_ROWS_BIG, 64, 0), (NR.LN_ROWS_BIG, 1024, 8)):
+        for act in (0, 1):
+            if rows > 1000 and act != (W == 64):
+                continue
+            assert NR.exact_ok(rows, W)
+            p = NR.ln_exact_case(rows, W, xdt, dydt, act)
+            dev = _ln_dev(p)
+            zero, one = _dev(np.zeros(rows), torch.float32), _dev(np.ones(rows), torch.float32)
+            dyt, add = _dev(p["dy"], _TDT[dydt], 8 if pitch else 0), _dev(p["add"], torch.float32, pitch)
+            tag = f"ln.exact[x {xdt},dy {dydt},rows{rows},W{W},act{act},pitch{pitch}]"
+            want_g, want_b = _want(p["want_dg"] + p["prev_g"], torch.float32), _want(p["want_db"] + p["prev_b"], torch.float32)
+            b, gaps = _ln_bwd_abi(p, dev, dyt, zero, one, act=act, pitch=pitch, add=add, prev=(p["prev_g"], p["prev_b"]))
+            rs += [_exact(tag + ".dx_f32", b["dx_f32"], _want(p["want_dx"], torch.float32)), _exact(tag + ".dx_lp", b["dx_lp"], _want(p["want_dx"], torch.bfloat16)),
+                   _exact(tag + ".dgamma", b["dgamma"], want_g), _exact(tag + ".dbeta", b["dbeta"], want_b), _all_ff(tag + ".gaps", *gaps)]
+            d, _ = _ln_bwd_abi(p, dev, dyt, zero, one, act=act, pitch=pitch, add=add, prev=(p["prev_g"], p["prev_b"]), defer=True)
+            _ln_reduce_multi([(d["partials"], d["dgamma"], d["dbeta"], d["nb"], W, 1)])
+            rs += [_exact(tag + ".deferred dgamma", d["dgamma"], want_g), _exact(tag + ".deferred dbeta", d["dbeta"], want_b)]
+    return rs
+
+
+def check_norm_exact_statistics():
+    """Forward statistics with one right answer: LayerNorm rows of +-a in equal number (mean exactly 0) and constant integer rows (mean = the
+    constant, y = beta exactly); group norm on integers over a power-of-two T (mean exact, rstd within the bounded term)."""
+    rs = []
+    for xdt in ("f32", "bf16"):
+        for W in (64, 512, 1024):
+            p = NR.ln_stats_case(33, W)
+            p["xdt"] = xdt
+            f, _ = _ln_fwd_abi(p, _ln_dev(p), lp=False)
+            rs += [_exact(f"ln.exact mean[{xdt},W{W}]", f["mean"], _want(p["want_mean"], torch.float32)),
+                   _exact(f"ln.exact y = beta[{xdt},W{W}]", f["y_f32"][1::2], _want(np.broadcast_to(p["beta"], (16, W)), torch.float32))]
+        for T in (1, 64, 1024):
+            p = NR.gn_exact_case(3, T, 64, xdt)
+            f = _gn_fwd_abi(p)
+            ref = NR.gn_ref_fwd(p)
+            rs += [_exact(f"gn.exact mean[{xdt},T{T}]", f["mean"], _want(p["want_mean"], torch.float32)),
+                   _bounded(f"gn.exact rstd[{xdt},T{T}]", f["rstd"], ref["rstd"], ref["rstd_b"])]
+    return rs
+
+
+def _gn_ws(B, C):
+    n = ops.lib().tav_gn_workspace_floats(B, C)
+    assert n == NR.gn_workspace_floats(B, C)
+    return _blank((n,), torch.float32)                                              # exactly the advertised size, under guard
+
+
+def _gn_fwd_abi(p):
+    B, T, C, dtype = p["B"], p["T"], p["C"], _TDT[p["dt"]]
+    x, gam, bet = _dev(p["x"], dtype), _dev(p["gamma"], torch.float32), _dev(p["beta"], torch.float32)
+    y, stats = _blank((B, T, C), dtype), _blank((B, C, 2), torch.float32)
+    ops.check(ops.lib().tav_gn_gelu_fwd(ops.ptr(x), ops.ptr(y), ops.dt(dtype), ops.ptr(gam), ops.ptr(bet), ops.ptr(stats), ops.ptr(_gn_ws(B, C)), B, T, C,
+                                        1e-5, ops.stream()), "gn_gelu_fwd")
+    return dict(y=y, stats=stats, mean=stats[..., 0], rstd=stats[..., 1], dev=(x, gam, bet))
+
+
+def _gn_bwd_abi(p, dev, stats, prev=None):
+    B, T, C, dtype = p["B"], p["T"], p["C"], _TDT[p["dt"]]
+    x, gam, bet = dev
+    dy, dx = _dev(p["dy"], dtype), _blank((B, T, C), dtype)
+    dg, db = (_filled(prev[0]), _filled(prev[1])) if prev is not None else (_blank((C,), torch.float32), _blank((C,), torch.float32))
+    ops.check(ops.lib().tav_gn_gelu_bwd(ops.ptr(x), ops.ptr(dy), ops.ptr(dx), ops.dt(dtype), ops.ptr(gam), ops.ptr(bet), ops.ptr(stats), ops.ptr(_gn_ws(B, C)),
+                                        ops.ptr(dg), ops.ptr(db), B, T, C, int(prev is not None), ops.stream()), "gn_gelu_bwd")
+    return dict(dx=dx, dgamma=dg, dbeta=db)
+
+
+def _gn_bounded_one(rs, B, T, C, dt, accumulate, chained=False, onset=False):
+    p = NR.gn_inputs(B, T, C, dt, onset=onset)
+    ref = NR.gn_ref_fwd(p)
+    tag = f"gn.bound[{dt},B{B},T{T},C{C},acc{int(accumulate)}{',onset' if onset else ''}]"
+    f = _gn_fwd_abi(p)
+    _some(rs, f, ref, tag, NR.GN_FWD_OUT)
+    if onset:
+        return
+    prev = (p["prev_g"], p["prev_b"]) if accumulate else None
+    (mv, m32), (rv, r32) = NR.fed(ref["mean"]), NR.fed(ref["rstd"])
+    _some(rs, _gn_bwd_abi(p, f["dev"], _dev(np.stack([m32, r32], -1), torch.float32), prev), NR.gn_ref_bwd(p, mv, rv, accumulate), tag, NR.GN_BWD_OUT)
+    if chained:
+        _some(rs, _gn_bwd_abi(p, f["dev"], f["stats"], prev), NR.gn_ref_bwd(p, ref["_mean"], ref["_rstd"], accumulate), tag + ".chained", NR.GN_BWD_OUT)
+
+
+def check_group_norm_bounded(dt, C, half):
+    """tav_gn_gelu_fwd / _bwd at one channel count and six of the twelve lengths (empty splits, one row per split, a ragged last split, one and
+    two unrolled chunks plus a tail in both statistics kernels, both branches of the apply block), B = 1 | 3 and accumulate alternating: stats
+    (mean, rstd), y, and -- fed the reference's stats -- dx, dgamma, dbeta within their bounds; T = 1599 also chained."""
+    rs = []
+    for i, T in enumerate(NR.GN_T[6 * half:6 * half + 6]):
+        k = i + C // 64
+        _gn_bounded_one(rs, 1 if k % 2 else 3, T, C, dt, accumulate=(k // 2) % 2 == 1, chained=T == 1599)
+    return rs
+
+
+def check_group_norm_exact(dt):
+    """norm_ref.gn_exact_case fed stats = (0, 1): the saturated GELU is exactly the identity, so dx, dgamma and dbeta (accumulated onto integer
+    contents) have one right answer."""
+    rs = []
+    for T, C in ((1, 64), (64, 320), (1024, 64)):
+        p = NR.gn_exact_case(3, T, C, dt)
+        dev = (_dev(p["x"], _TDT[dt]), _dev(p["gamma"], torch.float32), _dev(p["beta"], torch.float32))
+        stats = _dev(np.stack([np.zeros((3, C)), np.ones((3, C))], -1), torch.float32)
+        b = _gn_bwd_abi(p, dev, stats, (p["prev_g"], p["prev_b"]))
+        tag = f"gn.exact[{dt},T{T},C{C}]"
+        rs += [_exact(tag + ".dx", b["dx"], _want(p["want_dx"], _TDT[dt])), _exact(tag + ".dgamma", b["dgamma"], _want(p["want_dg"] + p["prev_g"], torch.float32)),
+               _exact(tag + ".dbeta", b["dbeta"], _want(p["want_db"] + p["prev_b"], torch.float32))]
+    return rs
+
+
+def check_group_norm_onset(dt):
+    """An atypical FIRST row -- 32 sigma off in the even channels, 256 sigma in the odd ones, T = 1599 -- against the statistics bound with kappa
+    capped at what a typical row is allowed (norm_ref.KAPPA_CAP): the pivot of the statistics pass must not be that row."""
+    rs = []
+    _gn_bounded_one(rs, 2, 1599, 64, dt, False, onset=True)
+    return rs
+
+
+def norm_fp64_checks():
+    """The normalisation cases against fp64, in the order all_checks() appends them."""
+    out = []
+    for dt_ in ("f32", "bf16"):
+        for W in NR.LN_W:
+            out.append(lambda d=dt_, w=W: check_layernorm_bounded(d, w))
+        for W, act in ((64, 0), (64, 1), (1024, int(dt_ == "bf16"))):
+            out.append(lambda d=dt_, w=W, a=act: check_layernorm_bounded_big(d, w, a))
+        for dydt in ("f32", "bf16"):
+            out.append(lambda d=dt_, e=dydt: check_layernorm_exact(d, e))
+        for C in NR.GN_C:
+            for half in (0, 1):
+                out.append(lambda d=dt_, c=C, h=half: check_group_norm_bounded(d, c, h))
+        out.append(lambda d=dt_: check_group_norm_exact(d))
+        out.append(lambda d=dt_: check_group_norm_onset(d))
+    out += [check_layernorm_options, check_norm_exact_statistics]
+    return out
+
+
 def all_checks():
     out = []
     for dtype in (torch.float32, torch.bfloat16):
@@ -2378,4 +2705,6 @@ def all_checks():
     out += gemm_fp64_checks()
     # the attention family against fp64: per-element bounds, exact selections, isolated and chained backward, the two helper kernels
     out += attention_fp64_checks()
+    # the normalisation family against fp64: per-element bounds, exact integer cases, the group norm's pivot on an atypical first row
+    out += norm_fp64_checks()
     return out
