@@ -24,7 +24,8 @@ extern "C" {
 #endif
 
 enum { TAV_F32 = 0, TAV_BF16 = 1, TAV_FP8 = 2 /* OCP e4m3, GEMM operands of tav_gemm_nt only */,
-       TAV_U8 = 3 /* decoded video frames, the source of tav_video_clip_transform only */ };
+       TAV_U8 = 3 /* decoded video frames, the source of tav_video_clip_transform only */,
+       TAV_I16 = 4 /* decoded 16-bit PCM, the source of tav_audio_resample only */ };
 enum {
     TAV_ERR_NULL = -1,  /* required pointer missing           */
     TAV_ERR_SHAPE = -2, /* size not supported by the kernel   */
@@ -330,6 +331,40 @@ typedef struct {
     float scale[3], shift[3];          /* y = v * scale[c] - shift[c]; host: 1 / (255 std), mean / std in f32 */
 } tav_clip_xform;
 int tav_video_clip_transform(const void* src, float* dst /* [nf][3][out_h][out_w] */, const tav_clip_xform* x, void* stream);
+
+/* Audio waveform transform (additive to ABI v7; models/tav.py:165-169, speech_file_to_array_fn): decoded PCM -> one row of the [B, T] batch
+ * the audio front-end reads and one row of its mask, one launch per utterance.  It is torchaudio.transforms.Resample(sr, target) at its
+ * defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), .squeeze() and the mean over the channels.
+ * Coefficients (the host's work): g = gcd(sr, target), o = sr / g, n = target / g, base = min(o, n) * 0.99, width = ceil(6 o / base); for phase
+ * p in [0, n) and tap k in [0, 2 width + o), in fp64: t = clamp((-p / n + (k - width) / o) * base, -6, 6), win = cos(t pi / 12)^2, t *= pi,
+ * h[p][k] = (t == 0 ? 1 : sin(t) / t) * win * (base / o); the table is rounded once to f32.  Application: each channel is padded with `width`
+ * zeros in front and `width + o` behind, y_c[q n + p] = sum_k h[p][k] xpad_c[q o + k], the first L_out = (n L + o - 1) / o samples are kept and
+ * y = (1 / C) sum_c y_c.  sr == target is the identity (Resample.forward returns its input; the sinc table of that pair is no delta): pass
+ * o = n = 1, width = 0 and a table of one phase with the one tap 1.0f.
+ * Taps outside the Hann window are exactly 0 in f32, so the kernel takes the compact table: table[p][0..ntap) holds taps first[p] ..
+ * first[p] + ntap - 1 of phase p (rows zero-filled past their own live taps), both in device memory.  The filter is linear: the channel mean
+ * of the input (ascending f32 sum over c, times 1.0f / C) is formed once per workgroup in LDS, then every output is fmaf over ascending k
+ * from 0.  TAV_I16 samples are scaled by 2^-15 (exact).  The zero padding is a predicate and every load index is clamped into [0, L).  No
+ * atomic, no cross-thread reduction: two launches give identical bits.
+ * Written: values[0..T_row) in full -- L_out samples, then 0.0f -- and, when mask is given, mask[0..T_row): 1.0f for the samples, then 0.0f.
+ * Nothing else.  The struct is read on the HOST when the call is made and travels as kernel arguments.
+ * TAV_ERR_NULL: src, values, table, first or a missing.  TAV_ERR_DTYPE: src_dtype neither TAV_F32 nor TAV_I16.  TAV_ERR_SHAPE: C outside
+ * 1..32; L < 1; a negative stride; o, n or ntap below 1 (or o, n above 2^20); n * ntap above 2^24; first_max (the largest first[p], which the
+ * host knows from its own table) negative or first_max + ntap past 2 width + o; T_row below L_out; L or T_row above 2^40; a rate pair for
+ * which tav_audio_resample_tile is 0. */
+typedef struct {
+    int32_t src_dtype;                 /* TAV_F32 or TAV_I16 */
+    int32_t C;                         /* channels, 1..32 */
+    int64_t L, sC, sL;                 /* samples per channel; element strides: planar [C][L] (L, 1), interleaved [L][C] (1, C), mono (0, 1) */
+    int32_t o, n, width, ntap;         /* sr / g, target / g, the filter's half width in input samples, taps per row of the compact table */
+    int32_t first_max, reserved;       /* max_p first[p] */
+    int64_t T_row;                     /* elements of the values (and mask) row, >= L_out */
+} tav_resample_args;
+int tav_audio_resample(const void* src, const float* table /* [n][ntap] */, const int32_t* first /* [n] */, float* values /* [T_row] */,
+                       float* mask /* [T_row] or NULL */, const tav_resample_args* a, void* stream);
+/* outputs one workgroup of tav_audio_resample makes for a rate pair (a multiple of 256 up to 1024: the largest whose input span fits its
+ * LDS buffer), 0 when none does (o / n beyond about 30).  Host only. */
+int tav_audio_resample_tile(int32_t o, int32_t n, int32_t width);
 
 /* per row of mask [B][n] (uint8/bool; keep where mask == keep_value): write ascending indices [B][nkeep];
  * counts[B] receives the number found (host checks == nkeep when it wants to).  A row with fewer than nkeep kept tokens gets its

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TAV_LIB") or os.path.join(_HERE, "libtavhip.so")      # TAV_LIB: developer knob, A/B of two builds (tools/ab_build.sh)
 
-TAV_F32, TAV_BF16, TAV_FP8, TAV_U8 = 0, 1, 2, 3
+TAV_F32, TAV_BF16, TAV_FP8, TAV_U8, TAV_I16 = 0, 1, 2, 3, 4
 ABI_VERSION = 7
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -76,6 +76,11 @@ class ClipXform(C.Structure):
                 ("scale", f32 * 3), ("shift", f32 * 3)]
 
 
+class ResampleArgs(C.Structure):
+    _fields_ = [("src_dtype", i32), ("C", i32), ("L", i64), ("sC", i64), ("sL", i64), ("o", i32), ("n", i32), ("width", i32), ("ntap", i32),
+                ("first_max", i32), ("reserved", i32), ("T_row", i64)]
+
+
 _SIGS = {
     "tav_version": (C.c_int, []),
     "tav_error_string": (C.c_char_p, [C.c_int]),
@@ -124,6 +129,8 @@ _SIGS = {
     "tav_gather_rows": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
     "tav_patchify": (C.c_int, [vp, vp, vp, i32, i64, i64, i64, i64, i64, vp]),
     "tav_video_clip_transform": (C.c_int, [vp, vp, C.POINTER(ClipXform), vp]),
+    "tav_audio_resample": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(ResampleArgs), vp]),
+    "tav_audio_resample_tile": (C.c_int, [i32, i32, i32]),
     "tav_mask_to_index": (C.c_int, [vp, i32, vp, vp, i64, i64, i64, vp]),
     "tav_ragged_lens": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
     "tav_mean_pool_fwd": (C.c_int, [vp, vp, i64, i64, i64, vp]),

@@ -4,6 +4,7 @@
   TAVForMAE   reference models/tav.py:420-504   3 encoders + fusion encoder + 7-way head
   collate_batch  reference models/tav.py:174-246   (mask / pad logic only: file decoding is out of scope)
   video_features_device  reference models/tav.py:51-121   decoded uint8 frames -> the normalised, resized clip, one HIP launch per clip
+  speech_features_device reference models/tav.py:165-169  decoded PCM -> the mono 16 kHz waveform, one HIP launch per utterance
 
 Same constructor arguments, forward() signatures and state_dict keys.  `from_pretrained` checkpoints are not
 reachable offline, so sub-models are built from a geometry preset (config.py) and initialised randomly; load a
@@ -558,6 +559,54 @@ def _decoded_video(v):
     return None
 
 
+def _pcm_tensor(pcm):
+    """Decoded PCM as the kernel takes it: int16 stays int16, every float type becomes float32."""
+    pcm = torch.as_tensor(pcm)
+    if pcm.dtype == torch.int16:
+        return pcm
+    if not pcm.dtype.is_floating_point:
+        raise TypeError(f"decoded PCM must be int16 or floating point, got {pcm.dtype}")
+    return pcm.float()
+
+
+def _resampled_length_checked(pcm, sampling_rate, target_sampling_rate, layout=None):
+    """L_out of one utterance, known on the host; ValueError for an empty waveform and where the reference's .squeeze() changes meaning."""
+    lay = ops.pcm_layout(pcm, layout)
+    nch, n = (1, pcm.shape[0]) if lay == "L" else (pcm.shape if lay == "CL" else pcm.shape[::-1])
+    if n < 1 or nch < 1:
+        raise ValueError(f"speech_features_device: empty waveform {tuple(pcm.shape)}")
+    l_out = ops.resampled_length(n, sampling_rate, target_sampling_rate)
+    if nch > 1 and l_out == 1:
+        raise ValueError(f"speech_features_device: {nch} channels of one resampled sample each -- the reference's .squeeze() leaves [{nch}] and "
+                         "its mean would run over the channels' place, not over them")
+    return lay, l_out
+
+
+def speech_features_device(pcm, sampling_rate, out=None, mask=None, device="cuda", target_sampling_rate=16000, layout=None):
+    """speech_file_to_array_fn (reference models/tav.py:165-169) after the decoder, on the device: torchaudio's Resample(sampling_rate,
+    16000), .squeeze() and the mean over the channels in ONE HIP launch (ops.audio_resample).  pcm: int16 or float, mono [L], planar [C, L]
+    (torchaudio.load) or interleaved [L, C], on the host or on the device.  Host PCM is shipped once, from pinned memory, non-blocking --
+    int16 as int16 (two bytes per sample on the link; the kernel scales by 2^-15 as torchaudio.load does); device PCM is read where it lies.
+    -> a 1-D f32 tensor of L_out = ceil(16000 L / sampling_rate) samples, or `out` (a row of the batch: samples, then 0.0) and `mask` (1.0
+    for the samples, then 0.0), both written in full.  There is no host form: without a GPU this raises."""
+    pcm = _pcm_tensor(pcm)
+    lay, _ = _resampled_length_checked(pcm, sampling_rate, target_sampling_rate, layout)
+    if not pcm.is_cuda:
+        dev = _dev(device)
+        staged = torch.empty(pcm.shape, dtype=pcm.dtype, pin_memory=True)
+        staged.copy_(pcm)
+        pcm = staged.to(dev, non_blocking=True)
+    table = ops.audio_resample_table(sampling_rate, target_sampling_rate, device=pcm.device)
+    return ops.audio_resample(pcm, table, out=out, mask=mask, layout=lay)
+
+
+def _decoded_audio(a):
+    """(pcm, sampling_rate) when a collate item's audio entry is decoded PCM -- {"pcm": ..., "sampling_rate": ...} -- else None."""
+    if isinstance(a, dict):
+        return a["pcm"], int(a["sampling_rate"])
+    return None
+
+
 def _draw_visual_mask(B, ntok):
     """reference :207-209: True w.p. 1/15 per token, drawn on the host (per-row counts Binomial(ntok, 1/15), unequal)."""
     m = torch.randint(-13, 2, (B, ntok))
@@ -580,6 +629,9 @@ def collate_batch(batch, check, visual_rows="equal", bucket=None):
     for (inp, label) in batch:
         texts.append(torch.as_tensor(inp[0]["input_ids"]).reshape(-1))
         masks.append(torch.as_tensor(inp[0]["attention_mask"]).reshape(-1).float())
+        if _decoded_audio(inp[1]) is not None:
+            raise ValueError("collate_batch takes finished 16 kHz waveforms: decoded PCM is resampled by the HIP kernel only "
+                             "(there is no CPU fallback) -- use collate_batch_device")
         speech.append(torch.as_tensor(inp[1]).float().reshape(-1))
         if _decoded_video(inp[2]) is not None:
             raise ValueError("collate_batch takes finished float clips: decoded uint8 frames are transformed by the HIP kernel only "
@@ -631,26 +683,45 @@ def collate_batch_device(batch, check, device="cuda", n_visual_true=None, genera
     Decoded items: the video entry may be uint8 frames ([T, H, W, 3] or [3, T, H, W]) or {"frames": ..., "speaker": ...} instead of a
     finished float clip.  The [B, num_frames, 3, size, size] batch is then allocated once and video_features_device(frames, speaker, check)
     fills each clip's slab with one launch (no stack copy), drawing its augmentation from torch's global CPU generator or clip_generator,
-    item by item in batch order, before any mask is drawn.  A batch is all decoded or all float."""
+    item by item in batch order, before any mask is drawn.  A batch is all decoded or all float.
+    Decoded audio: the audio entry may be {"pcm": tensor, "sampling_rate": int} (int16 or float; [L], [C, L] or [L, C]) instead of a finished
+    16 kHz waveform.  T = max_b L_out_b is known on the host; audio [B, T] and its mask are then allocated uninitialised and
+    speech_features_device fills each item's two rows with one launch (no pad_sequence, no arange mask).  It draws no random number.  A
+    batch is all PCM or all finished waveforms."""
     runtime.check_visual_rows(visual_rows, bucket)
     texts, masks, speech, vids, labels = [], [], [], [], []
     decoded = [_decoded_video(inp[2]) for (inp, _) in batch]
     if any(d is not None for d in decoded) and not all(d is not None for d in decoded):
         raise ValueError("collate_batch_device: a batch holds either decoded frames or finished float clips, not both")
-    for (inp, label), d in zip(batch, decoded):
+    pcms = [_decoded_audio(inp[1]) for (inp, _) in batch]
+    if any(p is not None for p in pcms) and not all(p is not None for p in pcms):
+        raise ValueError("collate_batch_device: a batch holds either decoded PCM or finished 16 kHz waveforms, not both")
+    for (inp, label), d, p in zip(batch, decoded, pcms):
         texts.append(torch.as_tensor(inp[0]["input_ids"]).reshape(-1))
         masks.append(torch.as_tensor(inp[0]["attention_mask"]).reshape(-1).float())
-        speech.append(torch.as_tensor(inp[1]).float().reshape(-1))
+        if p is None:
+            speech.append(torch.as_tensor(inp[1]).float().reshape(-1))
         if d is None:
             v = torch.as_tensor(inp[2]).float()
             vids.append(v if v.shape[1] == 3 else v.permute(1, 0, 2, 3))
         labels.append(float(label))
     B = len(labels)
     dev = torch.device(device)
-    lens = torch.tensor([len(s) for s in speech])
-    T = int(lens.max())
-    audio = torch.nn.utils.rnn.pad_sequence([s.to(dev, non_blocking=True) for s in speech], batch_first=True)          # zero padding, reference :228
-    amask = (torch.arange(T, device=dev)[None, :] < lens.to(dev, non_blocking=True)[:, None]).float()
+    if speech:
+        lens = torch.tensor([len(s) for s in speech])
+        T = int(lens.max())
+        audio = torch.nn.utils.rnn.pad_sequence([s.to(dev, non_blocking=True) for s in speech], batch_first=True)      # zero padding, reference :228
+        amask = (torch.arange(T, device=dev)[None, :] < lens.to(dev, non_blocking=True)[:, None]).float()
+    else:
+        if dev.type != "cuda":
+            raise ValueError(f"collate_batch_device(device={str(dev)!r}): decoded PCM is resampled by the HIP kernel on the GPU only; "
+                             "there is no CPU fallback")
+        pcms = [(_pcm_tensor(p), sr) for (p, sr) in pcms]
+        T = max(_resampled_length_checked(p, sr, 16000)[1] for (p, sr) in pcms)
+        audio = torch.empty(B, T, dtype=torch.float32, device=_dev(dev))
+        amask = torch.empty(B, T, dtype=torch.float32, device=audio.device)
+        for b, (p, sr) in enumerate(pcms):
+            speech_features_device(p, sr, out=audio[b], mask=amask[b], device=audio.device)
     if vids:
         video = torch.stack([v.to(dev, non_blocking=True) for v in vids])
     else:

@@ -4,8 +4,10 @@ No arithmetic happens here; torch is used for device memory and streams only.  S
 (name, stream) so that concurrent branches on different HIP streams never share a workspace.
 """
 import ctypes as C
+import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -719,6 +721,143 @@ def video_clip_transform(src, out, xform):
     if src.storage_offset() + last >= src.untyped_storage().nbytes() // src.element_size():
         raise ValueError("video_clip_transform: the transform's sizes and strides reach past the source tensor's storage")
     check(lib().tav_video_clip_transform(ptr(src), ptr(out), C.byref(xform), stream()), "video_clip_transform")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- audio waveform transform
+_resample_tables = {}
+
+
+def resample_ratio(sr, target=16000):
+    """(o, n) = (sr / g, target / g), g = gcd(sr, target)."""
+    sr, target = int(sr), int(target)
+    if sr < 1 or target < 1:
+        raise ValueError(f"sampling rates must be positive, got {sr} -> {target}")
+    g = math.gcd(sr, target)
+    return sr // g, target // g
+
+
+def resampled_length(L, sr, target=16000):
+    """Samples torchaudio's Resample(sr, target) returns for L: ceil(target * L / sr), in integers."""
+    o, n = resample_ratio(sr, target)
+    return (n * int(L) + o - 1) // o
+
+
+def sinc_resample_coefficients(sr, target=16000):
+    """torchaudio's _get_sinc_resample_kernel at Resample's defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99, dtype None):
+    fp64 arithmetic, rounded once to f32.  -> (h f32 [n][2 width + o], o, n, width), numpy."""
+    o, n = resample_ratio(sr, target)
+    base = min(o, n) * 0.99
+    width = math.ceil(6 * o / base)
+    k = np.arange(-width, width + o, dtype=np.float64)[None, :] / o
+    p = np.arange(0, -n, -1, dtype=np.float64)[:, None] / n
+    t = np.clip((p + k) * base, -6.0, 6.0)
+    win = np.cos(t * math.pi / 6 / 2) ** 2
+    t = t * math.pi
+    with np.errstate(invalid="ignore", divide="ignore"):
+        h = np.where(t == 0, 1.0, np.sin(t) / t) * win * (base / o)
+    return h.astype(np.float32), o, n, width
+
+
+class ResampleTable:
+    """The compact filter of one (sr, target) pair on one device: table f32 [n, ntap] and first int32 [n] there (row p holds taps first[p] ..
+    first[p] + ntap - 1 of phase p, zero-filled past its own live taps), their host copies (h, first_host) and o, n, width, ntap, tile."""
+
+    def __init__(self, sr, target, device):
+        self.sr, self.target = int(sr), int(target)
+        if self.sr == self.target:                                      # Resample.forward returns its input: one phase, the one tap 1.0
+            self.o, self.n, self.width = 1, 1, 0
+            self.h, self.first_host = np.ones((1, 1), np.float32), np.zeros(1, np.int32)
+        else:
+            full, self.o, self.n, self.width = sinc_resample_coefficients(sr, target)
+            K = full.shape[1]
+            nz = full != 0
+            lo, hi = nz.argmax(1), K - 1 - nz[:, ::-1].argmax(1)
+            ntap = int((hi - lo + 1).max())
+            self.first_host = np.minimum(lo, K - ntap).astype(np.int32)
+            cols = self.first_host[:, None] + np.arange(ntap)[None, :]
+            self.h = np.ascontiguousarray(np.take_along_axis(full, cols, 1))
+            kept = np.zeros_like(nz)
+            np.put_along_axis(kept, cols, True, 1)
+            assert np.all(full[~kept] == 0.0), "a tap outside the compact table is not 0.0f"
+        self.ntap = self.h.shape[1]
+        self.first_max = int(self.first_host.max())
+        assert self.first_host.min() >= 0 and self.first_max + self.ntap <= 2 * self.width + self.o
+        self.tile = int(lib().tav_audio_resample_tile(self.o, self.n, self.width))
+        if self.tile == 0:
+            raise ValueError(f"audio_resample_table: {self.sr} -> {self.target} Hz (o / n = {self.o} / {self.n}) needs a longer input span per "
+                             "workgroup than the kernel keeps in LDS")
+        self.device = torch.device(device)
+        self.table = torch.from_numpy(self.h).to(self.device)
+        self.first = torch.from_numpy(self.first_host).to(self.device)
+
+
+def audio_resample_table(sr, target=16000, device="cuda"):
+    """The ResampleTable of (sr, target) on `device`: computed in fp64 numpy, rounded to f32, compacted (every dropped tap is asserted to be
+    0.0f), uploaded once and cached."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(sr), int(target), str(device))
+    if key not in _resample_tables:
+        _resample_tables[key] = ResampleTable(sr, target, device)
+    return _resample_tables[key]
+
+
+def pcm_layout(src, layout=None):
+    """Layout of decoded PCM: "L" (mono [L]), "CL" (planar [C, L], torchaudio.load) or "LC" (interleaved [L, C], a decoder's frames).  A 2-D
+    tensor's shorter axis is taken as the channels (planar when equal); `layout` overrides."""
+    if layout is None:
+        layout = "L" if src.dim() == 1 else ("CL" if src.dim() == 2 and src.shape[0] <= src.shape[1] else "LC")
+    if layout not in ("L", "CL", "LC") or src.dim() != (1 if layout == "L" else 2):
+        raise ValueError(f"PCM: need [L], [C, L] or [L, C], got {tuple(src.shape)} as {layout}")
+    return layout
+
+
+def resample_args(src, table, T_row=None, layout=None):
+    """The tav_resample_args of one utterance: src's channel count, length and element strides, the table's rate pair, the row length
+    (L_out when None)."""
+    layout = pcm_layout(src, layout)
+    if src.dtype not in (torch.int16, torch.float32):
+        raise TypeError(f"PCM must be int16 or float32, got {src.dtype}")
+    a = L.ResampleArgs()
+    a.src_dtype = L.TAV_I16 if src.dtype == torch.int16 else L.TAV_F32
+    if layout == "L":
+        a.C, a.L, a.sC, a.sL = 1, src.shape[0], 0, src.stride(0)
+    elif layout == "CL":
+        (a.C, a.L), (a.sC, a.sL) = src.shape, src.stride()
+    else:
+        (a.L, a.C), (a.sL, a.sC) = src.shape, src.stride()
+    a.o, a.n, a.width, a.ntap, a.first_max = table.o, table.n, table.width, table.ntap, table.first_max
+    L_out = (a.n * a.L + a.o - 1) // a.o
+    a.T_row = L_out if T_row is None else int(T_row)
+    return a
+
+
+def audio_resample(src, table, out=None, mask=None, layout=None):
+    """tav_audio_resample: src (device, int16 or f32; [L], [C, L] or [L, C], any strides) through `table` (audio_resample_table) -> out, a 1-D
+    f32 row of at least L_out elements with unit stride -- a row of the batch tensor or, with out=None, a new tensor of L_out.  The row is
+    written in full: the samples, then 0.0; so is `mask` (same length): 1.0 for the samples, then 0.0.  One launch."""
+    if not src.is_cuda:
+        raise ValueError("audio_resample runs on the GPU only (libtavhip has no host form): move the PCM to the device, or use "
+                         "models.tav.speech_features_device, which ships it once")
+    a = resample_args(src, table, None if out is None else out.numel(), layout)
+    if a.C < 1 or a.L < 1:
+        raise ValueError(f"audio_resample: empty waveform {tuple(src.shape)}")
+    if a.T_row < resampled_length(a.L, table.sr, table.target):
+        raise ValueError(f"audio_resample: out holds {a.T_row} elements, the resampled waveform has {resampled_length(a.L, table.sr, table.target)}")
+    if out is None:
+        out = torch.empty(a.T_row, dtype=torch.float32, device=src.device)
+    for name, t in (("out", out), ("mask", mask)):
+        if t is not None and (t.dim() != 1 or t.numel() != a.T_row or t.dtype != torch.float32 or (t.numel() > 1 and t.stride(0) != 1) or
+                              t.device != src.device):
+            raise ValueError(f"audio_resample: {name} must be a 1-D float32 row of {a.T_row} elements with unit stride on {src.device}, "
+                             f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+    if table.table.device != src.device:
+        raise ValueError(f"audio_resample: the table lives on {table.table.device}, the PCM on {src.device}")
+    if src.storage_offset() + (a.C - 1) * a.sC + (a.L - 1) * a.sL >= src.untyped_storage().nbytes() // src.element_size():
+        raise ValueError("audio_resample: the sizes and strides reach past the source tensor's storage")
+    check(lib().tav_audio_resample(ptr(src), ptr(table.table), ptr(table.first), ptr(out), ptr(mask), C.byref(a), stream()), "audio_resample")
     return out
 
 

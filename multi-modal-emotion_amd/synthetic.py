@@ -43,11 +43,13 @@ def make_batch(cfg, batch_size, *, seed=1234, s_text=128, t_audio=80000, n_visua
     return [text, audio_d, visual], labels.to(device)
 
 
-def make_items(cfg, n, *, raw_video=None, seed=1234, s_text=128, t_audio=80000, speakers=None):
+def make_items(cfg, n, *, raw_video=None, seed=1234, s_text=128, t_audio=80000, speakers=None, raw_audio=None):
     """n seeded items in the collate contract, ([{"input_ids", "attention_mask"}, waveform, video], label), with waveforms of unequal length.
     raw_video=None: video is a finished float clip [frames, 3, image, image].  raw_video=(T, H, W): video is what a decoder yields, uint8
     [T, H, W, 3] frames -- for models.tav.collate_batch_device / video_features_device, which transform them on the device.  speakers: one
-    entry per item (None, True, False) wraps the frames as {"frames", "speaker"}."""
+    entry per item (None, True, False) wraps the frames as {"frames", "speaker"}.  raw_audio=(sampling_rate, channels): the waveform is what
+    an audio decoder yields, {"pcm": int16 [L, channels], "sampling_rate"}, L = the float waveform's length (for
+    models.tav.collate_batch_device / speech_features_device, which resample it on the device)."""
     g = torch.Generator(device="cpu").manual_seed(seed)
     tc, vc = cfg["text"], cfg["video"]
     items = []
@@ -55,6 +57,9 @@ def make_items(cfg, n, *, raw_video=None, seed=1234, s_text=128, t_audio=80000, 
         ids = torch.randint(3, tc["vocab"], (s_text,), generator=g)
         text = {"input_ids": ids, "attention_mask": torch.ones(s_text)}
         wave = torch.randn(t_audio - (i * 997) % max(t_audio // 2, 1), generator=g) * 0.1
+        if raw_audio is not None:
+            pcm = torch.randint(-32768, 32768, (len(wave), raw_audio[1]), generator=g, dtype=torch.int16)
+            wave = {"pcm": pcm, "sampling_rate": int(raw_audio[0])}
         if raw_video is None:
             video = torch.randn(vc["frames"], 3, vc["image"], vc["image"], generator=g)
         else:
