@@ -20,21 +20,10 @@
 #include <type_traits>
 #include "tavhip_internal.h"
 
-// A/B switches (tools/ab_build.sh): issue all LDS fragment reads of a tile ahead of its first MFMA
-#ifndef TAV_HOIST_FWD
-#define TAV_HOIST_FWD 0      // 1 needs 204 VGPRs (two waves per SIMD); without it the kernel fits three (165) and is 4-9 % faster
-#endif
-// (the same hoisting in the two backward kernels measured -1 %: not built)
-// forward kernel, bf16: K / V tiles staged by LDS-DMA (global_load_lds_dwordx4) into swizzled ROW images instead of registers + ds_write
-#ifndef TAV_ATT_DMA
-#define TAV_ATT_DMA 1      // 0: register staging (322 us at S = 1464, batch 32), 1: DMA one tile ahead (300-312), 2: two tiles ahead, unmasked mode (315)
-#endif
-#ifndef TAV_DKDV_BQ
-#define TAV_DKDV_BQ 64       // bf16 query-tile height of the dK/dV kernel (32 or 64)
-#endif
-#ifndef TAV_DKDV_FAST32
-#define TAV_DKDV_FAST32 1    // the unmasked pre-scaled bf16 dK/dV kernel (video / audio stacks) on 32-query tiles at THREE waves per SIMD (168 VGPRs, no scratch)
-#endif
+// Staging.  bf16: the streamed K / V (forward, dQ) and Q / dO (dK/dV) tiles go by LDS-DMA (global_load_lds_dwordx4) into swizzled ROW images,
+// one tile ahead (forward at S = 1464, batch 32: 300-312 us; through registers + ds_write 322; two tiles ahead 315).  f32 stages through registers.
+// LDS fragment reads are issued where they are used: hoisting a tile's reads ahead of its first MFMA needs 204 VGPRs in the forward (two waves
+// per SIMD; without it the kernel fits three at 165 and is 4-9 % faster) and measured -1 % in the two backward kernels.
 
 namespace tav {
 
@@ -59,12 +48,9 @@ template <bool LEN> using AttnArg = std::conditional_t<LEN, AttnPL, AttnP>;
 // tiles of a slice were dealt round-robin over the 8 XCDs and every L2 fetched every slice (round-3 PMC at the video shape: 1310 MB moved
 // per forward launch against 288 MB algorithmic).  Resident set per XCD at S = 1464: 32 CUs x 3 workgroups / 12 tiles = 8 slices x 375 KB
 // of K + V = 3 MB of the 4 MiB L2.  Placement is a speed matter only (the dispatcher's round-robin is observed, not promised).
-#ifndef TAV_ATT_XCD
-#define TAV_ATT_XCD 1      // 0: tiles dealt in plain id order (rounds 1-3), kept for A/B builds
-#endif
 struct AttnTile { int x, head, b; };
 TAV_DEV AttnTile attn_tile(const AttnP& p) {
-    const int id = TAV_ATT_XCD ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+    const int id = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int hb = id / p.tiles, b = hb / p.nh;
     AttnTile w;                    // (pinned to SGPRs: the slice bases feed the scalar operand of the LDS-DMA asm)
     w.x = to_sgpr(id - hb * p.tiles); w.head = to_sgpr(hb - b * p.nh); w.b = to_sgpr(b);
@@ -247,57 +233,29 @@ template <int ROWS = 64> struct PairDmaT {
 using PairDma = PairDmaT<64>;
 
 // ================================================================================================= forward
-// ablation switches for the forward kernel (tools/ab_build.sh; timing experiments only, results are wrong with any of them set)
-#ifdef TAV_ABL_ATT_NOMFMA
-#define ATT_FWD_MMA(a, b, c) do { (c)[0] += __uint_as_float((a).x ^ (b).x); } while (0)
-#else
-#define ATT_FWD_MMA(a, b, c) mma16<T>(a, b, c)
-#endif
-#ifdef TAV_ABL_ATT_NOEXP
-#define ATT_FWD_EXP2(x) ((x) * 0.5f)
-#else
-#define ATT_FWD_EXP2(x) fast_exp2(x)
-#endif
-#ifdef TAV_ABL_ATT_NOGLOAD
-constexpr bool ATT_ABL_NOGLOAD = true;
-#else
-constexpr bool ATT_ABL_NOGLOAD = false;
-#endif
-#ifdef TAV_ABL_ATT_NOBAR
-constexpr bool ATT_ABL_NOBAR = true;
-#else
-constexpr bool ATT_ABL_NOBAR = false;
-#endif
-#ifndef TAV_ATT_FWD_OCC
-#define TAV_ATT_FWD_OCC 3      // waves per SIMD the forward kernel is compiled for (register budget 512 / OCC; 4 spills and halves the speed)
-#endif
+constexpr int ATT_FWD_OCC = 3;       // waves per SIMD the forward kernel is compiled for (register budget 512 / OCC; 4 spills and halves the speed)
 // Lazy running maximum (PRE kernels): the accumulated O / l are rescaled only when a tile's scores exceed the reference exponent by more
 // than this many binary orders of magnitude; until then p = exp2(s - m_ref) may grow to 2^THR, which f32 accumulators and bf16 operands
 // (8-bit exponent) carry without loss.
-#ifndef TAV_ATT_LAZY_THR
-#define TAV_ATT_LAZY_THR 12.0f
-#endif
+constexpr float ATT_LAZY_THR = 12.0f;
 // PRE: q is pre-multiplied by scale * log2(e) (the engine folds the factor into the q rows of the QKV weight copy: no extra rounding), so
 // S^T = K q~^T is already the exp2-domain logit.  The unmasked, full tiles then take a fast path built for the VALU issue port, which is
 // what bounds this kernel at head dim 64 (rocprof r03: the port is 81 % busy, the matrix pipe 39 %):
 //   * the running reference exponent enters as the C operand of the first QK^T MFMA (-m on every row of the query's column), so the
 //     accumulators come out as s - m and p = exp2(acc): no fma per score;
-//   * O / l are rescaled only when the tile maximum passes the reference by TAV_ATT_LAZY_THR (rare after the first tile);
+//   * O / l are rescaled only when the tile maximum passes the reference by ATT_LAZY_THR (rare after the first tile);
 //   * ring slot, LDS addresses and the DMA source walk are compile-time / scalar: the loop body is instantiated once per slot.
-#ifndef TAV_ATT_FWD_NQ
-#define TAV_ATT_FWD_NQ 2     // 16-query tiles per wave of the unmasked pre-scaled bf16 forward (3: K/V fragment reads, DMA and barriers amortised over 1.5x the MFMAs; two waves per SIMD)
-#endif
-template <typename T, int MODE, bool PRE> constexpr int fwd_nq() { return (sizeof(T) == 2 && MODE == 0 && PRE) ? TAV_ATT_FWD_NQ : 2; }
+constexpr int ATT_FWD_NQ = 2;        // 16-query tiles per wave: 32 queries per wave, 128 per workgroup
 template <typename T, int MODE, bool PRE, bool LEN = false>
-__global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_OCC)) void attn_fwd_kernel(const AttnArg<LEN> p) {
-    constexpr int NQ = fwd_nq<T, MODE, PRE>();             // 16-query tiles per wave (2; 3 = 48 queries per wave, 192 per workgroup)
+__global__ __launch_bounds__(256, ATT_FWD_OCC) void attn_fwd_kernel(const AttnArg<LEN> p) {
+    constexpr int NQ = ATT_FWD_NQ;
     using H = HD<T>;
     constexpr int ES = H::ES, NSD = H::NSD, KSTEP = ET<T>::KSTEP, BKV = 64;
     constexpr int NCH = BKV * H::ROWCH / 256;
     // bf16: both tiles live in the swizzled row image (H::row_off), which is linear per 8 rows -- one DMA instruction fills 8 rows x 8
     // slots, the XOR applied to the SOURCE chunk a lane fetches -- and serves the row reads (K) as well as the transposed reads (V,
     // frag_tr_rowimg).  f32 keeps the register path and the padded natural V image.
-    constexpr bool DMA = (ES == 2) && TAV_ATT_DMA;
+    constexpr bool DMA = ES == 2;
     constexpr int KROW_B = BKV * H::ROWB, VNAT_B = DMA ? BKV * H::ROWB : BKV * H::PITCH_N;
     constexpr int BUF_B = KROW_B + VNAT_B + 2 * BKV * 4;
     constexpr int NBUF = 2;
@@ -422,7 +380,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
         constexpr bool KADD = decltype(kadd_tag)::value != 0;
         constexpr int NEXT = decltype(next_tag)::value;
         const int cur = t & 1, nxt = cur ^ 1;
-        if constexpr (NEXT != 0 && !ATT_ABL_NOGLOAD) {           // (slot nxt was last read in iteration t-1, behind a barrier)
+        if constexpr (NEXT != 0) {                                         // (slot nxt was last read in iteration t-1, behind a barrier)
             if constexpr (DMA) dma(t + 1, nxt, std::integral_constant<int, NEXT == 2>{});
             gload(t + 1);
         }
@@ -444,7 +402,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
 #pragma unroll
                     for (int qt = 0; qt < NQ; ++qt) {
                         if (s == 0) sacc[kt][qt] = cinit[qt];
-                        ATT_FWD_MMA(a, qf[qt][s], sacc[kt][qt]);
+                        mma16<T>(a, qf[qt][s], sacc[kt][qt]);
                     }
                 }
         };
@@ -467,7 +425,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
                 }
                 m0 = __builtin_elementwise_maximum(m0, sacc[3][qt][3]);
                 mx[qt] = max_over_row_groups(m0);
-                grow |= mx[qt] > TAV_ATT_LAZY_THR;
+                grow |= mx[qt] > ATT_LAZY_THR;
             }
             if (__any(grow)) {                                     // rare after the first tile: move the reference, THEN take the common path
 #pragma unroll
@@ -478,7 +436,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
 #pragma unroll
                     for (int kt = 0; kt < 4; ++kt) sacc[kt][qt] -= shift;
                     if (!first) {                                   // (O = l = 0 on the first tile; exp2(-shift) could overflow there)
-                        const float al = ATT_FWD_EXP2(-shift);
+                        const float al = fast_exp2(-shift);
                         lacc[qt] *= al;
 #pragma unroll
                         for (int dt = 0; dt < 4; ++dt) oacc[dt][qt] *= al;
@@ -490,7 +448,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) sacc[kt][qt][r] = ATT_FWD_EXP2(sacc[kt][qt][r]);
+                    for (int r = 0; r < 4; ++r) sacc[kt][qt][r] = fast_exp2(sacc[kt][qt][r]);
         } else {
             f32x4 zero2[NQ];
 #pragma unroll
@@ -517,13 +475,13 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
 #pragma unroll
                 for (int qt = 0; qt < NQ; ++qt) {
                     const float m_new = fmaxf(m_run[qt], max_over_row_groups(mx[qt]));
-                    alpha[qt] = ATT_FWD_EXP2(m_run[qt] - m_new);
+                    alpha[qt] = fast_exp2(m_run[qt] - m_new);
                     moved |= m_new > m_run[qt];
                     m_run[qt] = m_new;
 #pragma unroll
                     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) sacc[kt][qt][r] = ATT_FWD_EXP2(sacc[kt][qt][r] - m_new);
+                        for (int r = 0; r < 4; ++r) sacc[kt][qt][r] = fast_exp2(sacc[kt][qt][r] - m_new);
                 }
             } else {
 #pragma unroll
@@ -533,13 +491,13 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
                     for (int kt = 1; kt < 4; ++kt)
                         mx = fmaxf(fmaxf(mx, sacc[kt][qt][0]), fmaxf(sacc[kt][qt][1], fmaxf(sacc[kt][qt][2], sacc[kt][qt][3])));
                     const float m_new = fmaxf(m_run[qt], max_over_row_groups(mx) * c2);
-                    alpha[qt] = ATT_FWD_EXP2(m_run[qt] - m_new);
+                    alpha[qt] = fast_exp2(m_run[qt] - m_new);
                     moved |= m_new > m_run[qt];
                     m_run[qt] = m_new;
 #pragma unroll
                     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) sacc[kt][qt][r] = ATT_FWD_EXP2(__builtin_fmaf(sacc[kt][qt][r], c2, -m_new));
+                        for (int r = 0; r < 4; ++r) sacc[kt][qt][r] = fast_exp2(__builtin_fmaf(sacc[kt][qt][r], c2, -m_new));
                 }
             }
             if (__any(moved)) {        // wave-uniform: after the first tiles the running max rarely moves, skip 34 multiplies
@@ -565,7 +523,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
                 pb[qt] = acc_to_kfrag<T>(tl);
             }
 #pragma unroll
-            for (int qt = 0; qt < NQ; ++qt) ATT_FWD_MMA(ones_v, pb[qt], lacc[qt]);
+            for (int qt = 0; qt < NQ; ++qt) mma16<T>(ones_v, pb[qt], lacc[qt]);
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 uint4 a;
@@ -576,7 +534,7 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
                 }
                 else a = frag_kstrided<T>(Vnat, H::PITCH_N, ks * KSTEP, 16 * dt, lane);
 #pragma unroll
-                for (int qt = 0; qt < NQ; ++qt) ATT_FWD_MMA(a, pb[qt], oacc[dt][qt]);
+                for (int qt = 0; qt < NQ; ++qt) mma16<T>(a, pb[qt], oacc[dt][qt]);
             }
         }
         if (MODE == 2) {   // c[d] += sum_key mask[key] * V[key][d]; thread -> (d = tid & 63, 16 keys of this tile)
@@ -588,9 +546,9 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
                 else corr_part += cm[key] * ET<T>::ld(reinterpret_cast<const T*>(Vnat + key * H::PITCH_N) + d);
             }
         }
-        if constexpr (NEXT != 0 && !ATT_ABL_NOGLOAD && (MODE != 0 || NEXT == 2 || !DMA)) lstore(t + 1, nxt);   // (unmasked: only the last tile has per-key terms)
+        if constexpr (NEXT != 0 && (MODE != 0 || NEXT == 2 || !DMA)) lstore(t + 1, nxt);   // (unmasked: only the last tile has per-key terms)
         if constexpr (DMA) wait_vmcnt0();                     // tile t+1 has landed
-        if (!ATT_ABL_NOBAR) __syncthreads();
+        __syncthreads();
     };
     using K0 = std::integral_constant<int, (MODE == 1) ? 1 : 0>;      // middle tiles carry per-key terms only under the pre-softmax mask
     int t = 0;
@@ -640,229 +598,21 @@ __global__ __launch_bounds__(256, (fwd_nq<T, MODE, PRE>() > 2 ? 2 : TAV_ATT_FWD_
     }
 }
 
-// ================================================================================================= forward, 32x32x16 MFMA shape
-// The same algorithm as attn_fwd_kernel<bf16, 0, true> (no mask, pre-scaled q, lazy reference exponent, LDS-DMA ring) on
-// v_mfma_f32_32x32x16_bf16: a wave owns 32 queries x 64 keys per tile in 16 MFMA issues instead of 36, every lane's 32 scores of a tile belong to
-// ONE query (the running maximum needs one cross-lane step instead of two, the row sum none inside the loop), and the reference exponent is
-// one 16-register C operand.  The kernel is bound by instructions issued per SIMD (profiles/r03_experiments.md): fewer, longer MFMAs.
-//   S^T tile  (keys x queries) = K[32 keys][16 d] . Q^T[16 d][32 q]   lane (q = l % 32, h = l / 32): acc r <-> key 8 (r / 4) + 4 h + r % 4
-//   O^T tile  (d x queries)   += V^T[32 d][16 keys] . P^T[16 keys][32 q]; the k-slots of a 16-key chunk C are the keys the lane's accumulators
-//             8 c' .. 8 c' + 7 hold (16 C + 4 h + {0..3}, 16 C + 8 + 4 h + {0..3}) -- any assignment works as long as V^T's fragments use the same;
-//             M-tile T covers d in {16 T .. 16 T + 15} u {32 + 16 T .. 47 + 16 T}: two chunk pairs whose XOR-swizzled positions never share a
-//             32-byte bank window inside the 4-row block a transposed read fetches (HD<bf16>::row_off).
-// MEASURED SLOWER than the 16x16x32 kernel (video shape, batch 32: 254.6-263 us against 246.5-249 us; profiles/r03_experiments.md section 14)
-// and therefore not compiled by default: -DTAV_ATT_FWD32=1 builds it and routes the unmasked pre-scaled bf16 forward through it (all kernel
-// checks pass on it).
-#ifndef TAV_ATT_FWD32
-#define TAV_ATT_FWD32 0
-#endif
-#if TAV_ATT_FWD32
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-TAV_DEV void mma32(const uint4& a, const uint4& b, f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-#ifndef TAV_ATT_FWD32_OCC
-#define TAV_ATT_FWD32_OCC 3
-#endif
-__global__ __launch_bounds__(256, TAV_ATT_FWD32_OCC) void attn_fwd32_kernel(const AttnP p) {
-    using T = bf16;
-    using H = HD<T>;
-    constexpr int BKV = 64;
-    constexpr int KROW_B = BKV * H::ROWB, VNAT_B = BKV * H::ROWB;
-    constexpr int BUF_B = KROW_B + VNAT_B + 2 * BKV * 4;       // (the layout of attn_fwd_kernel: K image, V image, per-key terms)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lq = lane & 31, h = lane >> 5;
-    const AttnTile wg = attn_tile(p);
-    const int head = wg.head, b = wg.b, S = p.S;
-    const int q0 = wg.x * 128 + wave * 32;
-    const long hoff = (long)head * 64 * 2;
-    const char* Qb = p.q + (long)b * S * p.ld_q * 2 + hoff;
-    const char* Kb = p.k + (long)b * S * p.ld_k * 2 + hoff;
-    const char* Vb = p.v + (long)b * S * p.ld_v * 2 + hoff;
-
-    uint4 qf[4];                                              // Q[q][16 s + 8 h .. + 7]
-    {
-        int r = q0 + lq; r = r < S ? r : S - 1;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const uint4*>(Qb + (long)r * p.ld_q * 2 + (2 * s + h) * 16);
-    }
-    // lane constants of the LDS reads; key rows / chunks of 16 keys / the ring slot are immediates or one scalar add away
-    unsigned koff[4], vtoff[2];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) { koff[s] = (unsigned)H::row_off(lq, 2 * s + h); asm volatile("" : "+v"(koff[s])); }
-    {
-        const int g = lane >> 4, i = lane & 15, q4 = i >> 2, pp = i & 3;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int d0 = ((g & 1) ? 32 : 0) + 16 * tt;
-            vtoff[tt] = (unsigned)(H::row_off(4 * h + q4, d0 / 8 + (pp >> 1)) + 8 * (pp & 1));
-            asm volatile("" : "+v"(vtoff[tt]));
-        }
-    }
-    float m_run = -1e30f;
-    f32x16 mneg, oacc[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { mneg[r] = 0.f; oacc[0][r] = 0.f; oacc[1][r] = 0.f; }
-    f32x2_t l2 = {0.f, 0.f};                                  // this lane's share of sum_key p (its 32 keys per tile); halves joined at the end
-
-    const int nkt = (S + BKV - 1) / BKV;
-    PairDma kv;
-    kv.init(Kb, Vb, p.ld_k * 2, p.ld_v * 2, S, smem, smem + KROW_B, tid);
-    auto dma = [&](int t, int buf, auto ragged_tag) __attribute__((always_inline)) {
-        kv.template issue<decltype(ragged_tag)::value != 0>(t, (unsigned)(buf * BUF_B));
-    };
-    auto store_kadd = [&](int t, int buf) {                   // -inf for the keys past S of the (ragged) last tile
-        if (tid < BKV) reinterpret_cast<float*>(smem + buf * BUF_B + KROW_B + VNAT_B)[tid] = (t * BKV + tid < S) ? 0.f : -INFINITY;
-    };
-    using TagNo = std::integral_constant<int, 0>;
-    using TagYes = std::integral_constant<int, 1>;
-    if (nkt == 1) { dma(0, 0, TagYes{}); store_kadd(0, 0); } else dma(0, 0, TagNo{});
-#pragma unroll
-    for (int s = 0; s < 4; ++s) settle(qf[s]);
-    wait_vmcnt0();
-    __syncthreads();
-
-    // One K/V tile.  LAST (compile time): the tile adds the per-key terms (-inf past S).  NEXT: 0 no prefetch, 1 regular, 2 ragged tile.
-    auto tile_body = [&](const int t, auto last_tag, auto next_tag) __attribute__((always_inline)) {
-        constexpr bool LAST = decltype(last_tag)::value != 0;
-        constexpr int NEXT = decltype(next_tag)::value;
-        const int cur = t & 1, nxt = cur ^ 1;
-        if constexpr (NEXT != 0) dma(t + 1, nxt, std::integral_constant<int, NEXT == 2>{});
-        const char* Krow = smem + cur * BUF_B;
-        const char* Vimg = Krow + KROW_B;
-        f32x16 sacc[2];
-        uint4 kf[2][4], vf[4][2];
-        // all eight K fragments are requested before the first MFMA, all sixteen V^T fragments behind the QK^T MFMAs: they land under the
-        // softmax arithmetic (a read issued right in front of the MFMA that needs it exposes the LDS latency sixteen times per tile)
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) kf[kt][s] = *reinterpret_cast<const uint4*>(Krow + koff[s] + kt * 32 * H::ROWB);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                if (s == 0) sacc[kt] = mneg;
-                mma32(kf[kt][s], qf[s], sacc[kt]);
-            }
-#pragma unroll
-        for (int C = 0; C < 4; ++C)
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) {
-                const char* vt = Vimg + vtoff[tt] + C * 16 * H::ROWB;
-                const uint2 lo = lds_read_tr16(vt), hi = lds_read_tr16(vt + 8 * H::ROWB);
-                vf[C][tt] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-            }
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (LAST) {
-            const float* kadd = reinterpret_cast<const float*>(Vimg + VNAT_B);
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f32x4 ka = *reinterpret_cast<const f32x4*>(kadd + 32 * kt + 8 * j + 4 * h);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) sacc[kt][4 * j + r] += ka[r];
-                }
-        }
-        // sacc = s - m_ref.  Tile maximum of the lane's query over its 32 keys, then the other half's; the reference moves only when the
-        // maximum passes it by more than THR (or on the first tile, where it is still undefined: mneg = 0, sacc are the raw logits).
-        const bool first = (t == 0);
-        float m0 = vmax3(sacc[0][0], sacc[0][1], sacc[0][2]);
-#pragma unroll
-        for (int r = 3; r + 1 < 16; r += 2) m0 = vmax3(m0, sacc[0][r], sacc[0][r + 1]);
-        m0 = vmax3(m0, sacc[0][15], sacc[1][0]);
-#pragma unroll
-        for (int r = 1; r + 1 < 16; r += 2) m0 = vmax3(m0, sacc[1][r], sacc[1][r + 1]);
-        m0 = __builtin_elementwise_maximum(m0, sacc[1][15]);
-        {
-            const unsigned u = __float_as_uint(m0);
-            auto r2 = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-            m0 = vmax_raw(__uint_as_float(r2[0]), __uint_as_float(r2[1]));
-        }
-        if (__any(first || m0 > TAV_ATT_LAZY_THR)) {            // rare after the first tile: move the reference, THEN take the common path
-            const float shift = first ? m0 : fmaxf(m0, 0.f);
-            m_run = first ? shift : m_run + shift;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { mneg[r] = -m_run; sacc[0][r] -= shift; sacc[1][r] -= shift; }
-            if (!first) {
-                const float al = fast_exp2(-shift);
-                l2 *= al;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { oacc[0][r] *= al; oacc[1][r] *= al; }
-            }
-        }
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc[kt][r] = fast_exp2(sacc[kt][r]);
-        {
-            f32x2_t la = {0.f, 0.f}, lb = {0.f, 0.f};            // (two chains: sixteen dependent packed adds are a latency chain of their own)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) { la += f32x2_t{sacc[0][r], sacc[0][r + 1]}; lb += f32x2_t{sacc[1][r], sacc[1][r + 1]}; }
-            l2 += la + lb;
-        }
-        // O^T += V^T P^T, 16 keys per MFMA: chunk C = 2 kt + c' takes the accumulators 8 c' .. 8 c' + 7 of key tile kt
-#pragma unroll
-        for (int C = 0; C < 4; ++C) {
-            const int kt = C >> 1, c8 = 8 * (C & 1);
-            const uint4 pb = make_uint4(pack_bf16x2(sacc[kt][c8 + 0], sacc[kt][c8 + 1]), pack_bf16x2(sacc[kt][c8 + 2], sacc[kt][c8 + 3]),
-                                        pack_bf16x2(sacc[kt][c8 + 4], sacc[kt][c8 + 5]), pack_bf16x2(sacc[kt][c8 + 6], sacc[kt][c8 + 7]));
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) mma32(vf[C][tt], pb, oacc[tt]);
-        }
-        if constexpr (NEXT == 2) store_kadd(t + 1, nxt);
-        wait_vmcnt0();                                        // tile t+1 has landed
-        __syncthreads();
-    };
-    int t = 0;
-    for (; t + 2 < nkt; ++t) tile_body(t, TagNo{}, std::integral_constant<int, 1>{});
-    if (t + 1 < nkt) { tile_body(t, TagNo{}, std::integral_constant<int, 2>{}); ++t; }
-    tile_body(t, TagYes{}, std::integral_constant<int, 0>{});
-
-    float l = l2[0] + l2[1];
-    {
-        const unsigned u = __float_as_uint(l);
-        auto r2 = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-        l = __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
-    }
-    const int q = q0 + lq;
-    if (q < S) {
-        const float inv = 1.f / l;
-        T* orow = reinterpret_cast<T*>(p.o) + ((long)b * S + q) * p.ld_o + head * 64;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                     // accumulator rows 8 j + 4 h + {0..3} of M-tile tt
-                const int d = (j < 2 ? 8 * j : 32 + 8 * (j - 2)) + 4 * h + 16 * tt;
-                st4(orow + d, f32x4{oacc[tt][4 * j], oacc[tt][4 * j + 1], oacc[tt][4 * j + 2], oacc[tt][4 * j + 3]} * inv);
-            }
-        if (h == 0) p.lse[((long)b * p.nh + head) * S + q] = (m_run + log2f(l)) * 0.6931471805599453f;
-    }
-}
-
-#endif   // TAV_ATT_FWD32
-
 // ================================================================================================= backward: dK, dV
 // query-tile height of the dK/dV kernel: 64 for bf16 (half as many barriers and staging round trips per MFMA as 32), 32 for
 // f32 (register budget)
-template <typename T, int MODE, bool PRE> constexpr bool dkdv_fast32() { return TAV_DKDV_FAST32 && sizeof(T) == 2 && MODE == 0 && PRE; }
-template <typename T, int MODE, bool PRE> constexpr int dkdv_bq() { return sizeof(T) == 2 ? (dkdv_fast32<T, MODE, PRE>() ? 32 : TAV_DKDV_BQ) : 32; }
+// (the unmasked pre-scaled bf16 kernel -- video / audio stacks -- runs 32-query tiles at THREE waves per SIMD: 168 VGPRs, no scratch)
+template <typename T, int MODE, bool PRE> constexpr bool dkdv_fast32() { return sizeof(T) == 2 && MODE == 0 && PRE; }
+template <typename T, int MODE, bool PRE> constexpr int dkdv_bq() { return sizeof(T) == 2 ? (dkdv_fast32<T, MODE, PRE>() ? 32 : 64) : 32; }
 
 // (waves per SIMD the backward kernels are compiled for: at 3 both spill -- 48..256 B of scratch -- which halved the forward's speed when tried there)
-#ifndef TAV_ATT_DKDV_OCC
-#define TAV_ATT_DKDV_OCC 2
-#endif
-#ifndef TAV_ATT_DQ_OCC
-#define TAV_ATT_DQ_OCC 2
-#endif
+constexpr int ATT_DKDV_OCC = 2, ATT_DQ_OCC = 2;
 template <typename T, int MODE, bool PRE, bool LEN = false>
-__global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKDV_OCC)) void attn_bwd_dkdv_kernel(const AttnArg<LEN> p) {
+__global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : ATT_DKDV_OCC)) void attn_bwd_dkdv_kernel(const AttnArg<LEN> p) {
     using H = HD<T>;
     constexpr int ES = H::ES, NSD = H::NSD, KSTEP = ET<T>::KSTEP, BQ = dkdv_bq<T, MODE, PRE>(), NQT = BQ / 16;
     constexpr int NCH = BQ * H::ROWCH / 256;
-    constexpr bool DMA = (ES == 2) && TAV_ATT_DMA;              // bf16: Q / dO tiles by LDS-DMA (PairDmaT<BQ>); f32: register staging
+    constexpr bool DMA = ES == 2;                               // bf16: Q / dO tiles by LDS-DMA (PairDmaT<BQ>); f32: register staging
     constexpr int ROW_B = BQ * H::ROWB, NAT_B = H::DUAL ? 0 : BQ * H::PITCH_N;
     constexpr int BUF_B = 2 * ROW_B + 2 * NAT_B + 2 * BQ * 4;   // Qrow, dOrow, [Qnat, dOnat: f32 only], lse, delta
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1125,11 +875,11 @@ __global__ __launch_bounds__(256, (dkdv_fast32<T, MODE, PRE>() ? 3 : TAV_ATT_DKD
 
 // ================================================================================================= backward: dQ
 template <typename T, int MODE, bool PRE, bool LEN = false>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? TAV_ATT_DQ_OCC : 1)) void attn_bwd_dq_kernel(const AttnArg<LEN> p) {
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? ATT_DQ_OCC : 1)) void attn_bwd_dq_kernel(const AttnArg<LEN> p) {
     using H = HD<T>;
     constexpr int ES = H::ES, NSD = H::NSD, KSTEP = ET<T>::KSTEP, BKV = 64;
     constexpr int NCH = BKV * H::ROWCH / 256;
-    constexpr bool DMA = (ES == 2) && TAV_ATT_DMA;          // bf16: K / V tiles by LDS-DMA (PairDma), no staging registers; f32: register staging
+    constexpr bool DMA = ES == 2;                           // bf16: K / V tiles by LDS-DMA (PairDma), no staging registers; f32: register staging
     constexpr int ROW_B = BKV * H::ROWB, NAT_B = H::DUAL ? 0 : BKV * H::PITCH_N;
     constexpr int BUF_B = 2 * ROW_B + NAT_B + BKV * 4;   // Krow, Vrow, [Knat: f32 only], kadd
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1439,14 +1189,7 @@ static AttnP pack(const tav_attn_args* a) {
 }
 
 template <typename T, int MODE, bool PRE, bool LEN> static int launch_fwd(const AttnArg<LEN>& p, hipStream_t st) {
-#if TAV_ATT_FWD32
-    if constexpr (sizeof(T) == 2 && MODE == 0 && PRE && !LEN) {
-        AttnP pl = p; pl.tiles = (p.S + 127) / 128;
-        hipLaunchKernelGGL(attn_fwd32_kernel, dim3((unsigned)pl.tiles * p.nh * p.B), dim3(256), fwd_lds<bf16>(), st, pl);
-        return (int)hipGetLastError();
-    }
-#endif
-    constexpr int QW = 64 * fwd_nq<T, MODE, PRE>();          // queries per workgroup
+    constexpr int QW = 64 * ATT_FWD_NQ;                      // queries per workgroup
     AttnArg<LEN> pl = p; pl.tiles = (p.S + QW - 1) / QW;
     hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, PRE, LEN>), dim3((unsigned)pl.tiles * p.nh * p.B), dim3(256), fwd_lds<T>(), st, pl);
     return (int)hipGetLastError();

@@ -146,14 +146,9 @@ template <> TAV_DEV uint4 acc_to_kfrag<float>(const f32x4* t) {
 TAV_DEV unsigned lds_addr(const void* p) {
     return (unsigned)(uintptr_t)((__attribute__((address_space(3))) const char*)p);
 }
-// One wave instruction: lane l copies the 16 bytes at (sbase + voff_l) to LDS byte (lds_base + 16*l).  sbase (64-bit) and lds_base
-// must be wave-uniform (SGPRs), voff is the lane's 32-bit byte offset: advancing a K-tile costs ONE v_add_u32 per instruction instead
-// of a 64-bit multiply-add chain.  Issued from inline asm on purpose: hipcc would otherwise treat the DMA as a pending LDS write and
-// put `s_waitcnt vmcnt(0)` in front of every following ds_read, serialising load and compute.  The caller waits with a counted
-// vmcnt (wait_vmcnt0() in the simplest case) + a barrier before any wave reads the staged bytes.
 // A wave-uniform value the compiler computed on the VALU (integer division, ...) pinned to an SGPR.  __builtin_amdgcn_readfirstlane of a
 // value LLVM already knows to be uniform is folded away, and whether the dependent address chain then lives in SGPRs is a heuristic
-// (SIFixSGPRCopies) -- glds16_s needs its base there, so this one is opaque.
+// (SIFixSGPRCopies) -- the LDS-DMA helpers below need their bases there, so this one is opaque.
 // The hazard recognizer does not look inside inline asm, so the s_nops cover the gfx90a+ hazards by hand: "VALU writes VGPR -> readlane
 // reads it" (1 wait state; the v_mov that feeds %1 is often the instruction right in front) and "VALU writes SGPR -> VALU reads it
 // (2) / VMEM reads it (5)" behind.  Without them the lane read returns the register's PREVIOUS value.
@@ -166,13 +161,11 @@ TAV_DEV int xcd_remap(int id, int total) {
     const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
     return base + k;
 }
-TAV_DEV void glds16_s(const void* sbase, unsigned voff, unsigned lds_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_base)
-                 : "memory");
-}
+// One wave instruction: lane l copies the 16 bytes at (sbase + voff_l) to LDS byte (lds_base + 16*l).  sbase (64-bit) and lds_base
+// must be wave-uniform (SGPRs), voff is the lane's 32-bit byte offset: advancing a K-tile costs ONE v_add_u32 per instruction instead
+// of a 64-bit multiply-add chain.  Issued from inline asm on purpose: hipcc would otherwise treat the DMA as a pending LDS write and
+// put `s_waitcnt vmcnt(0)` in front of every following ds_read, serialising load and compute.  The caller waits with a counted
+// vmcnt (wait_vmcnt0() in the simplest case) + a barrier before any wave reads the staged bytes.
 // The GEMM main loops' form: no save / restore of M0.  That is legal only
 // because nothing the compiler generates for these kernels reads or writes M0 (gfx9+ DS instructions do not use it); tools/check_isa.py
 // verifies it on the built library (every M0 write is one of these and is followed by its LDS-DMA; no other M0 user exists).  Together with a
@@ -284,20 +277,13 @@ template <> TAV_DEV float gelu_grad_t<bf16>(float x) { float c, e; gelu_parts_fa
 
 // gelu(x) and gelu'(x) together (they share the exponential / the erf): the FFN1 epilogue stores the derivative for the backward
 // pass instead of the pre-activation, so the dgrad epilogue multiplies by it without any transcendental
-template <typename T> TAV_DEV void gelu_both_t(float x, float& y, float& dy);
-template <> TAV_DEV void gelu_both_t<float>(float x, float& y, float& dy) {
+TAV_DEV void gelu_both_f(float x, float& y, float& dy) {        // exact erf (f32 policy)
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
     y = x * cdf;
     dy = cdf + x * 0.39894228040143267794f * __expf(-0.5f * x * x);
 }
-template <> TAV_DEV void gelu_both_t<bf16>(float x, float& y, float& dy) {
-    float c, e;
-    gelu_parts_fast(x, c, e);
-    y = x * c;
-    dy = fmaf(x * 0.39894228040143267794f, e, c);
-}
 
-// The same pair for four values at once, written on two-wide vectors so the arithmetic compiles to packed FP32 instructions
+// The bf16 policy's pair for four values at once, written on two-wide vectors so the arithmetic compiles to packed FP32 instructions
 // (v_pk_fma_f32 / v_pk_mul_f32: two lanes of work per issue slot); rcp and exp2 stay scalar.  Same formula and constants as
 // gelu_parts_fast -- the FFN1 epilogue of a 256 x 256 tile is VALU bound on exactly this.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -316,7 +302,7 @@ TAV_DEV void gelu_both2_fast(f32x2 x, f32x2& y, f32x2& dy) {
 template <typename T> TAV_DEV void gelu_both4_t(f32x4 x, f32x4& y, f32x4& dy);
 template <> TAV_DEV void gelu_both4_t<float>(f32x4 x, f32x4& y, f32x4& dy) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { float a, b; gelu_both_t<float>(x[e], a, b); y[e] = a; dy[e] = b; }
+    for (int e = 0; e < 4; ++e) { float a, b; gelu_both_f(x[e], a, b); y[e] = a; dy[e] = b; }
 }
 template <> TAV_DEV void gelu_both4_t<bf16>(f32x4 x, f32x4& y, f32x4& dy) {
     f32x2 y0, d0, y1, d1;

@@ -39,13 +39,6 @@ struct GemmNT {
 
 TAV_DEV int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
-// ablation switches for tools/ab_build.sh (timing experiments only; results are wrong with any of them set)
-#ifdef TAV_ABL_NOMFMA
-#define TAV_NT_MMA(b, a, c) do { (c)[0] += __uint_as_float((b).x ^ (a).x); } while (0)
-#else
-#define TAV_NT_MMA(b, a, c) mma16<T>(b, a, c)
-#endif
-
 // TM = 16-row MFMA tiles per wave along M (2, 3 or 4); NW = waves per workgroup (4 or 8), arranged (NW/2) x 2, each wave a
 // (16*TM) x 64 block: the workgroup tile is (8*TM*NW) x 128 = 64/96/128 x 128 (NW = 4) or 256 x 128 (NW = 8, TM = 4).
 // The host picks the shape per launch:
@@ -54,13 +47,6 @@ TAV_DEV int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 //    (85 FLOP/B, one 8-wave workgroup per CU) is faster wherever its coarser tile grid still fills the chip;
 //  * the tile count must divide well over the 256 CUs (M = 11712, N = 768: 552 tiles of 128 rows leave 28 % of the chip idle in
 //    the last round, 732 tiles of 96 rows do not) and small-M problems must still produce enough workgroups.
-// 3 + 2 image rings of the 256 x 256 tiles (see R25 in gemm_nt_kernel); 0 = two whole K-tile stages (rounds 1-2), kept for A/B builds
-#ifndef TAV_NT_RING25
-#define TAV_NT_RING25 1
-#endif
-#ifndef TAV_TN_RING25
-#define TAV_TN_RING25 1
-#endif
 enum { NT_GEN = 0, NT_PLAIN = 1, NT_RESID = 2, NT_GELU_D = 3, NT_MUL_D = 4 };   // epilogue flavours (see the epilogue)
 template <typename T, typename TO, int TM, int NST, int NW, int TNW, int EPI = NT_GEN>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_nt_kernel(const GemmNT p) {
@@ -75,9 +61,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
     // be issued and land within ONE K-tile time and the ring is empty at every wait (the loop then runs at issue + round trip per K-tile: the
     // MFMA-free build takes as long as the full one).  With the fifth image, A(kt+2) is issued while tile kt is multiplied: one image is still
     // in flight at every wait, B(kt+1) goes out first in the iteration (most of a K-tile time to land), A(kt+2) has a K-tile time more.
-    constexpr bool R25 = (TAV_NT_RING25 != 0) && NW == 8 && TNW == 8 && NST == 2 && !F8 && ES == 2;
-    constexpr bool B3 = TAV_NT_RING25 == 2;                // experiment: the third slot goes to B (weights) instead of A
-    constexpr int NSA = R25 ? (B3 ? 2 : 3) : NST;
+    constexpr bool R25 = NW == 8 && TNW == 8 && NST == 2 && !F8 && ES == 2;
+    constexpr int NSA = R25 ? 3 : NST;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sA = smem;                  // [NSA][BM][128B]  activations (m)
     char* sB = smem + NSA * TILE_A;   // [NST][BN][128B]  weights (n)
@@ -126,13 +111,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
     auto stage_a = [&](int j, unsigned ko, int buf) { glds16_m0(Ab + ko, ga[j], ldsA + buf * TILE_A + j * 1024); };
     auto stage_b = [&](int j, unsigned ko, int buf) { glds16_m0(Bb + ko, gb[j], ldsB + buf * TILE_B + j * 1024); };
     auto stage_piece = [&](int pc, unsigned ko, int buf) {
-#ifdef TAV_NT_DMA_OLD
-        if (pc < TM) glds16_s(Ab, ga[pc] + ko, ldsA + buf * TILE_A + pc * 1024);
-        else glds16_s(Bb, gb[pc - TM] + ko, ldsB + buf * TILE_B + (pc - TM) * 1024);
-#else
-        if (pc < TM) glds16_m0(Ab + ko, ga[pc], ldsA + buf * TILE_A + pc * 1024);
-        else glds16_m0(Bb + ko, gb[pc - TM], ldsB + buf * TILE_B + (pc - TM) * 1024);
-#endif
+        if (pc < TM) stage_a(pc, ko, buf);
+        else stage_b(pc - TM, ko, buf);
     };
 
     f32x4 acc[TNW][TM];  // [tn][tm]
@@ -160,17 +140,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
     auto ktile = [&](int kt, int cur, auto prefetch) {
         if constexpr (decltype(prefetch)::value) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * NP) : "memory");
         else wait_vmcnt0();                                 // tail: fewer tiles in flight than the constant assumes
-#ifndef TAV_ABL_NOBAR
         __syncthreads();                                    // everybody's pieces landed; the buffer refilled below is no longer read
-#endif
         const char* cA = sA + cur * TILE_A;
         const char* cB = sB + cur * TILE_B;
         const unsigned ko = (unsigned)(kt + NST - 1) * 128u;
         const int nxt = (cur + NST - 1) % NST;
-#ifdef TAV_ABL_NOLDS
-        if (kt == 0)
-#endif
-        {
 #pragma unroll
         for (int t = 0; t < TM; ++t) fa0[t] = *reinterpret_cast<const uint4*>(cA + off_a[0][t]);
 #pragma unroll
@@ -179,24 +153,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
         for (int t = 0; t < TM; ++t) fa1[t] = *reinterpret_cast<const uint4*>(cA + off_a[1][t]);
 #pragma unroll
         for (int t = 0; t < TNW; ++t) fb1[t] = *reinterpret_cast<const uint4*>(cB + off_b[1][t]);
-        }
         __builtin_amdgcn_sched_barrier(0);                  // keep all 16 fragment reads in flight ahead of the MFMAs
 #pragma unroll
         for (int tn = 0; tn < TNW; ++tn) {
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm) {
                 if constexpr (F8) mma16_fp8(fb0[tn], fb1[tn], fa0[tm], fa1[tm], acc[tn][tm]);
-                else TAV_NT_MMA(fb0[tn], fa0[tm], acc[tn][tm]);
+                else mma16<T>(fb0[tn], fa0[tm], acc[tn][tm]);
             }
             if constexpr (decltype(prefetch)::value) {
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int pc = tn * NP / TNW; pc < (tn + 1) * NP / TNW; ++pc) {
-#ifdef TAV_ABL_NODMA
-                    if (kt < 0)
-#endif
-                    stage_piece(pc, ko, nxt);
-                }
+                for (int pc = tn * NP / TNW; pc < (tn + 1) * NP / TNW; ++pc) stage_piece(pc, ko, nxt);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -204,21 +172,20 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
 #pragma unroll
             for (int tn = 0; tn < TNW; ++tn)
 #pragma unroll
-                for (int tm = 0; tm < TM; ++tm) TAV_NT_MMA(fb1[tn], fa1[tm], acc[tn][tm]);
+                for (int tm = 0; tm < TM; ++tm) mma16<T>(fb1[tn], fa1[tm], acc[tn][tm]);
         }
     };
     // R25 iteration: ISSUE_B = B(kt+1) goes out (kt + 1 < nk), ISSUE_A = A(kt+2) goes out (kt + 2 < nk).  Issue order per iteration: B(kt+1),
     // then A(kt+2); at the next wait the TM youngest pieces are exactly A(kt+2)'s and may stay in flight.
-    // (cl / cs: current slot of the three-slot operand / of the two-slot operand; issue_s: the two-slot operand's image of tile kt+1 goes
-    // out, issue_l: the three-slot operand's image of tile kt+2)
+    // (cl / cs: current slot of A (three slots) / of B (two slots); issue_s: B's image of tile kt+1 goes out, issue_l: A's image of tile kt+2)
     auto ktile25 = [&](int kt, int cl, int cs, auto issue_s, auto issue_l) {
         constexpr bool IS = decltype(issue_s)::value, IL = decltype(issue_l)::value;
-        if constexpr (IS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(B3 ? PB : TM) : "memory");   // long(kt+1) was issued after short(kt): it may still fly
+        if constexpr (IS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TM) : "memory");   // A(kt+1) was issued after B(kt): it may still fly
         else wait_vmcnt0();
         __syncthreads();
-        const char* cA = sA + (B3 ? cs : cl) * TILE_A;
-        const char* cB = sB + (B3 ? cl : cs) * TILE_B;
-        const int nl = cl == 0 ? 2 : cl - 1;                  // slot of long(kt-1) = slot of long(kt+2)
+        const char* cA = sA + cl * TILE_A;
+        const char* cB = sB + cs * TILE_B;
+        const int nl = cl == 0 ? 2 : cl - 1;                  // slot of A(kt-1) = slot of A(kt+2)
         const int ns = cs ^ 1;
 #pragma unroll
         for (int t = 0; t < TM; ++t) fa0[t] = *reinterpret_cast<const uint4*>(cA + off_a[0][t]);
@@ -229,26 +196,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
 #pragma unroll
         for (int t = 0; t < TNW; ++t) fb1[t] = *reinterpret_cast<const uint4*>(cB + off_b[1][t]);
         __builtin_amdgcn_sched_barrier(0);
-        constexpr int PS = B3 ? TM : PB, PL = B3 ? PB : TM;   // pieces of the short / long operand per wave
-#ifdef TAV_NT_DMA_EARLY
-        constexpr int PPG = 2;                                // pieces per MFMA group: everything issued in the first quarter
-#else
-        constexpr int PPG = 1;
-#endif
 #pragma unroll
         for (int tn = 0; tn < TNW; ++tn) {
 #pragma unroll
-            for (int tm = 0; tm < TM; ++tm) TAV_NT_MMA(fb0[tn], fa0[tm], acc[tn][tm]);
+            for (int tm = 0; tm < TM; ++tm) mma16<T>(fb0[tn], fa0[tm], acc[tn][tm]);
             if constexpr (IS || IL) {
                 __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = tn * PPG; q < (tn + 1) * PPG; ++q) {
-                    if constexpr (IS) {
-                        if (q < PS) { if constexpr (B3) stage_a(q, (unsigned)(kt + 1) * 128u, ns); else stage_b(q, (unsigned)(kt + 1) * 128u, ns); }
-                    }
-                    if constexpr (IL) {
-                        if (q >= PS && q - PS < PL) { if constexpr (B3) stage_b(q - PS, (unsigned)(kt + 2) * 128u, nl); else stage_a(q - PS, (unsigned)(kt + 2) * 128u, nl); }
-                    }
+                // one piece per MFMA group: B's PB pieces first, then A's TM
+                if constexpr (IS) {
+                    if (tn < PB) stage_b(tn, (unsigned)(kt + 1) * 128u, ns);
+                }
+                if constexpr (IL) {
+                    if (tn >= PB && tn - PB < TM) stage_a(tn - PB, (unsigned)(kt + 2) * 128u, nl);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -256,17 +215,17 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
 #pragma unroll
         for (int tn = 0; tn < TNW; ++tn)
 #pragma unroll
-            for (int tm = 0; tm < TM; ++tm) TAV_NT_MMA(fb1[tn], fa1[tm], acc[tn][tm]);
+            for (int tm = 0; tm < TM; ++tm) mma16<T>(fb1[tn], fa1[tm], acc[tn][tm]);
     };
     if constexpr (R25) {
         static_assert(!R25 || PB + TM <= TNW, "one DMA piece per MFMA group");
         auto stage_l = [&](unsigned ko, int slot) {
 #pragma unroll
-            for (int j = 0; j < (B3 ? PB : TM); ++j) { if constexpr (B3) stage_b(j, ko, slot); else stage_a(j, ko, slot); }
+            for (int j = 0; j < TM; ++j) stage_a(j, ko, slot);
         };
         auto stage_s = [&](unsigned ko, int slot) {
 #pragma unroll
-            for (int j = 0; j < (B3 ? TM : PB); ++j) { if constexpr (B3) stage_a(j, ko, slot); else stage_b(j, ko, slot); }
+            for (int j = 0; j < PB; ++j) stage_b(j, ko, slot);
         };
         stage_l(0u, 0);
         stage_s(0u, 0);
@@ -292,9 +251,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
     // uncoalesced residual reads.  Instead the f32 accumulator tile goes through the (now idle) staging LDS -- one ds_write_b128
     // per 16x16 tile, 16-B chunks XOR-swizzled with the row so both the writes and the row-major reads are conflict free -- and
     // the epilogue runs row-major: 32 threads per row, 16 B per thread, every global access a full 512-B (f32) / 256-B (bf16) run.
-#ifdef TAV_ABL_NOEPI                                        // timing ablation: prologue + main loop only
-    if (p.alpha != 12345.f) { if (acc[0][0][0] == 1.2345e-30f) p.C[0] = 1; return; }
-#endif
     __syncthreads();                                       // all waves finished reading the operand images
     float* sC = reinterpret_cast<float*>(smem);            // [EP_ROWS][BN] f32 inside the (now idle) staging buffers
     constexpr int ROWB_C = BN * 4;                          // bytes per staged row
@@ -335,11 +291,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
     // the STORES issued before it (their write acknowledgements), and the loop runs at "depth" accesses per memory round trip.  The gelu'
     // side input takes two registers per row: all of a pass's rows are requested up front, every load is older than every store and the
     // loop never waits on a store.  The f32 residual takes four (16 x 4 registers on top of the accumulators would spill): depth 8.
-#ifdef TAV_PD_OLD
-    constexpr int PD = NIT > 8 ? 8 : NIT;
-#else
     constexpr int PD = (EPI == NT_MUL_D) ? NIT : (NIT > 8 ? 8 : NIT);
-#endif
     constexpr bool EARLY = (TNW == 4);                      // ... and no registers to spare while they are
     const bool pre_r = f_resid, pre_g = !pre_r && f_gin && sizeof(TS) == 2, pre_c = !pre_r && !pre_g && f_acc && sizeof(TO) == 4;
     const bool any_side = pre_r || pre_c || pre_g;
@@ -362,9 +314,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
         auto side_load = [&](int it) __attribute__((always_inline)) -> f32x4 {
             const int m = m0 + row_lo + rr + it * RPI;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#ifdef TAV_ABL_NOSIDE
-            if (p.alpha == 12345.f)
-#endif
             if (FULL || (n < p.N && m < p.M)) {
                 if (pre_r) v = ld4(reinterpret_cast<const float*>(Rb + (o_r + it * s_r)));
                 else if (pre_c) { if constexpr (sizeof(TO) == 4) v = ld4(reinterpret_cast<const float*>(Cb + (o_c + it * s_c))); }
@@ -411,21 +360,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
                 if (it + 1 < NIT) v_next = staged(it + 1);
                 if (FULL || m < p.M) {
                     v = v * alpha + bv;
-#ifdef TAV_ABL_NOSTORE
-                    if (p.alpha == 12345.f)
-#endif
                     if (f_pre) st4(reinterpret_cast<TO*>(Pb + (o_p + it * s_p)), v);
                     if (f_act3) {                               // GELU out, gelu' to C_pre
                         f32x4 d, y4;
-#ifdef TAV_ABL_SCALARGELU
-                        for (int e = 0; e < 4; ++e) { float y, dy; gelu_both_t<TS>(v[e], y, dy); y4[e] = y; d[e] = dy; }
-#else
                         gelu_both4_t<TS>(v, y4, d);
-#endif
                         v = y4;
-#ifdef TAV_ABL_NOSTORE
-                        if (p.alpha == 12345.f)
-#endif
                         if (GEN ? Cpre != nullptr : true) st4(reinterpret_cast<TO*>(Pb + (o_p + it * s_p)), d);
                     } else if (f_gelu) { v[0] = gelu_t<TS>(v[0]); v[1] = gelu_t<TS>(v[1]); v[2] = gelu_t<TS>(v[2]); v[3] = gelu_t<TS>(v[3]); }
                     if (f_gin) {
@@ -443,9 +382,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) __attribute__((amdgpu_wav
                         if (pre_c) v += sv;
                         else v += ld4(reinterpret_cast<const TO*>(Cb + (o_c + it * s_c)));
                     }
-#ifdef TAV_ABL_NOSTORE                                      // timing ablation: everything but the output stores (never true at run time)
-                    if (p.alpha == 12345.f)
-#endif
                     st4(reinterpret_cast<TO*>(Cb + (o_c + it * s_c)), v);
                 }
             }
@@ -525,7 +461,7 @@ template <> TAV_DEV uint4 tn_frag<float>(const char* tile, int krow0, int col0, 
     return r;
 }
 
-// K-tile and ring depth per dtype (64 tokens, two buffers).  A deeper ring of shorter tiles at the same LDS budget (32 tokens x 4 buffers,
+// K-tile and ring depth (64 tokens, two buffers, for both dtypes).  A deeper ring of shorter tiles at the same LDS budget (32 tokens x 4 buffers,
 // three tiles in flight) was tried on the theory that a workgroup's K-tile period is one DMA round trip: it is not -- that variant pays
 // twice the barriers and ran 17 % slower (profiles/r02_experiments.md).
 // Bias gradients (column sums of dY) on the matrix pipe: one extra MFMA per 16-column dY fragment with an all-ones first operand gives the
@@ -536,13 +472,6 @@ template <> TAV_DEV uint4 ones_frag<bf16>() { return make_uint4(0x3f803f80u, 0x3
 template <> TAV_DEV uint4 ones_frag<float>() { return make_uint4(0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u); }
 
 template <typename T> struct TNShape { static constexpr int KT = 64, NST = 2; };
-template <> struct TNShape<bf16> {
-#ifdef TAV_ABL_TN_RING4
-    static constexpr int KT = 32, NST = 4;                  // measured 17 % SLOWER (942 -> 1107 us per video layer at batch 32): twice the barriers
-#else
-    static constexpr int KT = 64, NST = 2;
-#endif
-};
 
 template <typename T>
 TAV_DEV void gemm_tn_body(const GemmTN& p, const int tile, const int split) {
@@ -779,10 +708,9 @@ TAV_DEV void gemm_tn_big_body(const GemmTN& p, const int tile, const int split) 
         }
     const unsigned strideA = (unsigned)(KT * p.lda * ES), strideB = (unsigned)(KT * p.ldb * ES);
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr(smem) + wave * 8 * ROWB);
-    // LDS: FIVE 32 KB images (two [64][128] sub-images each) -- three dY slots and two X slots (TAV_TN_RING25; the NT kernel's ring, see there):
-    // dY(kt+2) is issued while tile kt is multiplied, X(kt+1) goes out first in the iteration.  Without the macro: two whole stages.
-    constexpr bool R25 = TAV_TN_RING25 != 0;
-    constexpr int NSA = R25 ? 3 : 2;
+    // LDS: FIVE 32 KB images (two [64][128] sub-images each) -- three dY slots and two X slots (the NT kernel's ring, see R25 there):
+    // dY(kt+2) is issued while tile kt is multiplied, X(kt+1) goes out first in the iteration.
+    constexpr int NSA = 3;
     constexpr int IMG = 2 * SUB;                            // one operand's K-tile image (halves 0 / 1)
     constexpr int OFF_B = NSA * IMG;                        // X images behind the dY images
     // ragged last K-tile of one operand: ordinary loads, zero fill (block-uniform condition at the call sites)
@@ -830,17 +758,17 @@ TAV_DEV void gemm_tn_big_body(const GemmTN& p, const int tile, const int split) 
 
     // The DMA pieces of later K-tiles (8 per wave and iteration) are issued between the MFMA groups of the first K-step: back to back right
     // after the barrier they cost every wave of the CU ~1000 cycles of issue time at the same moment, with nothing on the matrix pipe.
-    // Iteration kt issues X(kt+1) [R25: and dY(kt+2); else dY(kt+1)]; issue order X then dY, so at the next wait the 4 youngest pieces are
-    // dY's and -- R25 -- may stay in flight.
-    constexpr int AHEAD_A = R25 ? 2 : 1;
-    if (nk > 0) { stage_a(0, 0); stage_b(0, 0); if (R25 && nk > 1) stage_a(1, 1); }
+    // Iteration kt issues X(kt+1) and dY(kt+2); issue order X then dY, so at the next wait the 4 youngest pieces are dY's and may stay
+    // in flight.
+    constexpr int AHEAD_A = 2;
+    if (nk > 0) { stage_a(0, 0); stage_b(0, 0); if (nk > 1) stage_a(1, 1); }
     int ca = 0;
     for (int kt = 0; kt < nk; ++kt) {
         const int cb = kt & 1;
-        if (R25 && is_dma(kt + 1)) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        if (is_dma(kt + 1)) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else wait_vmcnt0();
         __syncthreads();
-        const int na = R25 ? (ca == 0 ? 2 : ca - 1) : (ca ^ 1), nb = cb ^ 1;      // slots of dY(kt + AHEAD_A), X(kt + 1)
+        const int na = ca == 0 ? 2 : ca - 1, nb = cb ^ 1;      // slots of dY(kt + AHEAD_A), X(kt + 1)
         const bool dma_b = is_dma(kt + 1), dma_a = is_dma(kt + AHEAD_A);          // block-uniform
         if (kt + 1 < nk && !dma_b) stage_b(kt + 1, nb);                            // (ragged last tile: through registers, up front)
         if (kt + AHEAD_A < nk && !dma_a) stage_a(kt + AHEAD_A, na);
@@ -872,7 +800,7 @@ TAV_DEV void gemm_tn_big_body(const GemmTN& p, const int tile, const int split) 
                 else { mma16<T>(ones, f1[2], bacc[0]); mma16<T>(ones, f1[3], bacc[1]); }
             }
         }
-        ca = R25 ? (ca == 2 ? 0 : ca + 1) : (ca ^ 1);
+        ca = ca == 2 ? 0 : ca + 1;
     }
     __syncthreads();
 
@@ -1044,8 +972,8 @@ static double nt_small_us(int M, int N, double nk, int nz, int tm, int epi) {
     return (double)((long)((t + slots[tm] - 1) / slots[tm])) * (kt + fix[tm] + e * tm / 4.0);
 }
 static double nt_big_round_us(double nk, int epi) {
-    // (3 + 2 ring: 1.37-1.52 us per K-tile at every K measured; with two whole stages K-tiles beyond the 36th cost a third more)
-    const double kt = TAV_NT_RING25 ? nk * 1.45 : (nk <= 36.0 ? nk : 36.0 + 1.33 * (nk - 36.0)) * 1.48;
+    // (3 + 2 ring: 1.37-1.52 us per K-tile at every K measured)
+    const double kt = nk * 1.45;
     return kt + 6.5 + ((epi & 1) ? 9.0 : 0.0) + ((epi & 2) ? 4.0 : 0.0) + ((epi & 4) ? 3.0 : 0.0) + ((epi & 8) ? 4.7 : 0.0) + ((epi & 16) ? 6.7 : 0.0);
 }
 // Returns the tile for the launch; when `rows_big` is given and a mixed schedule is faster, *rows_big < M is the number of leading rows that
@@ -1105,11 +1033,7 @@ static void nt_plan(const tav_gemm_nt_args* a, int* tm_out, int* rows_big, int* 
     const int es = a->in_dtype == TAV_FP8 ? 1 : (a->in_dtype == TAV_BF16 ? 2 : 4);
     const int nz = (int)((a->nzb > 0 ? a->nzb : 1) * (a->nzg > 0 ? a->nzg : 1));
     int tm = a->tile_m_hint & 31;                            // 2/3/4: 64/96/128 x 128 tiles (4 waves); 8: 256 x 128, 16: 256 x 256 (8 waves); 17: as 0 but one launch
-#ifdef TAV_ABL_NOSPLIT                                       // tools/ab_build.sh: one tile per launch, for same-box A/B of the mixed schedule
-    const bool may_split = false;
-#else
     const bool may_split = tm == 0 && a->in_dtype == TAV_BF16 && nz == 1;
-#endif
     *rows_big = (int)a->M; *tm_rest = 4;
     if (a->in_dtype == TAV_F32 && (tm == 8 || tm == 16)) tm = 4;
     if (tm != 8 && tm != 16 && (tm < 2 || tm > 4))
@@ -1162,7 +1086,7 @@ extern "C" int tav_gemm_nt(const tav_gemm_nt_args* a, void* stream_) {
         if (in_dtype != TAV_BF16) nst = 2;
         dim3 grid(p.tiles_m * p.tiles_n, nzb * p.nzg), block(tm >= 8 ? 512 : 256);
         // 256x128: 3 x 48 KB (its f32 epilogue tile needs 128 KB); 256x256: 2 x 64 KB, or 3 A + 2 B images = 160 KB (bf16, R25)
-        const size_t lds = (TAV_NT_RING25 && tm == 16 && in_dtype == TAV_BF16) ? (size_t)160 * 1024 : (size_t)nst * (bm + bn) * 128;
+        const size_t lds = (tm == 16 && in_dtype == TAV_BF16) ? (size_t)160 * 1024 : (size_t)nst * (bm + bn) * 128;
 #define TAV_NT_LAUNCH_S(TT, TOO, NS, EP)                                                                                 \
     do {                                                                                                                 \
         if (tm == 4) hipLaunchKernelGGL((gemm_nt_kernel<TT, TOO, 4, NS, 4, 4, EP>), grid, block, lds, stream, p);         \
@@ -1201,9 +1125,6 @@ extern "C" int tav_gemm_nt(const tav_gemm_nt_args* a, void* stream_) {
                 else hipLaunchKernelGGL((gemm_nt_kernel<fp8, float, 4, 2, 4, 4>), grid, block, lds, stream, p);
             }
         } else if (in_dtype == TAV_BF16) {
-#ifdef TAV_ABL_GENEPI
-            epi = NT_GEN;
-#endif
             if (out_dtype == TAV_BF16) {
                 if (epi == NT_PLAIN) TAV_NT_LAUNCH(bf16, bf16, NT_PLAIN);
                 else if (epi == NT_GELU_D) TAV_NT_LAUNCH(bf16, bf16, NT_GELU_D);
@@ -1394,7 +1315,7 @@ extern "C" int tav_gemm_tn_grouped_ws(const tav_gemm_tn_problem* probs, int32_t 
         ws_off += (long)red.nbias[k] * probs[k].N1;
     }
     grp.n = nprob; red.n = nprob; red.nsplit = nsplit;
-    if (big) hipLaunchKernelGGL((gemm_tn_grouped_big_kernel<bf16>), dim3(total, nsplit), dim3(512), (TAV_TN_RING25 ? 5 : 4) * 2 * 64 * 256, stream, grp);
+    if (big) hipLaunchKernelGGL((gemm_tn_grouped_big_kernel<bf16>), dim3(total, nsplit), dim3(512), 5 * 2 * 64 * 256, stream, grp);
     else if (dtype == TAV_BF16) hipLaunchKernelGGL((gemm_tn_grouped_kernel<bf16>), dim3(total), dim3(256), 4 * 64 * 256, stream, grp);
     else hipLaunchKernelGGL((gemm_tn_grouped_kernel<float>), dim3(total), dim3(256), 4 * 64 * 512, stream, grp);
     if (nsplit > 1) hipLaunchKernelGGL(tn_group_reduce_kernel, dim3((unsigned)((end4 + 255) / 256)), dim3(256), 0, stream, red);

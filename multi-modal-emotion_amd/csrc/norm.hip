@@ -203,9 +203,7 @@ __global__ __launch_bounds__(256) void ln_param_reduce_multi_kernel(const LnRedu
 // cap on workgroups of the LN backward (= rows of the dgamma/dbeta partial buffer).  Measured at 11712 x 768: 256 -> 35.5 us,
 // 512 -> 33.9 us, 1024 -> 38.0 us (more partial rows for ln_param_reduce); at 46848 x 768 (batch 32): 256 -> 157 us, 512 -> 106.5 us
 // (4.7 TB/s), 1024 -> 131 us, 2048 -> 136 us: one workgroup per CU keeps too few bytes in flight, four pay for their partial rows.
-#ifndef LN_MAX_BLOCKS
-#define LN_MAX_BLOCKS 512
-#endif
+constexpr int LN_MAX_BLOCKS = 512;
 static inline int ln_blocks(long rows) {
     long b = (rows + 15) / 16;      // >= 4 rows per wave so the per-lane dgamma/dbeta partials amortise
     return (int)(b < 1 ? 1 : (b > LN_MAX_BLOCKS ? LN_MAX_BLOCKS : b));

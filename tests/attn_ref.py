@@ -13,7 +13,7 @@ taken from the operands as the kernel holds them (rounded to bf16 / f32 first); 
 
 Operands of spread magnitude (make_inputs): query row i is randn * 2^(i % 7 - 3) (its logits have a standard deviation of 1/8 .. 8: nearly
 flat to nearly one-hot rows, period 7 coprime to 16 and 64), the columns of v carry 2^(d % 5 - 2), those of dO 2^(d % 7 - 3); `spike` multiplies
-key S // 3 by 6 and key S - 7 by 48 (far past TAV_ATT_LAZY_THR: the lazy rescale of the pre-scaled forward runs in the last tiles); mode-1 masks
+key S // 3 by 6 and key S - 7 by 48 (far past ATT_LAZY_THR: the lazy rescale of the pre-scaled forward runs in the last tiles); mode-1 masks
 put finfo(float32).min on keys j % 5 == 3 and -65504 on j % 7 == 5 (key 0 stays: no row is fully masked); mode-2 masks are {0, -0.5, 2, 1} by
 j % 4 ("small") or the reference style {0, -65504, 65505, 1} in segments.
 
@@ -23,7 +23,7 @@ from), D_L = chain_len(L) for the reductions over keys or queries; 2u per additi
 
   logit      e_t = D 2u (c A_ij + Mb_i) + 4u (|t_ij| + M_i) + 3u |mask_j log2 e|, c = scale log2(e) (1 when pre-scaled: that rounding is in q
              and the reference shares it).  M_i bounds the running reference exponent while key j still matters: the kernels keep it between
-             t_ij - TAV_ATT_LAZY_THR and the row maximum, and a key more than 160 below the maximum is flushed to zero by every later
+             t_ij - ATT_LAZY_THR and the row maximum, and a key more than 160 below the maximum is flushed to zero by every later
              rescale, so M_i = max {|t_ij| : t_ij >= max_j t_ij - 160} + 12; Mb_i = M_i + log2 L + 1 also covers -lse log2(e), the start
              of the backward accumulators.  The exponent rides every addition of the chain (C operand of the fast path), so it is charged
              at every one of them.  4u: the multiply by c (or the fma), the f32 value of log2(e), the subtraction; 3u: the mask term.
@@ -72,7 +72,7 @@ LOG2E = 1.4426950408889634
 LN2 = 0.6931471805599453
 SCALE = 0.125
 C2 = SCALE * LOG2E                                        # what a pre-scaled q carries (ops.ATTN_Q_PRESCALE)
-LAZY_THR = 12.0                                           # TAV_ATT_LAZY_THR
+LAZY_THR = 12.0                                           # ATT_LAZY_THR
 FMIN = float(np.finfo(np.float32).min)
 TINY = 2.0 ** -120
 RB = 2.0 ** -8                                            # half a bf16 ulp relative to the value itself, at most

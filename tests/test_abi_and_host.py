@@ -607,6 +607,20 @@ def test_emitted_isa_discipline():
         assert ci.check_text([("bad", txt)])[0], txt
 
 
+def test_kernel_sources_carry_no_compile_time_switches():
+    """csrc/ holds only what ships: no #if / #ifdef / #ifndef / #elif apart from an include guard (#ifndef X directly followed by
+    #define X).  Experiments live on branches (tools/ab_build.sh builds a second tree for a same-box A/B), not behind -D switches."""
+    csrc = os.path.join(ROOT, "multi-modal-emotion_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len(files) >= 12
+    for f in files:
+        lines = open(os.path.join(csrc, f)).read().splitlines()
+        for n, line in enumerate(lines):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b\s*(\w*)", line)
+            guard = m and m.group(1) == "ifndef" and n + 1 < len(lines) and re.match(r"\s*#\s*define\s+%s\s*$" % m.group(2), lines[n + 1])
+            assert not m or guard, f"{f}:{n + 1}: {line.strip()}"
+
+
 def test_head_mask_layouts_and_oracle_head_mask():
     """VideoMAEEncoder's head_mask entry (reference utils/TAVFormer.py:190, :368-370): the layouts HF's get_head_mask produces become per-head
     factors, anything finer is refused; the oracle's restatement multiplies the probabilities before the post-softmax mask is added."""

@@ -7,7 +7,7 @@ hipcc neither pads hazards inside inline asm nor knows what an asm statement doe
 are verified on the binary itself.  (Declaring "m0" as a clobber of glds16_m0 is not an alternative: hipcc 7.2 answers `inline asm clobber list
 contains reserved registers: m0 ... may lead to undefined behaviour` -- M0 is not allocatable, there is nothing for the compiler to keep out of it.)
 
- 1. M0 discipline (glds16_s / glds16_m0 / glds16_x4).  The GEMM main loops write M0 WITHOUT saving it.  That is only legal while nothing the
+ 1. M0 discipline (glds16_m0 / glds16_x2 / glds16_x4).  The GEMM main loops write M0 WITHOUT saving it.  That is only legal while nothing the
     compiler generates uses M0.  Checked: every instruction that names m0 is `s_mov_b32 m0, x`, `s_add_u32 m0, x, y` or `s_mov_b32 sN, m0`;
     every M0 write is followed -- over at most one s_nop -- by a global_load_lds_dwordx4, or is the restore that directly follows one; and no
     other implicit M0 user (ds_gws*, s_sendmsg*, *movrel*, v_interp*, ds_*addtid*, s_set_gpr_idx*, buffer_load ... lds) exists in the library.
