@@ -533,6 +533,15 @@ int tav_sum_partials(const float* partials, int64_t n, float* out, void* stream)
 int tav_adamw_chunked(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* sizes,
                       const int32_t* chunk_prefix, int32_t ntensors, int32_t nchunks, const float* clip_coef, const float* lr, float beta1,
                       float beta2, float eps, float weight_decay, int32_t* step, float* bias_corr, void* stream);
+/* tav_adamw_chunked with parameter groups (torch.optim.AdamW's list of dicts): tensor t takes the learning rate and the weight decay of group
+ * group_of[t] (device, int32, ntensors entries; clamped into [0, ngroups) on the device) from hyper (DEVICE, f32 [ngroups][2] = {lr, weight_decay}),
+ * 1 <= ngroups <= tav_optim_max_groups() (64).  Both values are read by every launch, so a captured hipGraph replays with whatever was written
+ * into the table between replays.  One step counter, one pair of betas and one eps for all groups; clip_coef (optional), step and bias_corr as
+ * above.  The arithmetic per element is tav_adamw_chunked's: with every group set to one {lr, weight_decay} the two calls give the same bits. */
+int tav_optim_max_groups(void);
+int tav_adamw_chunked_groups(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* sizes,
+                             const int32_t* chunk_prefix, int32_t ntensors, int32_t nchunks, const float* clip_coef, const int32_t* group_of,
+                             const float* hyper, int32_t ngroups, float beta1, float beta2, float eps, int32_t* step, float* bias_corr, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Data-parallel exchange: the ONE collective of the path, the mean of a gradient bucket over the ranks of a node

@@ -172,6 +172,8 @@ _SIGS = {
     "tav_sumsq_chunked": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "tav_sum_partials": (C.c_int, [vp, i64, vp, vp]),
     "tav_adamw_chunked": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, f32, f32, f32, f32, vp, vp, vp]),
+    "tav_optim_max_groups": (C.c_int, []),
+    "tav_adamw_chunked_groups": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp]),
 }
 
 _lib = None

@@ -678,16 +678,10 @@ __global__ __launch_bounds__(256) void sumsq_chunk_kernel(const float* const* __
     __syncthreads();
     if (threadIdx.x == 0) partials[c] = red[0] + red[1] + red[2] + red[3];
 }
-__global__ __launch_bounds__(256) void adamw_chunk_kernel(float* const* __restrict__ params, const float* const* __restrict__ grads,
-                                                          float* const* __restrict__ m1, float* const* __restrict__ m2, const int64_t* __restrict__ sizes,
-                                                          const int32_t* __restrict__ prefix, int ntensors, const float* __restrict__ clip_coef,
-                                                          const float* __restrict__ lr_dev, float b1, float b2, float eps, float wd, const float* __restrict__ bc) {
-    const float lr = lr_dev[0], bc1 = bc[0], bc2 = bc[1];
-    const int c = blockIdx.x, t = chunk_owner(prefix, ntensors, c);
-    const long off = (long)(c - prefix[t]) * OPT_CHUNK;
-    float* p = params[t] + off; const float* g = grads[t] + off; float* ea = m1[t] + off; float* es = m2[t] + off;
-    long n = sizes[t] - off; n = n < OPT_CHUNK ? n : OPT_CHUNK;
-    const float cc = clip_coef ? clip_coef[0] : 1.f;
+// One chunk of one tensor (n <= OPT_CHUNK elements from p / g / ea / es) with the learning rate and the weight decay of that tensor: the body of
+// adamw_chunk_kernel (one lr, one wd for the launch) and of adamw_chunk_groups_kernel (a pair per parameter group), so the two cannot drift apart.
+TAV_DEV void adamw_chunk_update(float* p, const float* g, float* ea, float* es, long n, float cc, float lr,
+                                float wd, float b1, float b2, float eps, float bc1, float bc2) {
     const float decay = 1.f - lr * wd, step = lr / bc1, rs2 = 1.f / sqrtf(bc2), omb1 = 1.f - b1, omb2 = 1.f - b2;
     // One arithmetic for every element, whichever of the loops below it falls into: contraction is OFF and the three multiply-adds are written
     // out, so the 16-byte and the scalar form agree bit for bit.  (With the compiler free to contract, the two forms differed in the last bit of
@@ -744,6 +738,38 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(float* const* __restri
         done = 4 * n4;
     }
     for (long i = done + threadIdx.x; i < n; i += 256) upd(p[i], g[i], ea[i], es[i]);
+}
+__global__ __launch_bounds__(256) void adamw_chunk_kernel(float* const* __restrict__ params, const float* const* __restrict__ grads,
+                                                          float* const* __restrict__ m1, float* const* __restrict__ m2, const int64_t* __restrict__ sizes,
+                                                          const int32_t* __restrict__ prefix, int ntensors, const float* __restrict__ clip_coef,
+                                                          const float* __restrict__ lr_dev, float b1, float b2, float eps, float wd, const float* __restrict__ bc) {
+    const float lr = lr_dev[0], bc1 = bc[0], bc2 = bc[1];
+    const int c = blockIdx.x, t = chunk_owner(prefix, ntensors, c);
+    const long off = (long)(c - prefix[t]) * OPT_CHUNK;
+    float* p = params[t] + off; const float* g = grads[t] + off; float* ea = m1[t] + off; float* es = m2[t] + off;
+    long n = sizes[t] - off; n = n < OPT_CHUNK ? n : OPT_CHUNK;
+    const float cc = clip_coef ? clip_coef[0] : 1.f;
+    adamw_chunk_update(p, g, ea, es, n, cc, lr, wd, b1, b2, eps, bc1, bc2);
+}
+// Parameter groups: the same walk; tensor t belongs to group group_of[t] (clamped into the table) and takes that group's {lr, wd} from the
+// device table `hyper` -- three more block-uniform loads per chunk, all of them before the element loops.
+constexpr int OPT_MAX_GROUPS = 64;
+__global__ __launch_bounds__(256) void adamw_chunk_groups_kernel(float* const* __restrict__ params, const float* const* __restrict__ grads,
+                                                                 float* const* __restrict__ m1, float* const* __restrict__ m2,
+                                                                 const int64_t* __restrict__ sizes, const int32_t* __restrict__ prefix, int ntensors,
+                                                                 const float* __restrict__ clip_coef, const int32_t* __restrict__ group_of,
+                                                                 const float* __restrict__ hyper, int ngroups, float b1, float b2, float eps,
+                                                                 const float* __restrict__ bc) {
+    const float bc1 = bc[0], bc2 = bc[1];
+    const int c = blockIdx.x, t = chunk_owner(prefix, ntensors, c);
+    int gi = group_of[t];
+    gi = gi < 0 ? 0 : (gi >= ngroups ? ngroups - 1 : gi);
+    const float lr = hyper[2 * gi], wd = hyper[2 * gi + 1];
+    const long off = (long)(c - prefix[t]) * OPT_CHUNK;
+    float* p = params[t] + off; const float* g = grads[t] + off; float* ea = m1[t] + off; float* es = m2[t] + off;
+    long n = sizes[t] - off; n = n < OPT_CHUNK ? n : OPT_CHUNK;
+    const float cc = clip_coef ? clip_coef[0] : 1.f;
+    adamw_chunk_update(p, g, ea, es, n, cc, lr, wd, b1, b2, eps, bc1, bc2);
 }
 
 }  // namespace tav
@@ -1042,6 +1068,18 @@ extern "C" int tav_adamw_chunked(float* const* params, const float* const* grads
     hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, ST, step, beta1, beta2, bias_corr);
     hipLaunchKernelGGL(adamw_chunk_kernel, dim3(nchunks), dim3(256), 0, ST, params, grads, exp_avg, exp_avg_sq, sizes, chunk_prefix, ntensors, clip_coef, lr,
                        beta1, beta2, eps, weight_decay, (const float*)bias_corr);
+    return tav_last_error();
+}
+extern "C" int tav_optim_max_groups(void) { return OPT_MAX_GROUPS; }
+extern "C" int tav_adamw_chunked_groups(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                        const int64_t* sizes, const int32_t* chunk_prefix, int32_t ntensors, int32_t nchunks, const float* clip_coef,
+                                        const int32_t* group_of, const float* hyper, int32_t ngroups, float beta1, float beta2, float eps, int32_t* step,
+                                        float* bias_corr, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !sizes || !chunk_prefix || !group_of || !hyper || !step || !bias_corr) return TAV_ERR_NULL;
+    if (ntensors <= 0 || nchunks <= 0 || ngroups < 1 || ngroups > OPT_MAX_GROUPS) return TAV_ERR_SHAPE;
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, ST, step, beta1, beta2, bias_corr);
+    hipLaunchKernelGGL(adamw_chunk_groups_kernel, dim3(nchunks), dim3(256), 0, ST, params, grads, exp_avg, exp_avg_sq, sizes, chunk_prefix, ntensors, clip_coef,
+                       group_of, hyper, (int)ngroups, beta1, beta2, eps, (const float*)bias_corr);
     return tav_last_error();
 }
 extern "C" int tav_clip_coef(const float* sumsq, float max_norm, float* coef_out, float* norm_out, void* stream) {

@@ -343,6 +343,11 @@ class GraphedStep:
 
     def __init__(self, stepper, forward_loss, stream=None, segments=4, use_graphs=True, fractions=None, mode="chain", tail_bf16=False, shard_optimizer=False):
         from . import runtime
+        ngroups = len(getattr(getattr(stepper, "opt", None), "param_groups", ()))
+        if ngroups > 1:
+            raise ValueError(f"ddp.GraphedStep takes an optimizer with one parameter group, this one has {ngroups}: the bucket-wise "
+                             "norm and the sharded update know one learning rate and one weight decay (parameter groups run on the eager "
+                             "data-parallel step, BucketedAllReduce + FusedAdamW)")
         if runtime.visual_rows() != "equal":
             raise ValueError("ddp.GraphedStep captures fixed shapes: ragged visual rows (runtime.set_visual_rows('ragged')) run on the eager "
                              "data-parallel step")

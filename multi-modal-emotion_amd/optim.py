@@ -10,21 +10,22 @@ from ._lib import check, lib, ptr, stream
 
 
 class _PtrTable:
-    """Pinned host staging + device array of int64 (pointers / sizes), refreshed with an async copy."""
+    """Pinned host staging + device array of int64 (pointers / sizes; int32 for the group index of every tensor), refreshed with an async copy."""
     CAPTURE_SLOTS = 8
 
-    def __init__(self, n, device):
+    def __init__(self, n, device, dtype=torch.int64):
+        self.dtype = dtype
         # two pinned staging buffers used in turn: the asynchronous H2D copy of step k may still be pending when the host prepares
         # step k+1 (eager mode at large batch: the GPU lags the host), so a buffer is rewritten only after ITS last copy finished
-        self.host = [torch.empty(n, dtype=torch.int64).pin_memory() for _ in range(2)]
+        self.host = [torch.empty(n, dtype=dtype).pin_memory() for _ in range(2)]
         self.done = [None, None]
         self.turn = 0
         self.last = None
         # pinned sources of CAPTURED uploads, one slot per capture, allocated here (a pinned allocation inside a capture can itself
         # invalidate it) and never rewritten once a capture has taken it
-        self.cap_slots = [torch.empty(n, dtype=torch.int64).pin_memory() for _ in range(self.CAPTURE_SLOTS)]
+        self.cap_slots = [torch.empty(n, dtype=dtype).pin_memory() for _ in range(self.CAPTURE_SLOTS)]
         self.cap_used = 0
-        self.dev = torch.empty(n, dtype=torch.int64, device=device)
+        self.dev = torch.empty(n, dtype=dtype, device=device)
 
     def set(self, values):
         capturing = self.dev.is_cuda and torch.cuda.is_current_stream_capturing()
@@ -37,7 +38,7 @@ class _PtrTable:
                 raise RuntimeError(f"FusedAdamW: more than {len(self.cap_slots)} captures of the optimizer step (raise _PtrTable.CAPTURE_SLOTS)")
             buf = self.cap_slots[self.cap_used]
             self.cap_used += 1
-            buf[:n].copy_(torch.tensor(values, dtype=torch.int64))
+            buf[:n].copy_(torch.tensor(values, dtype=self.dtype))
             self.dev[:n].copy_(buf[:n], non_blocking=True)
             self.last = None                         # a replay rewrites self.dev behind the host's back: the next eager call uploads again
             return self.dev
@@ -47,7 +48,7 @@ class _PtrTable:
         self.turn ^= 1
         if self.done[k] is not None:
             self.done[k].synchronize()
-        self.host[k][:n].copy_(torch.tensor(values, dtype=torch.int64))
+        self.host[k][:n].copy_(torch.tensor(values, dtype=self.dtype))
         self.dev[:n].copy_(self.host[k][:n], non_blocking=True)
         self.done[k] = None
         if self.dev.is_cuda:
@@ -60,11 +61,46 @@ class _PtrTable:
 
 class FusedAdamW:
     """torch.optim.AdamW semantics (decoupled weight decay, bias correction, eps outside the sqrt) for every parameter that
-    has a gradient at step() time; parameters whose .grad is None are skipped like torch does."""
+    has a gradient at step() time; parameters whose .grad is None are skipped like torch does.
+
+    params: an iterable of tensors (one group), or torch's list of dicts {"params": [...], "lr": ..., "weight_decay": ...} -- parameter groups
+    with their own learning rate and weight decay (missing keys take the constructor's defaults).  betas, eps, the step counter and the bias
+    correction are the optimizer's: one for all groups.  `param_groups` is torch's list of dicts (a scheduler writes "lr" into them), `params` the
+    flat list in group order.  `lr` / `weight_decay` ARE group 0 of a one-group optimizer; with more groups they read group 0 and refuse to be
+    assigned.  One group runs tav_adamw_chunked exactly as before there were groups; more run tav_adamw_chunked_groups: still one launch, with
+    every group's {lr, weight_decay} in a device table that eager steps and graph replays read alike (sync_lr)."""
 
     def __init__(self, params, lr=1e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        self.params = [p for p in params if p.requires_grad]
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        params = list(params)
+        self.betas, self.eps = betas, eps
+        dicts = [isinstance(g, dict) for g in params]
+        if any(dicts) and not all(dicts):
+            raise TypeError("FusedAdamW: params is either a list of tensors or a list of dicts, not a mix")
+        groups = params if params and all(dicts) else [{"params": params}]
+        if len(groups) > 1 and len(groups) > int(lib().tav_optim_max_groups()):
+            raise ValueError(f"FusedAdamW: {len(groups)} parameter groups, the update kernel's table holds {int(lib().tav_optim_max_groups())}")
+        self.param_groups, self.params, self._group_of, seen = [], [], {}, set()
+        for gi, g in enumerate(groups):
+            unknown = set(g) - {"params", "lr", "weight_decay", "betas", "eps"}
+            if unknown:
+                raise ValueError(f"FusedAdamW: parameter group {gi} has options this optimizer does not take: {sorted(unknown)}")
+            if tuple(g.get("betas", betas)) != tuple(betas) or g.get("eps", eps) != eps:
+                raise ValueError(f"FusedAdamW: parameter group {gi} sets its own betas / eps; the fused update keeps ONE step counter and ONE bias "
+                                 "correction for all groups, so betas and eps are the optimizer's (only lr and weight_decay are per group)")
+            plist = [g["params"]] if torch.is_tensor(g["params"]) else list(g["params"])
+            for p in plist:
+                if id(p) in seen:
+                    raise ValueError("FusedAdamW: some parameters appear in more than one parameter group")
+                seen.add(id(p))
+            plist = [p for p in plist if p.requires_grad]
+            for p in plist:
+                self._group_of[p] = gi
+            self.params += plist
+            self.param_groups.append({"params": plist, "lr": g.get("lr", lr), "weight_decay": g.get("weight_decay", weight_decay), "betas": tuple(betas),
+                                      "eps": eps})
+        self._hyper = None           # device table [groups][2] = {lr, weight_decay} of tav_adamw_chunked_groups (more than one group only)
+        self._hyper_host = None      # what the table holds, as the host last wrote it (None: unknown, written again)
+        self._group_table = None
         self.state = {}
         self._tables = None
         self._chunks = None
@@ -78,6 +114,29 @@ class FusedAdamW:
         self.norm_buffers = None
         self._norm_tables = None
         self.generation = 0          # bumped by load_state_dict (new moment tensors): a captured step that points at the old ones is stale
+
+    # lr / weight_decay of a one-group optimizer are group 0's entries (every caller from before there were groups reads and writes these)
+    @property
+    def lr(self):
+        return self.param_groups[0]["lr"]
+
+    @lr.setter
+    def lr(self, value):
+        self._set_group0("lr", value)
+
+    @property
+    def weight_decay(self):
+        return self.param_groups[0]["weight_decay"]
+
+    @weight_decay.setter
+    def weight_decay(self, value):
+        self._set_group0("weight_decay", value)
+
+    def _set_group0(self, key, value):
+        if len(self.param_groups) > 1:
+            raise AttributeError(f"FusedAdamW.{key} cannot be assigned on an optimizer with {len(self.param_groups)} parameter groups: "
+                                 f'write param_groups[i]["{key}"]')
+        self.param_groups[0][key] = value
 
     def zero_grad(self, set_to_none=True):
         """set_to_none=True (torch >= 2.0 default): drop the gradients, the next step() skips those parameters.  set_to_none=False (the default of
@@ -100,6 +159,10 @@ class FusedAdamW:
             self._scal = torch.zeros(8, dtype=torch.float32, device=dev)
             self._step_dev = torch.full((1,), int(getattr(self, "_loaded_step", 0)), dtype=torch.int32, device=dev)
             self._lr_pin = torch.empty(1, dtype=torch.float32).pin_memory()
+            if len(self.param_groups) > 1:
+                self._group_table = _PtrTable(max(n, len(self.params)), dev, torch.int32)
+                self._hyper = torch.zeros(len(self.param_groups), 2, dtype=torch.float32, device=dev)
+                self._hyper_host = None
         for p in act:
             if p not in self.state:
                 if p.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -162,13 +225,21 @@ class FusedAdamW:
             check(lib().tav_clip_coef(ptr(self._scal[0:1]), float(max_norm), ptr(self._scal[1:2]), ptr(self._scal[2:3]), stream()), "clip_coef")
             coef = self._scal[1:2]
             self.last_norm = self._scal[2:3]
-        if self._lr_host != self.lr:                # refresh the device-side learning rate only when the schedule moved it
-            self._lr_pin[0] = self.lr
-            self._scal[4:5].copy_(self._lr_pin, non_blocking=True)
-            self._lr_host = self.lr
-        check(lib().tav_adamw_chunked(ptr(d_p), ptr(d_g), ptr(d_m), ptr(d_v), ptr(d_s), ptr(d_c), n, nchunks, ptr(coef), ptr(self._scal[4:5]),
-                                      self.betas[0], self.betas[1], self.eps, self.weight_decay, ptr(self._step_dev), ptr(self._scal[5:7]), stream()),
-              "adamw_chunked")
+        if len(self.param_groups) > 1:
+            # the group of every ACTIVE tensor, in the order of the pointer tables and through the same staging (a captured upload owns its pinned slot)
+            d_go = self._group_table.set([self._group_of[p] for p in act])
+            self._sync_hyper()
+            check(lib().tav_adamw_chunked_groups(ptr(d_p), ptr(d_g), ptr(d_m), ptr(d_v), ptr(d_s), ptr(d_c), n, nchunks, ptr(coef), ptr(d_go),
+                                                 ptr(self._hyper), len(self.param_groups), self.betas[0], self.betas[1], self.eps, ptr(self._step_dev),
+                                                 ptr(self._scal[5:7]), stream()), "adamw_chunked_groups")
+        else:
+            if self._lr_host != self.lr:            # refresh the device-side learning rate only when the schedule moved it
+                self._lr_pin[0] = self.lr
+                self._scal[4:5].copy_(self._lr_pin, non_blocking=True)
+                self._lr_host = self.lr
+            check(lib().tav_adamw_chunked(ptr(d_p), ptr(d_g), ptr(d_m), ptr(d_v), ptr(d_s), ptr(d_c), n, nchunks, ptr(coef), ptr(self._scal[4:5]),
+                                          self.betas[0], self.betas[1], self.eps, self.weight_decay, ptr(self._step_dev), ptr(self._scal[5:7]), stream()),
+                  "adamw_chunked")
         engine.bump_weight_epoch()          # parameters changed through raw pointers: refresh cached operand copies
         ops.fp8_roll_all()                  # fp8 policy: this step's gathered maxima become the next step's quantisation scales (no-op otherwise)
         return self.last_norm
@@ -182,13 +253,33 @@ class FusedAdamW:
         as an argument: nothing on the host can be overwritten before the device has read it."""
         if self._tables is None:
             raise RuntimeError("FusedAdamW.sync_lr: no optimizer step has run yet")
-        if self._lr_host != self.lr:
+        if len(self.param_groups) > 1:
+            self._sync_hyper()
+        elif self._lr_host != self.lr:
             self._scal[4:5].fill_(self.lr)
             self._lr_host = self.lr
 
+    def _sync_hyper(self):
+        """Bring the device table of the groups' {lr, weight_decay} to param_groups: one fill kernel per entry that moved, the value its argument
+        (no host staging word that a later write could change before the device has read it).  Weight decays move when the optimizer is built or
+        loaded, learning rates whenever a scheduler wrote them.  Inside a capture a fill would be replayed with the value of capture time and undo
+        what sync_lr() wrote before the replay: the table must be current before the capture starts."""
+        G = len(self.param_groups)
+        if self._hyper_host is None:
+            self._hyper_host = [[None, None] for _ in range(G)]
+        for gi, g in enumerate(self.param_groups):
+            for k, key in enumerate(("lr", "weight_decay")):
+                v = float(g[key])
+                if self._hyper_host[gi][k] != v:
+                    if self._hyper.is_cuda and torch.cuda.is_current_stream_capturing():
+                        raise RuntimeError(f'FusedAdamW: param_groups[{gi}]["{key}"] changed since the device table was written; call sync_lr() '
+                                           "before capturing the optimizer step")
+                    self._hyper[gi, k].fill_(v)
+                    self._hyper_host[gi][k] = v
+
     def captures_released(self):
         """Every hipGraph that captured this optimizer's step has been destroyed: the pinned upload slots those captures took may be reused."""
-        for t in self._tables or ():
+        for t in tuple(self._tables or ()) + ((self._group_table,) if self._group_table is not None else ()):
             t.cap_used = 0
 
     # ---- checkpoint format of torch.optim.AdamW (reference utils/global_functions.py:199-258 saves optimizer.state_dict() into best.pt and
@@ -200,18 +291,32 @@ class FusedAdamW:
             if p in self.state:
                 m, v = self.state[p]
                 state[i] = {"step": torch.tensor(float(step)), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(self.params)))}
-        return {"state": state, "param_groups": [group]}
+        groups, first = [], 0
+        for g in self.param_groups:                  # parameter indices run 0 .. n-1 in group order, as torch numbers them
+            groups.append({"lr": g["lr"], "betas": tuple(self.betas), "eps": self.eps, "weight_decay": g["weight_decay"], "amsgrad": False,
+                           "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                           "params": list(range(first, first + len(g["params"])))})
+            first += len(g["params"])
+        return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
         groups = sd["param_groups"]
         idx = [i for g in groups for i in g["params"]]
         if len(idx) != len(self.params):
             raise ValueError(f"optimizer state has {len(idx)} parameters, this optimizer {len(self.params)}")
+        theirs, mine = [len(g["params"]) for g in groups], [len(g["params"]) for g in self.param_groups]
+        if theirs != mine:
+            raise ValueError(f"optimizer state has parameter groups of {theirs} parameters, this optimizer of {mine}")
         g0 = groups[0]
-        self.lr, self.betas, self.eps, self.weight_decay = g0["lr"], tuple(g0["betas"]), g0["eps"], g0["weight_decay"]
+        if any(tuple(g["betas"]) != tuple(g0["betas"]) or g["eps"] != g0["eps"] for g in groups):
+            raise ValueError("optimizer state has per-group betas / eps; the fused update keeps one bias correction and one step counter for all groups")
+        self.betas, self.eps = tuple(g0["betas"]), g0["eps"]
+        for own, g in zip(self.param_groups, groups):
+            own["lr"], own["weight_decay"], own["betas"], own["eps"] = g["lr"], g["weight_decay"], self.betas, self.eps
         self._lr_host = None
+        self._hyper_host = None
+        if self._hyper is not None:
+            self._sync_hyper()                       # the device table of the groups follows the loaded values at once
         self.generation += 1
         steps = set()
         for pos, i in enumerate(idx):
@@ -232,6 +337,49 @@ class FusedAdamW:
     @property
     def step_count(self):
         return int(self._step_dev.item()) if self._tables is not None else int(getattr(self, "_loaded_step", 0))
+
+
+PRETRAINED_STACKS = ("bert", "wav2vec2", "videomae")
+
+
+def default_param_groups(model, PREFormer, lr, weight_decay, encoder_lr_scale=1.0, no_decay_norm_bias=False):
+    """The parameter groups of a fine-tuning run of the TAV model, for FusedAdamW / TrainStep(param_groups=...).
+
+    PRETRAINED parameters are those under the `bert`, `wav2vec2` and `videomae` attributes of either module (the three encoders that start from
+    published weights); NEW ones are everything else (fusion encoder, bridges, embeddings, masked_spec_embed, norms, head: what randomize_model
+    initialises from scratch).  NO-DECAY parameters are those with ndim <= 1 (biases, LayerNorm / GroupNorm weights, embedding vectors).
+    Groups, always in this order, an axis split only when its option is in use and empty groups dropped:
+
+        new, decayed          lr                     weight_decay
+        new, no decay         lr                     0                (no_decay_norm_bias)
+        pretrained, decayed   lr * encoder_lr_scale  weight_decay     (encoder_lr_scale != 1)
+        pretrained, no decay  lr * encoder_lr_scale  0                (both)
+
+    Only parameters that require a gradient are listed, each once, model before PREFormer inside a group.  With encoder_lr_scale == 1.0 and
+    no_decay_norm_bias False the result is the FLAT list TrainStep has always built: one group, the single-group kernel, the same order."""
+    if not encoder_lr_scale > 0:
+        raise ValueError(f"encoder_lr_scale must be positive, got {encoder_lr_scale}")
+    flat = [p for p in model.parameters() if p.requires_grad] + [p for p in PREFormer.parameters() if p.requires_grad]
+    if encoder_lr_scale == 1.0 and not no_decay_norm_bias:
+        return flat
+    seen = set()
+    flat = [p for p in flat if not (id(p) in seen or seen.add(id(p)))]          # (a tensor both modules hold is listed once)
+    pretrained = set()
+    for mod in (model, PREFormer):
+        for name in PRETRAINED_STACKS:
+            stack = getattr(mod, name, None)
+            if stack is not None:
+                pretrained.update(id(p) for p in stack.parameters())
+    buckets = {}
+    for p in flat:
+        key = (encoder_lr_scale != 1.0 and id(p) in pretrained, bool(no_decay_norm_bias) and p.ndim <= 1)
+        buckets.setdefault(key, []).append(p)
+    groups = []
+    for pre in (False, True):
+        for nodecay in (False, True):
+            if buckets.get((pre, nodecay)):
+                groups.append({"params": buckets[(pre, nodecay)], "lr": lr * encoder_lr_scale if pre else lr, "weight_decay": 0.0 if nodecay else weight_decay})
+    return groups
 
 
 def bucket_norm_tables(buffers, chunk):
@@ -290,6 +438,9 @@ class ShardedAdamW(FusedAdamW):
 
     def __init__(self, params, world, rank, group=None, **kw):
         super().__init__(params, **kw)
+        if len(self.param_groups) > 1:
+            raise ValueError("ShardedAdamW takes one parameter group: its update runs over shard pieces with one learning rate and one weight decay "
+                             "(use FusedAdamW, eager or replicated data-parallel, for parameter groups)")
         self.world, self.rank, self.group = int(world), int(rank), group
         self.buckets = {}                 # bucket index -> (parameters, flat buffer, cuts)
         self._ready = False
@@ -299,6 +450,8 @@ class ShardedAdamW(FusedAdamW):
     @classmethod
     def from_replicated(cls, opt, world, rank, group=None):
         """Continue a FusedAdamW (its warm-up steps, or a resumed best.pt) as a sharded optimizer: each rank keeps the slices it will own."""
+        if len(opt.param_groups) > 1:
+            raise ValueError(f"ShardedAdamW.from_replicated: the optimizer has {len(opt.param_groups)} parameter groups; the sharded update takes one")
         new = cls(opt.params, world, rank, group, lr=opt.lr, betas=opt.betas, eps=opt.eps, weight_decay=opt.weight_decay)
         new._full = dict(opt.state)
         new._loaded_step = opt.step_count

@@ -51,7 +51,8 @@ def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
     PREFormer = PreFormer().to(device)
     model, PREFormer = train_tav_network(model, PREFormer, dl_train, dl_val, criterion, param_dict["lr"], param_dict["epoch"], param_dict["weight_decay"],
                                          param_dict["T_max"], Metric, param_dict["patience"], param_dict["clip"], es, None,
-                                         graphs=bool(param_dict.get("graph", 0)), sync=sync)
+                                         graphs=bool(param_dict.get("graph", 0)), sync=sync, encoder_lr_scale=param_dict.get("encoder_lr_scale", 1.0),
+                                         no_decay_norm_bias=bool(param_dict.get("no_decay_norm_bias", 0)))
     evaluate_tav(model, PREFormer, dl_test, Metric, sync=sync)
     return model, PREFormer
 
@@ -70,7 +71,8 @@ def main(argv=None):
     param_dict = {"epoch": args.epoch, "patience": args.patience, "lr": args.learning_rate, "clip": args.clip, "batch_size": args.batch_size,
                   "weight_decay": args.weight_decay, "model": args.model, "T_max": args.T_max, "seed": args.seed, "label_task": args.label_task,
                   "mask": args.mask, "loss": args.loss, "beta": args.beta, "epoch_switch": args.epoch_switch, "weights": weights,
-                  "label2id": {v: k for k, v in id2label.items()}, "id2label": id2label, "graph": args.graph, "loop_sync": args.loop_sync}
+                  "label2id": {v: k for k, v in id2label.items()}, "id2label": id2label, "graph": args.graph, "loop_sync": args.loop_sync,
+                  "encoder_lr_scale": args.encoder_lr_scale, "no_decay_norm_bias": args.no_decay_norm_bias}
     model_param = {"output_dim": args.output_dim, "dropout": args.dropout, "early_div": args.early_div, "num_layers": args.num_layers,
                    "learn_PosEmbeddings": args.learn_PosEmbeddings}
     small = cfg["video"]["image"] != 224

@@ -13,7 +13,7 @@ import torch
 
 from .. import ddp as tav_ddp
 from .. import ops
-from ..optim import FusedAdamW
+from ..optim import FusedAdamW, default_param_groups
 from ..utils.global_functions import checkpoint_file, load_model, save_model
 
 try:                                    # optional, as in the reference's environment
@@ -25,29 +25,51 @@ PATIENCE_ITER = 0
 
 
 class CosineWarmRestarts:
-    """torch CosineAnnealingWarmRestarts(T_0=T_max, T_mult=1, eta_min=0).step(epoch_float) for FusedAdamW."""
+    """torch CosineAnnealingWarmRestarts(T_0=T_max, T_mult=1, eta_min=0).step(epoch_float) for FusedAdamW: one base learning rate per
+    parameter group, every group moved by every step() (an optimizer object without param_groups counts as one group, its `lr`)."""
 
     def __init__(self, optimizer, T_0):
-        self.opt, self.T_0, self.base_lr = optimizer, T_0, optimizer.lr
+        self.opt, self.T_0 = optimizer, T_0
+        self.base_lrs = self._lrs()
+
+    def _lrs(self):
+        groups = getattr(self.opt, "param_groups", None)
+        return [self.opt.lr] if groups is None else [g["lr"] for g in groups]
+
+    def _set_lrs(self, lrs):
+        groups = getattr(self.opt, "param_groups", None)
+        if groups is None:
+            self.opt.lr = lrs[0]
+            return
+        if len(lrs) != len(groups):
+            raise ValueError(f"scheduler has {len(lrs)} learning rates, the optimizer {len(groups)} parameter groups")
+        for g, lr in zip(groups, lrs):
+            g["lr"] = lr
+
+    @property
+    def base_lr(self):
+        return self.base_lrs[0]
 
     def step(self, epoch):
         t_cur = epoch % self.T_0
         self._t_cur, self._last_epoch = t_cur, epoch
-        self.opt.lr = self.base_lr * (1 + math.cos(math.pi * t_cur / self.T_0)) / 2
+        self._set_lrs([base_lr * (1 + math.cos(math.pi * t_cur / self.T_0)) / 2 for base_lr in self.base_lrs])
 
     def get_last_lr(self):
-        return [self.opt.lr]
+        return self._lrs()
 
     def state_dict(self):
         """Keys of torch.optim.lr_scheduler.CosineAnnealingWarmRestarts.state_dict() that define the schedule."""
-        return {"T_0": self.T_0, "T_i": self.T_0, "T_mult": 1, "eta_min": 0, "T_cur": getattr(self, "_t_cur", 0), "base_lrs": [self.base_lr],
-                "last_epoch": getattr(self, "_last_epoch", 0), "_last_lr": [self.opt.lr]}
+        return {"T_0": self.T_0, "T_i": self.T_0, "T_mult": 1, "eta_min": 0, "T_cur": getattr(self, "_t_cur", 0), "base_lrs": list(self.base_lrs),
+                "last_epoch": getattr(self, "_last_epoch", 0), "_last_lr": self._lrs()}
 
     def load_state_dict(self, sd):
-        self.T_0, self.base_lr = sd["T_0"], sd["base_lrs"][0]
+        if len(sd["base_lrs"]) != len(self.base_lrs):
+            raise ValueError(f"scheduler state has {len(sd['base_lrs'])} base learning rates, the optimizer {len(self.base_lrs)} parameter groups")
+        self.T_0, self.base_lrs = sd["T_0"], list(sd["base_lrs"])
         self._t_cur, self._last_epoch = sd.get("T_cur", 0), sd.get("last_epoch", 0)
         if sd.get("_last_lr"):
-            self.opt.lr = sd["_last_lr"][0]
+            self._set_lrs(list(sd["_last_lr"]))
 
 
 def get_statistics(input, label, model, PREFormer, criterion, Metric, check="train", epoch=None, n_visual_true=None, visual_caps=None):
@@ -153,13 +175,20 @@ def recorded_loss(acc, input, label, model, PREFormer, criterion, Metric, check=
 class TrainStep:
     """One optimisation step of reference :56-65: get_statistics -> backward -> (all-reduce) -> clip_grad_norm_ -> AdamW."""
 
-    def __init__(self, model, PREFormer, criterion, lr=1e-6, weight_decay=1e-4, clip=1.0, bucket_mb=48.0, reduce_dtype=None, zero_grad_like_torch_1_10=False):
+    def __init__(self, model, PREFormer, criterion, lr=1e-6, weight_decay=1e-4, clip=1.0, bucket_mb=48.0, reduce_dtype=None, zero_grad_like_torch_1_10=False,
+                 param_groups=None, encoder_lr_scale=1.0, no_decay_norm_bias=False):
+        """param_groups: torch's list of dicts for the optimizer (FusedAdamW); None builds optim.default_param_groups(encoder_lr_scale,
+        no_decay_norm_bias) -- with their defaults the flat parameter list, one group, as ever."""
         self.model, self.pre, self.criterion, self.clip = model, PREFormer, criterion, clip
         # what `model.zero_grad()` (reference :64-65, :98-99, :104-105) does to .grad: torch 1.10 -- the version the reference pins,
         # requirements.txt:100 -- zero-FILLS; torch >= 2.0 sets None.  Matters only for grad_accum's second step (see there).
         self.zero_to_none = not zero_grad_like_torch_1_10
-        self.params = [p for p in model.parameters() if p.requires_grad] + [p for p in PREFormer.parameters() if p.requires_grad]
-        self.opt = FusedAdamW(self.params, lr=lr, weight_decay=weight_decay)
+        if param_groups is None:
+            param_groups = default_param_groups(model, PREFormer, lr, weight_decay, encoder_lr_scale, no_decay_norm_bias)
+        elif encoder_lr_scale != 1.0 or no_decay_norm_bias:
+            raise ValueError("TrainStep: pass either param_groups or encoder_lr_scale / no_decay_norm_bias, not both")
+        self.opt = FusedAdamW(param_groups, lr=lr, weight_decay=weight_decay)
+        self.params = self.opt.params                # (flat, in group order: the reducer's buckets and the optimizer walk the same list)
         self.reducer = None
         alone_ok = os.environ.get("TAV_DDP_SINGLE_RANK", "0") == "1"         # exercise the RCCL path with one rank (tests)
         if torch.distributed.is_available() and torch.distributed.is_initialized() and (torch.distributed.get_world_size() > 1 or alone_ok):
@@ -337,18 +366,22 @@ def one_epoch(epoch, train_dataloader, val_dataloader, model, PREFormer, criteri
 
 
 def train_tav_network(model, PREFormer, train_dataloader, val_dataloader, criterion, learning_rate, epochs, weight_decay, T_max, Metric, patience, clip,
-                      epoch_switch, checkpoint=None, path=None, log_val=2400, zero_grad_like_torch_1_10=False, graphs=False, sync="step"):
+                      epoch_switch, checkpoint=None, path=None, log_val=2400, zero_grad_like_torch_1_10=False, graphs=False, sync="step",
+                      encoder_lr_scale=1.0, no_decay_norm_bias=False):
     """reference :147-164.  `path` (None = keep nothing on disk) replaces the cluster path hard-coded at :137; `checkpoint` is a loaded
     best.pt dict whose optimizer / scheduler state resumes the run (:152-155).  graphs=True: every training batch whose shapes match an
     earlier one of the epoch replays a captured step (graphed.py; same results bit for bit); the whole run then executes on one side stream.
     sync="log" (needs Metrics(on_device=True) or Metric=None): the host reads nothing per step -- loss sum, ragged status word and confusion
     matrix stay on the device (LogSync) and are read every log_val batches, at the end of an epoch and at the end of validate(); losses,
-    matrices, patience and best.pt decisions are the same numbers at the same places as with "step"."""
+    matrices, patience and best.pt decisions are the same numbers at the same places as with "step".
+    encoder_lr_scale / no_decay_norm_bias: optim.default_param_groups -- the pretrained encoders train at learning_rate * encoder_lr_scale, biases
+    and norm weights without weight decay (up to four parameter groups in one fused update; the defaults keep the single group)."""
     if sync not in ("step", "log"):
         raise ValueError(f'sync must be "step" or "log", got {sync!r}')
     if sync == "log" and Metric is not None and not getattr(Metric, "on_device", False):
         LogSync(Metric)                          # raises: says to pass on_device=True
-    stepper = TrainStep(model, PREFormer, criterion, lr=learning_rate, weight_decay=weight_decay, clip=clip, zero_grad_like_torch_1_10=zero_grad_like_torch_1_10)
+    stepper = TrainStep(model, PREFormer, criterion, lr=learning_rate, weight_decay=weight_decay, clip=clip, zero_grad_like_torch_1_10=zero_grad_like_torch_1_10,
+                        encoder_lr_scale=encoder_lr_scale, no_decay_norm_bias=no_decay_norm_bias)
     if graphs:
         from .graphed import run_graphed
         return run_graphed(_train_epochs, stepper, model, PREFormer, train_dataloader, val_dataloader, criterion, epochs, T_max, Metric, patience,

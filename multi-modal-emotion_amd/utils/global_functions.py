@@ -2,7 +2,7 @@
 NewCrossEntropyLoss (:51-83), MySampler (:21-49), arg_parse (:260-297, same flag names) and a dependency-free Metrics
 (the reference wraps torchmetrics, :114-188, which is outside the hot path and not installed here)."""
 import os
-from argparse import ArgumentParser
+from argparse import ArgumentParser, ArgumentTypeError
 
 import torch
 from torch import nn
@@ -167,6 +167,13 @@ class Metrics:
                 (f1 * w).sum().item(), rec.mean().item(), prec.mean().item(), self.cm.clone())
 
 
+def _positive_float(text):
+    v = float(text)
+    if not v > 0:
+        raise ArgumentTypeError(f"must be > 0, got {text}")
+    return v
+
+
 def arg_parse(description, argv=None):
     """Same flag names / defaults as the reference (:260-297); extra flags select the MI355X runtime options."""
     parser = ArgumentParser(description=f" Run experiments on {description} ")
@@ -211,4 +218,9 @@ def arg_parse(description, argv=None):
     parser.add_argument("--loop-sync", dest="loop_sync", default="step", choices=["step", "log"],
                         help="step: the host reads the loss and the metrics after every step, as the reference; log: they stay on the device (one "
                              "ops.step_stats launch per step) and are read where the loops log (tav_nn only; train_tav_network(sync='log'))")
+    parser.add_argument("--encoder-lr-scale", dest="encoder_lr_scale", default=1.0, type=_positive_float,
+                        help="learning rate of the pretrained encoders (bert, wav2vec2, videomae) as a multiple of --learning_rate; the fusion "
+                             "encoder, bridges and head keep --learning_rate (tav_nn only; optim.default_param_groups)")
+    parser.add_argument("--no-decay-norm-bias", dest="no_decay_norm_bias", default=0, type=int, choices=[0, 1],
+                        help="1: no weight decay on biases and LayerNorm / GroupNorm weights (parameters with ndim <= 1; tav_nn only)")
     return parser.parse_args(argv)
