@@ -8,11 +8,9 @@ last gradient of a bucket has been accumulated, a side HIP stream waits on an ev
 all-reduce (average) and re-points the parameters' .grad at views of the reduced bucket (no copy back).  The main stream
 keeps running the backward of earlier layers meanwhile; `finish()` joins the side stream before clipping / the update.
 """
-import os
 
 import torch
 import torch.distributed as dist
-
 
 
 def _rt():
@@ -255,7 +253,7 @@ class BucketedAllReduce:
         """Hook mode packs a gradient the moment autograd has accumulated it -- before the backward pass ends -- so the LayerNorm parameter
         gradients must be complete then: the deferred second stage (ops.ln_flush, run when the pass ends) is switched off while hooks are live."""
         from . import ops
-        ops.ln_defer[0] = not (self._active and not self._manual and bool(self._hooks))
+        ops.ln_hook_mode(self._active and not self._manual and bool(self._hooks))
 
 
 # ====================================================================================================================
@@ -329,10 +327,6 @@ class SegmentedBackward:
             if g is not None:
                 p.grad = g if p.grad is None else p.grad + g
         return self.final[s]
-
-
-_SKIP_REDUCE = os.environ.get("TAV_DDP_SKIP_REDUCE", "0") == "1"
-ARENA = os.environ.get("TAV_DDP_ARENA", "1") == "1"      # gradient arena: the layers' weight-gradient kernels write into the bucket (0: pack everything by copy)     # measurement knob: time the graph chain without the collective (results unreduced)
 
 
 class GraphedStep:
@@ -469,7 +463,7 @@ class GraphedStep:
             for s in range(self.seg.nseg):
                 self._run_and_pack(s)
                 flat = self.flats[s][1]
-                if flat is None or not red._active or _SKIP_REDUCE:
+                if flat is None or not red._active:
                     continue
                 runtime.stream_wait(red.side, stream)               # fork: bucket s is packed
                 with torch.cuda.stream(red.side):
@@ -542,7 +536,7 @@ class GraphedStep:
         from . import runtime
         expected = self._bucket_order([p for p in self.seg.final[s] if p.requires_grad])
         flat, views = None, {}
-        if expected and ARENA:
+        if expected:
             n = sum(p.numel() for p in expected)
             reuse = self.flats[s][1] if len(self.flats) > s and self.flats[s][1] is not None else None     # (eager mode: keep the buffers)
             # allocated inside the capture, i.e. from the graphs' private pool: the reference kept in self.flats pins it for good, and
@@ -557,7 +551,7 @@ class GraphedStep:
             for p in expected:
                 views[id(p)] = flat[off:off + p.numel()].view_as(p)
                 off += p.numel()
-            # the gradient ARENA: the layers' grouped weight-gradient launches of this segment write straight into these views
+            # the gradient arena: the layers' grouped weight-gradient launches of this segment write straight into these views
             runtime.grad_slots.clear()
             runtime.grad_slots.update({p.data_ptr(): views[id(p)] for p in expected})
         try:
@@ -635,10 +629,10 @@ class GraphedStep:
             return
         if self.shard is not None and s is not None:
             self.shard.attach_bucket(s, self.flats[s][0], flat)     # (eager chain: the plan is met bucket by bucket in the first pass)
-            if red._active and not _SKIP_REDUCE:
+            if red._active:
                 self.shard.reduce_to_owners(s, self._wire_dtype(s), average_on_wire=red._avg)
             return
-        if not red._active or _SKIP_REDUCE:
+        if not red._active:
             return
         wd = self._wire_dtype(s) if s is not None else red.reduce_dtype
         buf = flat if wd is None else flat.to(wd)
@@ -711,7 +705,7 @@ class GraphedStep:
         sizes = ", ".join(f"{(flat.numel() * 4 / 2 ** 20) if flat is not None else 0:.0f}" for _, flat in self.flats)
         how = f"{len(self.graphs)} hipGraphs" if self.use_graphs else "eager chain"
         tot = sum(sum(p.numel() for p in pl) for pl, flat in self.flats if flat is not None)
-        arena = f"; gradient arena: {100.0 * getattr(self, 'in_place', 0) / max(tot, 1):.0f} % of the bucket elements written in place by their kernels" if ARENA else ""
+        arena = f"; gradient arena: {100.0 * getattr(self, 'in_place', 0) / max(tot, 1):.0f} % of the bucket elements written in place by their kernels"
         if self.mode == "single":
             return (f"ONE hipGraph (forward, backward in {self.seg.nseg} segments, optimizer); bucket s all-reduced by a CAPTURED raw RCCL call (C ABI "
                     f"tav_allreduce_bucket, RCCL {self.comm.version}) on the reducer branch while segment s+1 runs; buckets [{sizes}] MiB{arena}")

@@ -10,7 +10,6 @@ Design (MI355X-first):
     exactly the tensors its backward needs; nothing is allocated or synchronised inside the kernels, so a whole step can
     be captured into a hipGraph.
 """
-import os
 import weakref
 
 import torch
@@ -26,7 +25,14 @@ def bump_weight_epoch():
 
 
 class Policy:
-    def __init__(self, name="bf16"):
+    """Precision policy of a step: "bf16", "fp32", "fp8", "fp8-all" or "fp8-wgrad8".
+
+    fp8_fwd / fp8_bwd: which GEMMs of an fp8 layer take e4m3 operands (bit 0 qkv, 1 out-proj, 2 FFN1, 3 FFN2; forward and dgrad).  Three cases:
+    a policy without e4m3 sites ("bf16", "fp32") has masks 0 and refuses the arguments (ValueError); an explicit mask is used as given; None
+    means the default -- forward 0 for "fp8", 15 for "fp8-all"; backward 15.  On top of that "fp8-all" and "fp8-wgrad8" IGNORE the arguments
+    and run 15 / 15: their e4m3 weight gradients need the quantised copy of every operand.  Nothing is read from the process environment."""
+
+    def __init__(self, name="bf16", fp8_fwd=None, fp8_bwd=None):
         name = {"bfloat16": "bf16", "float32": "fp32", "f32": "fp32", "float8": "fp8", "e4m3": "fp8"}.get(name, name)
         if name not in ("bf16", "fp32", "fp8", "fp8-all", "fp8-wgrad8"):
             raise ValueError(f"unknown precision policy {name!r}")
@@ -45,17 +51,23 @@ class Policy:
         # since the 256-wide weight-gradient tile exists (profiles/r02_experiments.md).
         self.fp8_wgrad8 = name in ("fp8-wgrad8", "fp8-all")
         # which of a layer's GEMMs take e4m3 operands: bit 0 qkv, 1 out-proj, 2 FFN1, 3 FFN2 -- forward (fwd) and their dgrads (bwd).
-        # The others run the bf16 kernels.  (TAV_FP8_FWD_MASK / TAV_FP8_BWD_MASK: error-attribution experiments, tools/gpu_fp8_attrib.py.)
+        # The others run the bf16 kernels.  (The fp8_fwd / fp8_bwd arguments: error-attribution experiments, tools/gpu_fp8_attrib.py.)
         # Default (round 4, measured at config 5's REAL depth -- 24 video layers -- over THREE seeds, profiles/r04_fp8_seeds.txt): NO forward GEMM on
         # e4m3.  Round 3 kept the QKV projection (logits 6.1e-3 on seed 0), but that was one lucky draw: the same policy gives 1.13e-2 and 1.36e-2 on
         # seeds 1 and 2 -- over the 1e-2 budget -- with the pre-scaled or the plain q alike (bf16: 5.9e-3 / 7.2e-3 / 4.2e-3); e4m3 out-proj / FFN1 /
         # FFN2 inputs cost 1.5e-2 .. 2.2e-2 each (profiles/r03_fp8_attribution.txt), also under MX block scales (profiles/r04_fp8_mx_emulation.txt).
-        # All four dgrads stay on e4m3: they cannot touch the logits or the loss, and the gradient norm moves by < 2.5e-3.  TAV_FP8_FWD_MASK=1
+        # All four dgrads stay on e4m3: they cannot touch the logits or the loss, and the gradient norm moves by < 2.5e-3.  fp8_fwd=1
         # restores round 3's policy; "fp8-all" / "fp8-wgrad8" remain the all-e4m3 throughput experiments.
-        self.fp8_fwd = int(os.environ.get("TAV_FP8_FWD_MASK", "15" if name == "fp8-all" else "0")) if self.fp8 else 0
-        self.fp8_bwd = int(os.environ.get("TAV_FP8_BWD_MASK", "15")) if self.fp8 else 0
+        if not self.fp8 and (fp8_fwd is not None or fp8_bwd is not None):
+            raise ValueError(f"fp8_fwd / fp8_bwd select the e4m3 GEMMs of an fp8 policy; {name!r} has none")
+        self.fp8_fwd = self.fp8_bwd = 0
+        if self.fp8:
+            self.fp8_fwd = int(fp8_fwd) if fp8_fwd is not None else (15 if name == "fp8-all" else 0)
+            self.fp8_bwd = int(fp8_bwd) if fp8_bwd is not None else 15
         if self.fp8_wgrad8:
             self.fp8_fwd = self.fp8_bwd = 15             # (the e4m3 weight gradients read the transposed quantised copies of every operand)
+        # dgrad outputs that only feed a LayerNorm backward leave the GEMM in the operand dtype (EncoderLayerFn.backward); False: in f32
+        self.dgrad_lp = True
 
 
 class WeightCache:
@@ -216,11 +228,8 @@ def _to_lp(pol, x32):
 _LP_HINT = {}
 
 
-_LP_HINT_ON = os.environ.get("TAV_LP_HINT", "1") == "1"
-
-
 def _hint_set(g32, glp):
-    if _LP_HINT_ON and glp is not None and g32 is not None and g32.is_cuda:
+    if glp is not None and g32 is not None and g32.is_cuda:
         _LP_HINT[torch.cuda.current_stream().cuda_stream] = (g32, glp)
 
 
@@ -233,13 +242,6 @@ def _hint_take(g):
 
 def _c(t):
     return t if t is None or t.is_contiguous() else t.contiguous()
-
-
-_BWD_LP_OUT = os.environ.get("TAV_BWD_LP_OUT", "1") == "1"
-
-
-def _DGRAD_OUT(pol):
-    return torch.float32 if (pol.f32 or not _BWD_LP_OUT) else pol.lp
 
 
 # ---------------------------------------------------------------------------------------------- encoder layer
@@ -256,9 +258,7 @@ class LayerSpec:
         self.head_scale, self.probs_out = head_scale, probs_out
 
 
-GROUPED_WGRAD = [os.environ.get("TAV_GROUPED_WGRAD", "1") == "1"]
-# attention pre-scale of the q rows (see WeightCache.layer); TAV_ATTN_PRESCALE=0 keeps q unscaled (the round-2 kernels' convention, A/B)
-QSC = ops.ATTN_Q_PRESCALE if os.environ.get("TAV_ATTN_PRESCALE", "1") == "1" else None
+QSC = ops.ATTN_Q_PRESCALE          # attention pre-scale of the q rows (see WeightCache.layer)
 
 
 def _layer_wgrads(pairs, into=None):
@@ -266,7 +266,7 @@ def _layer_wgrads(pairs, into=None):
     every tile sums over all tokens (no split slabs, no reduce kernels) when the layer's tiles fill the chip; else one TN GEMM each.
     into: destinations inside a data-parallel bucket (see _arena_into), honoured by the grouped launch."""
     tiles = sum(((a.shape[1] + 127) // 128) * ((b.shape[1] + 127) // 128) for a, b in pairs)
-    if GROUPED_WGRAD[0] and len(pairs) <= 4 and tiles >= 256:
+    if len(pairs) <= 4 and tiles >= 256:
         return ops.gemm_tn_grouped(pairs, want_bias=True, into=into)
     return [ops.gemm_tn(a, b, want_bias=True) for a, b in pairs]
 
@@ -338,8 +338,6 @@ class EncoderLayerFn(torch.autograd.Function):
         def lin(bit, inp, w_n, w_8, tag, **kw):       # one forward linear -> (output, the Fp8 copy of its input or None)
             if not fm & bit:
                 return ops.gemm_nt(inp, w_n, **kw), None
-            if _MX_EMULATE and bit != 1:
-                return ops.gemm_nt(_mx_roundtrip(inp), _mx_roundtrip(w_n), **kw), None
             inp8 = ops.fp8_quantize(inp, want_t=w8, state=st(tag))
             return ops.gemm_nt_fp8(inp8, w_8, **kw), inp8
 
@@ -350,7 +348,7 @@ class EncoderLayerFn(torch.autograd.Function):
             a = x_lp if x_lp is not None else _to_lp(pol, x)
             mean1 = rstd1 = None
         qkv, a8 = lin(1, a, wqkv, wqkv8, "a", bias=bqkv)
-        o, lse, aux = ops.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=QSC is not None,
+        o, lse, aux = ops.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=True,
                                    seq_lens=spec.seq_lens)
         hs, o_ctx = spec.head_scale, o
         if hs is not None:                                      # head_mask: context = m_h * softmax(s) v (+ the rank-1 mask term, unscaled)
@@ -362,7 +360,7 @@ class EncoderLayerFn(torch.autograd.Function):
                 raise NotImplementedError("head_mask with a pre-softmax key mask is not on any path of the reference")
         if spec.probs_out is not None:
             spec.probs_out.append(ops.attn_probs(qkv[:, :H], qkv[:, H:2 * H], lse, B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode,
-                                                 q_prescaled=QSC is not None, head_scale=hs))
+                                                 q_prescaled=True, head_scale=hs))
         y1, o8 = lin(2, o_ctx, wo_n, wo8, "o", bias=bo, resid=x, out_dtype=torch.float32)
         if spec.pre_ln:
             x1 = y1
@@ -406,9 +404,9 @@ class EncoderLayerFn(torch.autograd.Function):
             a8, o8, c8, h8 = (ops.Fp8(None, t, s, M, t.shape[0]) for t, s in zip(sv[19:27:2], sv[20:27:2]))
         # dgrad outputs that ONLY feed a LayerNorm backward (pre-LN layers) leave the GEMM in the operand dtype: LN backward takes the
         # rounded values straight into its f32 row arithmetic and adds the f32 residual gradient there, so the residual stream itself
-        # stays f32 -- and the GEMM epilogue writes, and LN backward reads, half the bytes (TAV_BWD_LP_OUT=0: f32 as in round 2).
+        # stays f32 -- and the GEMM epilogue writes, and LN backward reads, half the bytes (Policy.dgrad_lp).
         # An fp8 layer keeps them f32.
-        dgrad_out = torch.float32 if fp8 else _DGRAD_OUT(pol)
+        dgrad_out = pol.lp if pol.dgrad_lp and not fp8 else torch.float32
 
         def dgrad(dy_lp, bit, w_8, w_t, **kw):   # dY [M, N] x W [N, K] -> [M, K]: the NT GEMM against the transposed copy W^T [K, N(_pad)]
             if bm & bit:
@@ -434,22 +432,22 @@ class EncoderLayerFn(torch.autograd.Function):
             dy1, dy1_lp, dg1, db1 = _ln_bwd(pol, g1, y1, ln1_w, ln1_b, mean1, rstd1)
         # attention
         do, dy18 = dgrad(dy1_lp, 2, wo8, wo_t)
-        qs, ks, vs, pre = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], QSC is not None
+        qs, ks, vs = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
         if hs is None:
             dqkv = ops.attn_bwd(qs, ks, vs, o, do, lse, (corr, o_soft) if spec.mask_mode == 2 else None,
-                                B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=pre, seq_lens=spec.seq_lens)
+                                B, S, nh, key_mask=key_mask, mask_mode=spec.mask_mode, q_prescaled=True, seq_lens=spec.seq_lens)
         elif spec.mask_mode == 2:
             # context = o + (m_h - 1) o_soft: the whole of dO goes through the usual backward, (m_h - 1) dO once more through the softmax part alone
-            dqkv = ops.attn_bwd(qs, ks, vs, o, do, lse, (corr, o_soft), B, S, nh, key_mask=key_mask, mask_mode=2, q_prescaled=pre)
-            dqkv2 = ops.attn_bwd(qs, ks, vs, o_soft, ops.head_scale(None, do, hs, -1.0, B, S, nh), lse, None, B, S, nh, mask_mode=0, q_prescaled=pre)
+            dqkv = ops.attn_bwd(qs, ks, vs, o, do, lse, (corr, o_soft), B, S, nh, key_mask=key_mask, mask_mode=2, q_prescaled=True)
+            dqkv2 = ops.attn_bwd(qs, ks, vs, o_soft, ops.head_scale(None, do, hs, -1.0, B, S, nh), lse, None, B, S, nh, mask_mode=0, q_prescaled=True)
             ops.head_scale(dqkv, dqkv2, None, 1.0, B, S, 3 * nh, out=dqkv)
         else:                                                   # context = m_h o
-            dqkv = ops.attn_bwd(qs, ks, vs, o, ops.head_scale(None, do, hs, 0.0, B, S, nh), lse, None, B, S, nh, mask_mode=0, q_prescaled=pre)
+            dqkv = ops.attn_bwd(qs, ks, vs, o, ops.head_scale(None, do, hs, 0.0, B, S, nh), lse, None, B, S, nh, mask_mode=0, q_prescaled=True)
         if hs is not None:
             o = o_ctx                                           # what the out-projection multiplied (its weight gradient below)
         if spec.pre_ln:
             da, dqkv8 = dgrad(dqkv, 1, wqkv8, wqkv_t, out_dtype=dgrad_out)
-            g0, g0_lp, dg1, db1 = _ln_bwd(pol, da, x, ln1_w, ln1_b, mean1, rstd1, dx_add=dy1, need_lp=_LP_HINT_ON and not pol.f32)
+            g0, g0_lp, dg1, db1 = _ln_bwd(pol, da, x, ln1_w, ln1_b, mean1, rstd1, dx_add=dy1, need_lp=not pol.f32)
             if not pol.f32:
                 _hint_set(g0, g0_lp)
         else:
@@ -466,31 +464,7 @@ class EncoderLayerFn(torch.autograd.Function):
         return (g0, None, None, None, None, *grads)
 
 
-# Experiment hook (tools/gpu_fp8_mx_probe.py; never set in the product): TAV_FP8_MX_EMULATE=1 runs the forward GEMMs selected by Policy.fp8_fwd bits
-# 1-3 (out-proj / FFN1 / FFN2) on operands rounded to MX-e4m3 -- e4m3 elements with a power-of-two scale per 32 k-values, the format the
-# block-scaled MFMA takes natively -- by quantise / dequantise in torch, to measure what block scales would buy BEFORE building that path.
-_MX_EMULATE = os.environ.get("TAV_FP8_MX_EMULATE", "0") == "1"
-
-
-def _mx_roundtrip(x, block=32):
-    M, K = x.shape
-    xb = x.float().reshape(M, K // block, block)
-    amax = xb.abs().amax(-1, keepdim=True).clamp_min(1e-30)
-    sc = torch.exp2(torch.floor(torch.log2(448.0 / amax)))           # E8M0: the largest power of two that keeps the block inside +-448
-    return ((xb * sc).to(torch.float8_e4m3fn).float() / sc).reshape(M, K).to(x.dtype)
-
-
-_F32_BRANCHES = tuple(b for b in os.environ.get("TAV_F32_BRANCHES", "").split(",") if b)      # error attribution only (tools/gpu_bf16_attrib.py)
-_f32_ctx = []
-
-
 def encoder_layer(ectx, spec, x, x_lp, key_mask, params):
-    if _F32_BRANCHES and spec.branch in _F32_BRANCHES and not ectx.pol.f32:
-        # attribution experiment: this stack's transformer layers run under the fp32 policy inside an otherwise bf16 step
-        if not _f32_ctx:
-            _f32_ctx.append(Ctx("fp32"))
-        x2, _ = EncoderLayerFn.apply(x, None, key_mask, _f32_ctx[0], spec, *params)
-        return x2, None
     fp8, slow = _fp8_layer(ectx.pol, spec), spec.head_scale is not None or spec.probs_out is not None
     if fp8 and slow:
         raise NotImplementedError("head_mask / output_attentions are built for the bf16 and fp32 policies only")
@@ -711,8 +685,9 @@ class GroupNormGeluFn(torch.autograd.Function):
         return dx, dg, db, None
 
 
-# Input gradient of the strided convs without a column buffer (round 4; 0 = the NT GEMM into [T_out, k*Ci] + col2im of rounds 1-3).
-CONV_PHASE_DGRAD = [os.environ.get("TAV_CONV_PHASE", "1") == "1"]
+# Input gradient of the strided convs without a column buffer (round 4; False = the NT GEMM into [T_out, k*Ci] + col2im of rounds 1-3,
+# also the fallback of the shapes the phase form does not cover).
+CONV_PHASE_DGRAD = [True]
 CONV_PAD = 2                  # zero rows in front of and behind every batch entry of a padded gradient buffer (covers k <= 3 * stride taps)
 _CONV_PADDED = {}             # data_ptr of a padded buffer's interior view -> the buffer, from the layer that wrote it to the one that reads it
 

@@ -259,32 +259,13 @@ class PreFormer(nn.Module):
             hidden, hidden_lp = E.layer_norm_f32(ectx, hidden, enc.layer_norm.weight, enc.layer_norm.bias, self.cfg["audio"]["eps"])   # :361
             return E.LinearFn.apply(hidden, hidden_lp if not ectx.pol.f32 else None, self.wav_2_768.weight, self.wav_2_768.bias, None, ectx, True)   # :363
 
-        main = torch.cuda.current_stream()
-        side = runtime.multistream[0] and runtime.front_side[0] and audio_features.is_cuda
-        if side:        # the three front-ends are independent (models/tav.py:349-368): audio and video on side streams, text here
-            ev = torch.cuda.Event()
-            ev.record(main)
-            s_a, s_v = runtime.front_streams(2)
-            runtime.share_with(s_a, audio_features, audio_mask)
-            runtime.share_with(s_v, video_embeds, visual_mask)
-            with torch.cuda.stream(s_a):
-                runtime.stream_wait(s_a, main, ev)
-                x_audio = audio_frontend()
-            with torch.cuda.stream(s_v):
-                runtime.stream_wait(s_v, main, ev)
-                x_video, Nv = video_frontend()
         if input_ids is not None:
             input_ids = input_ids.to(dev)
             x_text, _ = self.bert.embed(input_ids)                                      # :349
             St = input_ids.shape[1]
             parts.append(x_text)
-        if side:
-            for st, ten in ((s_a, x_audio), (s_v, x_video)):
-                runtime.stream_wait(main, st)
-                ten.record_stream(main)
-        else:
-            x_audio = audio_frontend()
-            x_video, Nv = video_frontend()
+        x_audio = audio_frontend()
+        x_video, Nv = video_frontend()
         parts += [x_audio, x_video]
         tav = E.ConcatSeqFn.apply(B, *parts)                                            # :372-375
 

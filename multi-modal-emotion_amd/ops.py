@@ -5,7 +5,6 @@ No arithmetic happens here; torch is used for device memory and streams only.  S
 """
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import torch
@@ -203,8 +202,7 @@ class Fp8:
 # Delayed scaling (round 4): a tensor that is quantised every step at the same place of the graph keeps a 4-float STATE on the device
 # (tav_fp8_quantize_delayed).  Its first quantisation calibrates (current scaling: amax passes + quantiser, what rounds 2-3 did every time);
 # from then on ONE launch quantises with the scale the previous step left and gathers the new maximum on the way; fp8_roll_all() -- called by the
-# optimizer step, inside the captured graph -- turns the gathered maxima into the next step's scales.  TAV_FP8_DELAYED=0: always current scaling.
-fp8_delayed = [os.environ.get("TAV_FP8_DELAYED", "1") == "1"]
+# optimizer step, inside the captured graph -- turns the gathered maxima into the next step's scales.
 _fp8_state_sets = []
 
 
@@ -253,7 +251,7 @@ def fp8_quantize(x, *, want_q=True, want_t=False, state=None):
         sts, key = state
         i = sts.slot(key)
         scales = sts.dev[i]
-        if fp8_delayed[0] and i in sts.calibrated:
+        if i in sts.calibrated:
             check(lib().tav_fp8_quantize_delayed(ptr(x), dt(x), rows, cols, x.stride(0), ptr(scales), ptr(q), cols, ptr(qt), rows_pad, rows_pad, stream()),
                   "fp8_quantize_delayed")
             return Fp8(q, qt, scales, rows, cols)
@@ -417,8 +415,20 @@ def ln_fwd(x, gamma, beta, eps, *, want_f32=True, lp_dtype=None, act=0):
 #     clone the still unwritten buffer);
 #   * a parameter that already HAS a gradient is accumulated in place, at once: it reads the buffer -- so a LayerNorm whose gamma / beta
 #     carry a gradient (accumulation over several backwards, zero-filled gradients) is reduced immediately, not deferred.
-ln_defer = [os.environ.get("TAV_LN_DEFER", "1") == "1"]      # (TAV_LN_DEFER=0: the immediate two-launch form, for A/B runs)
+# Two facts, kept apart: whether this torch can run the flush when the pass ends (cleared for good by the queue_callback fallback below), and
+# whether a hook-mode reducer is live (ln_hook_mode, owned by ddp.BucketedAllReduce).
+_ln_state = {"supported": True, "hook_mode": False}
 _ln_pending = {"task": -1, "items": []}
+
+
+def ln_hook_mode(live):
+    """A hook-mode gradient reducer went live / away: while one is, LayerNorm parameter gradients are reduced at once."""
+    _ln_state["hook_mode"] = bool(live)
+
+
+def ln_deferring():
+    """Whether a LayerNorm backward inside an autograd pass defers its parameter reduce to the end of the pass."""
+    return _ln_state["supported"] and not _ln_state["hook_mode"]
 
 
 def _graph_task_id():
@@ -454,7 +464,7 @@ def _ln_defer_register(part, dgamma, dbeta, nblk, W):
         try:
             torch.autograd.Variable._execution_engine.queue_callback(ln_flush)
         except Exception:                       # (a torch without this private hook: reduce at once and stop deferring)
-            ln_defer[0] = False
+            _ln_state["supported"] = False
             _ln_pending["items"] = [item]
             ln_flush()
             return
@@ -476,7 +486,7 @@ def ln_bwd(dy, x, gamma, beta, mean, rstd, *, dx_add=None, want_f32=True, lp_dty
         dgamma = torch.empty(W, dtype=torch.float32, device=x.device)
         dbeta = torch.empty(W, dtype=torch.float32, device=x.device)
         nblk = lib().tav_ln_bwd_partials(rows)
-        defer = ln_defer[0] and _graph_task_id() >= 0 and _grad_free_leaf(gamma) and _grad_free_leaf(beta)
+        defer = ln_deferring() and _graph_task_id() >= 0 and _grad_free_leaf(gamma) and _grad_free_leaf(beta)
         if defer:
             part = torch.empty(nblk * 2 * W, dtype=torch.float32, device=x.device)      # its own slab: alive until ln_flush()
         else:

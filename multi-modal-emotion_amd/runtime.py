@@ -4,10 +4,11 @@ from . import engine
 _ctx = None
 
 
-def set_precision(name="bf16"):
-    """'bf16' (bf16 operands / f32 accumulate, the benchmarked mode) or 'fp32' (exact-f32 MFMA, parity mode)."""
+def set_precision(policy="bf16"):
+    """'bf16' (bf16 operands / f32 accumulate, the benchmarked mode), 'fp32' (exact-f32 MFMA, parity mode), one of the 'fp8*' names, or an
+    engine.Policy built by the caller (e.g. Policy("fp8", fp8_fwd=1): an fp8 policy with its own e4m3 masks)."""
     global _ctx
-    _ctx = engine.Ctx(name)
+    _ctx = engine.Ctx(policy)
     return _ctx
 
 
@@ -112,33 +113,15 @@ _inputs_event = [None]
 multistream = [True]
 
 
-import os as _os
-
-front_side = [_os.environ.get("TAV_FRONT_STREAMS", "0") == "1"]     # PreFormer front-ends on side streams (measured: slower, off)
-_prio = _os.environ.get("TAV_STREAM_PRIO", "0") == "1"     # measured: priorities break the overlap under graph replay (55 vs 37.7 ms)
-
-
 def branch_streams(n=3):
-    """(audio, video, text) streams; the video branch is the critical path, so it gets the high priority."""
+    """(audio, video, text) streams.  All at the default priority: a high-priority video stream broke the overlap under graph replay
+    (measured: 55 vs 37.7 ms)."""
     import torch
     dev = torch.cuda.current_device()
     if dev not in _streams:
-        pr = [0, -1, 0] if _prio else [0, 0, 0]
-        _streams[dev] = [torch.cuda.Stream(device=dev, priority=pr[i]) for i in range(n)]
+        _streams[dev] = [torch.cuda.Stream(device=dev) for _ in range(n)]
     _register_branches(_streams[dev])
     return _streams[dev]
-
-
-_front = {}
-
-
-def front_streams(n=2):
-    import torch
-    dev = torch.cuda.current_device()
-    if dev not in _front:
-        _front[dev] = [torch.cuda.Stream(device=dev) for _ in range(n)]
-    _register_branches(_front[dev])
-    return _front[dev]
 
 
 # ---- capture guard.  Round 3 lost a run to a core dump (`hipStreamEndCapture` inside torch/cuda/graphs.py capture_end, ROCm 7.2): while a
@@ -176,7 +159,7 @@ def check_edge(waiter, producer):
     for st in (waiter, producer):
         if not known(st):
             raise RuntimeError(f"hipGraph capture on {origin}: stream {st} is neither the capture's origin nor one of its registered branches "
-                               f"(runtime.branch_streams / front_streams / fork); a dependency on it ({waiter} waits for {producer}) would crash hipStreamEndCapture")
+                               f"(runtime.branch_streams / fork); a dependency on it ({waiter} waits for {producer}) would crash hipStreamEndCapture")
     if not _same(waiter, origin) and not _same(producer, origin):
         raise RuntimeError(f"hipGraph capture on {origin}: dependency between two branch streams ({waiter} waits for {producer}); under capture every "
                            f"edge must start or end at the origin stream (ROCm 7.2 crashes in hipStreamEndCapture otherwise) -- join through the origin")
@@ -194,7 +177,7 @@ def stream_wait(waiter, producer, event=None):
 
 class capture:
     """`with runtime.capture(graph, stream, **kw):` = torch.cuda.graph(graph, stream=stream, **kw) with the guard above armed: `stream` is the
-    origin; streams handed out by branch_streams() / front_streams() inside the block (or passed as `branches=`) are its branches.
+    origin; streams handed out by branch_streams() inside the block (or passed as `branches=`) are its branches.
     Dropout drawn inside the block reads its seeds from device words that live as long as the graph does (see dropout_seeds): a plain
     graph.replay() repeats the draws that followed the capture, capture.replay() takes fresh ones as eager calls would."""
 

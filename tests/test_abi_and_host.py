@@ -621,6 +621,91 @@ def test_kernel_sources_carry_no_compile_time_switches():
             assert not m or guard, f"{f}:{n + 1}: {line.strip()}"
 
 
+def test_python_package_reads_only_its_three_environment_variables():
+    """The Python half of the same rule: the package reads TAV_LIB (the two-build A/B of tools/ab_build.sh), TAV_DEBUG_CHECKS (host-synchronising
+    input checks) and TAV_DDP_SINGLE_RANK (the one-rank data-parallel step of the tests and bench.py) from the environment and nothing else;
+    experiments are arguments (engine.Policy) or branches, never latent switches in the process environment."""
+    pkg = os.path.join(ROOT, "multi-modal-emotion_amd")
+    names, nfiles = set(), 0
+    for d, _, fs in os.walk(pkg):
+        for f in fs:
+            if f.endswith(".py"):
+                nfiles += 1
+                for line in open(os.path.join(d, f)).read().splitlines():
+                    if re.search(r"\benviron\b|getenv", line):
+                        names.update(re.findall(r"""["']([A-Z][A-Z0-9_]*)["']""", line))
+    assert nfiles >= 20
+    assert names == {"TAV_LIB", "TAV_DEBUG_CHECKS", "TAV_DDP_SINGLE_RANK"}, sorted(names)
+
+
+def test_policy_masks_are_arguments_not_environment(monkeypatch):
+    """engine.Policy: the e4m3 masks of an fp8 policy are keyword arguments with the documented defaults, forced to 15 / 15 by the e4m3 weight
+    gradients, refused on a policy without e4m3 sites -- and nothing in the process environment changes what a policy name means."""
+    from tav_amd.engine import Ctx, Policy
+    assert [(Policy(n).fp8_fwd, Policy(n).fp8_bwd) for n in ("fp8", "fp8-all", "fp8-wgrad8")] == [(0, 15), (15, 15), (15, 15)]
+    assert [(Policy(n).fp8_fwd, Policy(n).fp8_bwd, Policy(n).fp8) for n in ("bf16", "fp32")] == [(0, 0, False)] * 2
+    p = Policy("fp8", fp8_fwd=1, fp8_bwd=12)
+    assert (p.fp8_fwd, p.fp8_bwd, p.fp8_wgrad8) == (1, 12, False)
+    p = Policy("fp8", fp8_fwd=0, fp8_bwd=0)
+    assert (p.fp8_fwd, p.fp8_bwd) == (0, 0) and p.fp8 and p.fp8_stacks == ("video",)
+    assert (Policy("fp8", fp8_bwd=3).fp8_fwd, Policy("fp8", fp8_bwd=3).fp8_bwd) == (0, 3)
+    assert (Policy("fp8-all", fp8_fwd=5).fp8_fwd, Policy("fp8-all", fp8_fwd=5).fp8_bwd) == (15, 15)      # "fp8-all" has e4m3 weight gradients too
+    p = Policy("fp8-wgrad8", fp8_fwd=1, fp8_bwd=2)
+    assert (p.fp8_fwd, p.fp8_bwd, p.fp8_wgrad8) == (15, 15, True)
+    for kw in ({"fp8_fwd": 1}, {"fp8_bwd": 0}):
+        for name in ("bf16", "fp32"):
+            with pytest.raises(ValueError, match="fp8_fwd / fp8_bwd"):
+                Policy(name, **kw)
+    # dgrad outputs in the operand dtype: on by default wherever the operand dtype is not f32 anyway (an fp8 LAYER still takes f32 ones)
+    assert all(Policy(n).dgrad_lp is True and Policy(n).lp == torch.bfloat16 for n in ("bf16", "fp8", "fp8-all", "fp8-wgrad8"))
+    assert Policy("fp32").lp == torch.float32                                                         # either way an f32 dgrad output
+    monkeypatch.setenv("TAV_FP8_FWD_MASK", "1")
+    monkeypatch.setenv("TAV_FP8_BWD_MASK", "0")
+    monkeypatch.setenv("TAV_BWD_LP_OUT", "0")
+    p = Policy("fp8")
+    assert p.fp8_fwd == 0 and p.fp8_bwd == 15 and p.dgrad_lp is True
+    given = Policy("fp8", fp8_fwd=3)
+    assert Ctx(given).pol is given and Ctx("fp8").pol.fp8_fwd == 0                                    # a context takes a built policy as it is
+
+
+def test_ln_deferral_keeps_torch_support_and_hook_mode_apart():
+    """ops.ln_deferring(): the deferred LayerNorm parameter reduce needs a torch that can run the flush when the pass ends (a fact the
+    queue_callback fallback clears for good) AND no live hook-mode reducer (ops.ln_hook_mode, driven by ddp.BucketedAllReduce).  A reducer
+    going away must not turn deferral back on where torch cannot do it.  No process group: the reducer's own method runs on a stand-in."""
+    from tav_amd import ddp, ops
+    saved = dict(ops._ln_state)
+    try:
+        ops._ln_state.update(supported=False, hook_mode=False)
+        assert not ops.ln_deferring()
+        ops.ln_hook_mode(True)
+        assert not ops.ln_deferring()
+        ops.ln_hook_mode(False)
+        assert not ops.ln_deferring()                         # hook mode off does not bring back what torch cannot do
+        assert ops._ln_state["supported"] is False
+
+        class Reducer:                                         # what BucketedAllReduce._sync_ln_defer reads of its reducer
+            def __init__(self, active, manual, hooks):
+                self._active, self._manual, self._hooks = active, manual, hooks
+        for red in (Reducer(True, False, [object()]), Reducer(True, False, []), Reducer(False, False, [object()])):
+            ddp.BucketedAllReduce._sync_ln_defer(red)
+            assert not ops.ln_deferring() and ops._ln_state["supported"] is False
+
+        ops._ln_state.update(supported=True, hook_mode=False)
+        assert ops.ln_deferring()
+        ops.ln_hook_mode(True)
+        assert not ops.ln_deferring()
+        ops.ln_hook_mode(False)
+        assert ops.ln_deferring()
+        for red, defer in ((Reducer(True, False, [object()]), False), (Reducer(True, True, [object()]), True), (Reducer(True, False, []), True),
+                           (Reducer(False, False, [object()]), True)):
+            ddp.BucketedAllReduce._sync_ln_defer(red)
+            assert ops.ln_deferring() is defer
+        assert not hasattr(ops, "ln_defer")                   # no list for another module to write into
+    finally:
+        ops._ln_state.clear()
+        ops._ln_state.update(saved)
+
+
 def test_head_mask_layouts_and_oracle_head_mask():
     """VideoMAEEncoder's head_mask entry (reference utils/TAVFormer.py:190, :368-370): the layouts HF's get_head_mask produces become per-head
     factors, anything finer is refused; the oracle's restatement multiplies the probabilities before the post-softmax mask is added."""

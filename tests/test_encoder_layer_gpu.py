@@ -58,15 +58,14 @@ def _step(policy, shape, pre_ln, params, x, gy):
 
 @pytest.mark.parametrize("pre_ln", [True, False])
 @pytest.mark.parametrize("shape", ["wide", "narrow"])
-def test_fp8_layer_without_e4m3_sites_is_the_bf16_layer(gpu, monkeypatch, shape, pre_ln):
+def test_fp8_layer_without_e4m3_sites_is_the_bf16_layer(gpu, shape, pre_ln):
     params, x, gy = _case(shape)
-    monkeypatch.setenv("TAV_FP8_FWD_MASK", "0")
-    monkeypatch.setenv("TAV_FP8_BWD_MASK", "0")
-    monkeypatch.setattr(engine, "_BWD_LP_OUT", False)
-    pol = engine.Policy("fp8")
+    pol = engine.Policy("fp8", fp8_fwd=0, fp8_bwd=0)
     assert pol.fp8 and "video" in pol.fp8_stacks and pol.fp8_fwd == 0 and pol.fp8_bwd == 0 and not pol.fp8_wgrad8
+    plain = engine.Policy("bf16")
+    plain.dgrad_lp = False                       # f32 dgrad outputs, as an fp8 layer forces them
     got = _step(pol, shape, pre_ln, params, x, gy)
-    ref = _step("bf16", shape, pre_ln, params, x, gy)
+    ref = _step(plain, shape, pre_ln, params, x, gy)
     names = ["x2", "dx"] + [f"param {i}" for i in range(16)]
     diff = [n for n, a, b in zip(names, got, ref) if not torch.equal(a, b)]
     print(f"[{shape}, pre_ln={pre_ln}] tensors that differ: {diff or 'none'}")

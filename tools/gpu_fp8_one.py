@@ -1,5 +1,6 @@
-"""Config 5 at full depth (24 video layers), batch 2, ONE policy setting from the environment (TAV_FP8_FWD_MASK / TAV_FP8_BWD_MASK / TAV_ATTN_PRESCALE /
-TAV_FP8_DELAYED ...) against the fp32 oracle: logits / loss / grad-norm errors.  usage: python tools/gpu_fp8_one.py [policy] [label] [seed]"""
+"""Config 5 at full depth (24 video layers), batch 2, ONE policy setting -- a policy name and, for an fp8 policy, optionally its e4m3 masks
+(engine.Policy fp8_fwd / fp8_bwd; omitted: the policy's defaults) -- against the fp32 oracle: logits / loss / grad-norm errors.
+usage: python tools/gpu_fp8_one.py [policy] [label] [seed] [fwd-mask] [bwd-mask]"""
 import os
 import sys
 
@@ -10,17 +11,19 @@ import torch  # noqa: E402
 torch.set_num_threads(16)
 import test_model_gpu as T  # noqa: E402
 from tav_amd import config as C  # noqa: E402
-from tav_amd import runtime  # noqa: E402
+from tav_amd import engine, runtime  # noqa: E402
 from tav_amd.models.tav import PreFormer, TAVForMAE  # noqa: E402
 from tav_amd.optim import grad_norm  # noqa: E402
 
 pol = sys.argv[1] if len(sys.argv) > 1 else "fp8"
 label = sys.argv[2] if len(sys.argv) > 2 else ""
 seed = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+fm = int(sys.argv[4]) if len(sys.argv) > 4 else None
+bm = int(sys.argv[5]) if len(sys.argv) > 5 else None
 cfg = C.preset("B5")
 cfg, batch, lab, (sdp, sdm), o_logits, o_loss, o_gn, o_grads = T._oracle_full("B5", seed=seed, batch_size=2, cfg=cfg, tag="B5-full")
 label = f"{label} seed {seed}"
-runtime.set_precision(pol)
+runtime.set_precision(engine.Policy(pol, fp8_fwd=fm, fp8_bwd=bm))
 pre, model = PreFormer(cfg), TAVForMAE(T.ARGS, cfg)
 pre.load_state_dict(sdp)
 model.load_state_dict(sdm)
