@@ -13,13 +13,13 @@
 // 2- to 4-deep ring with the next tile's DMA pieces issued between the MFMA groups, one barrier per K-tile (the 256 x 256 tiles of both kernels:
 // five 32 KB images = 160 KB, three for the activation-side operand, which is issued two K-tiles ahead, two for the other).  The host picks the tile -- or a mix of
 // both over disjoint row ranges -- per call from a fitted cost model (nt_pick_tile, tav_gemm_nt_schedule) and the epilogue flavour (EPI) from the
-// arguments.  TN tiles: 128 x 128 (4 waves) or 256 x 256 (8 waves, token axis split into f32 slabs), 64-token K-tiles, transposed fragment reads.
+// arguments: every such host decision is a pure function of gemm_plan.h, this file keeps the kernels and the enqueue.  TN tiles: 128 x 128 (4 waves) or 256 x 256 (8 waves, token axis split into f32 slabs), 64-token K-tiles, transposed fragment reads.
 // LDS image of the NT kernel: [row][8 chunks of 16 B], chunk index XOR-swizzled with (row>>1)&7 so that the
 // ds_read_b128 fragment reads (16 rows x one chunk per 16-lane group) are bank-conflict free.
-#include <stdlib.h>
 #include "common.h"
 #include <type_traits>
 #include "tavhip_internal.h"
+#include "gemm_plan.h"
 
 namespace tav {
 
@@ -947,253 +947,100 @@ __global__ void colsum_final_kernel(const float* __restrict__ part, float* __res
 
 using namespace tav;
 
-// tile height: minimise (tiles per CU, rounded up) x (cost of one tile ~ TM + fixed overhead)
-static int nt_small_tile(int M, int N, int nz) {
-    const int tiles_n = (N + 127) / 128;
-    int tm = 4;
-    double best = 1e30;
-    for (int c = 4; c >= 2; --c) {
-        const long tiles = (long)((M + 32 * c - 1) / (32 * c)) * tiles_n * nz;
-        const double cost = (double)((tiles + 255) / 256) * (c + 0.8);
-        if (cost < best - 1e-9) { best = cost; tm = c; }
-    }
-    return tm;
-}
-// Fitted launch times in microseconds: rounds x (K-tiles x time per K-tile + prologue and epilogue), constants from tools/gpu_ab.py `layer`
-// at batch 32 and 8 with per-tile hints (profiles/r02_microbench_*; they reproduce its timings within ~5 %).  K-tiles beyond the 36th cost
-// 1.3-1.6x (K = 3072 operands; not a channel-aliasing effect -- padding the row stride changes nothing).
-// `epi`: bit 0 f32 residual / accumulate read, bit 1 f32 output, bit 2 GELU, bit 3 gelu' side input, bit 4 second output.
-static double nt_small_us(int M, int N, double nk, int nz, int tm, int epi) {
-    static const double slots[5] = {0, 0, 768, 512, 512}, tk[5] = {0, 0, 0.56, 0.72, 0.85}, fix[5] = {0, 0, 3.6, 4.0, 4.4};
-    const long t = (long)((M + 32 * tm - 1) / (32 * tm)) * ((N + 127) / 128) * nz;
-    // two workgroups per CU hide one's epilogue behind the other's main loop: the residual read costs little after a short K loop
-    const double e = ((epi & 1) ? 2.0 + 0.2 * nk : 0.0) + ((epi & 2) ? 2.0 : 0.0) + ((epi & 4) ? 2.0 : 0.0) + ((epi & 8) ? 1.0 : 0.0) + ((epi & 16) ? 2.5 : 0.0);
-    const double kt = (nk <= 36.0 ? nk : 36.0 + 1.6 * (nk - 36.0)) * tk[tm];
-    return (double)((long)((t + slots[tm] - 1) / slots[tm])) * (kt + fix[tm] + e * tm / 4.0);
-}
-static double nt_big_round_us(double nk, int epi) {
-    // (3 + 2 ring: 1.37-1.52 us per K-tile at every K measured)
-    const double kt = nk * 1.45;
-    return kt + 6.5 + ((epi & 1) ? 9.0 : 0.0) + ((epi & 2) ? 4.0 : 0.0) + ((epi & 4) ? 3.0 : 0.0) + ((epi & 8) ? 4.7 : 0.0) + ((epi & 16) ? 6.7 : 0.0);
-}
-// Returns the tile for the launch; when `rows_big` is given and a mixed schedule is faster, *rows_big < M is the number of leading rows that
-// take the 256 x 256 tile (whole rounds of 256 workgroups) and *tm_rest the 128-wide tile of a second launch over the remaining rows.
-static int nt_pick_tile(int M, int N, int K, int nz, bool bf16_in, int epi, int* rows_big = nullptr, int* tm_rest = nullptr) {
-    int tm = nt_small_tile(M, N, nz);
-    if (rows_big) *rows_big = M;
-    // 256x256 (8 waves, one workgroup per CU) against the 128-wide winner.  The big tile stages half the bytes per FLOP (1.35 PFLOP/s at
-    // 4096^3 against 1.15) but nothing on its CU computes while it runs its epilogue, whereas two 128-wide workgroups per CU overlap one's
-    // epilogue with the other's main loop: memory-heavy epilogues (f32 residual in, f32 out) favour the small tile, plain bf16 outputs the
-    // big one.  A last, partly filled round of big tiles costs a whole round: when the grid is a few rounds long (N = 768 at batch 32:
-    // 2.14 rounds) the rows of that last round go to a second launch with the small tile instead.
-    if (bf16_in && M >= 256 && N >= 256) {
-        const double nk = (double)K / 64.0;
-        const long tn_big = (N + 255) / 256;
-        const long t_big = (long)((M + 255) / 256) * tn_big * nz;
-        const double us_small = nt_small_us(M, N, nk, nz, tm, epi);
-        const double big_round = nt_big_round_us(nk, epi);
-        const double us_big = (double)((t_big + 255) / 256) * big_round;
-        double us_best = us_small;
-        if (us_big < 0.98 * us_small) { tm = 16; us_best = us_big; }
-        const long full = t_big / 256;
-        if (rows_big && nz == 1 && full >= 1 && t_big % 256 != 0) {
-            const long m_tiles = full * 256 / tn_big;
-            const int rows_a = (int)(m_tiles * 256), m_rest = M - rows_a;
-            if (m_tiles >= 1 && m_rest > 0) {
-                const int tr = nt_small_tile(m_rest, N, 1);
-                const double us_split = (double)((m_tiles * tn_big + 255) / 256) * big_round + nt_small_us(m_rest, N, nk, 1, tr, epi) + 2.0;   // + the seam between two launches
-                if (us_split < 0.93 * us_best) { tm = 16; *rows_big = rows_a; *tm_rest = tr; }   // (the model is good to ~5 %: only clear wins)
-            }
-        }
-    }
-    return tm;
-}
+// ================================================================================================ host: enqueue only
+// Every decision -- argument checks, tile plan, kernel and launch geometry, workspace layout -- is a pure function of gemm_plan.h.
+static_assert(NT_GEN == plan::EPI_GEN && NT_PLAIN == plan::EPI_PLAIN && NT_RESID == plan::EPI_RESID && NT_GELU_D == plan::EPI_GELU_D &&
+              NT_MUL_D == plan::EPI_MUL_D && TN_GROUP_MAX == plan::TN_PROBLEMS_MAX, "gemm_plan.h mirrors these");
 
-static int nt_validate(const tav_gemm_nt_args* a, bool need_ptrs) {
-    if (!a || (need_ptrs && (!a->A || !a->B || !a->C))) return TAV_ERR_NULL;
-    if (a->M <= 0 || a->N <= 0 || a->K <= 0) return TAV_ERR_SHAPE;
-    const int es = a->in_dtype == TAV_FP8 ? 1 : (a->in_dtype == TAV_BF16 ? 2 : 4);
-    if (a->in_dtype != TAV_BF16 && a->in_dtype != TAV_F32 && a->in_dtype != TAV_FP8) return TAV_ERR_DTYPE;
-    if (a->in_dtype == TAV_F32 && a->out_dtype != TAV_F32) return TAV_ERR_DTYPE;
-    if (a->out_dtype != TAV_F32 && a->out_dtype != TAV_BF16) return TAV_ERR_DTYPE;
-    if ((a->K * es) % 128 != 0) return TAV_ERR_SHAPE;      // K-tile = 128 bytes
-    if ((a->M * a->lda + a->K) * es >= (1ll << 32) || (a->N * a->ldb + a->K) * es >= (1ll << 32)) return TAV_ERR_SHAPE;   // 32-bit staging offsets per (zb, zg) slice
-    if (a->N % 4 != 0) return TAV_ERR_SHAPE;
-    {   // the epilogue addresses a tile's rows with 32-bit element offsets from the tile's first row
-        const int64_t ldmax = std::max(std::max(a->ldc, a->C_pre ? a->ld_pre : 0), std::max(a->gelu_in ? a->ld_gelu_in : 0, a->resid ? a->ld_resid : 0));
-        if (ldmax < 0 || 256 * ldmax + a->N >= (1ll << 30)) return TAV_ERR_SHAPE;
-    }
-    const int pk = 16 / es;
-    if (a->lda % pk || a->ldb % pk || a->ldc % 4) return TAV_ERR_ALIGN;
-    if (a->a_zb % pk || a->a_zg % pk || a->b_zb % pk || a->b_zg % pk || a->c_zb % 4 || a->c_zg % 4 || a->gelu_zb % 4) return TAV_ERR_ALIGN;
-    return 0;
-}
-// The tile plan of one call: `tm` for the first `rows_big` rows (all of them unless a mixed schedule wins), `tm_rest` for the others.
-static void nt_plan(const tav_gemm_nt_args* a, int* tm_out, int* rows_big, int* tm_rest) {
-    const int es = a->in_dtype == TAV_FP8 ? 1 : (a->in_dtype == TAV_BF16 ? 2 : 4);
-    const int nz = (int)((a->nzb > 0 ? a->nzb : 1) * (a->nzg > 0 ? a->nzg : 1));
-    int tm = a->tile_m_hint & 31;                            // 2/3/4: 64/96/128 x 128 tiles (4 waves); 8: 256 x 128, 16: 256 x 256 (8 waves); 17: as 0 but one launch
-    const bool may_split = tm == 0 && a->in_dtype == TAV_BF16 && nz == 1;
-    *rows_big = (int)a->M; *tm_rest = 4;
-    if (a->in_dtype == TAV_F32 && (tm == 8 || tm == 16)) tm = 4;
-    if (tm != 8 && tm != 16 && (tm < 2 || tm > 4))
-        tm = nt_pick_tile((int)a->M, (int)a->N, (int)(a->K * es / 2), nz, a->in_dtype != TAV_F32,
-                          ((a->resid || a->accumulate) ? 1 : 0) | (a->out_dtype == TAV_F32 ? 2 : 0) | ((a->act & 3) ? 4 : 0) | (a->gelu_in ? 8 : 0) | (a->C_pre ? 16 : 0),
-                          may_split ? rows_big : nullptr, tm_rest);
-    if (a->in_dtype == TAV_FP8 && tm != 16) tm = 4;          // fp8 operands: the 128 x 128 and 256 x 256 tiles only
-    *tm_out = tm;
-}
+// the kernels of plan::nt_keys, in its order
+template <int DTYPE> struct NtElem;
+template <> struct NtElem<TAV_F32> { using type = float; };
+template <> struct NtElem<TAV_BF16> { using type = bf16; };
+template <> struct NtElem<TAV_FP8> { using type = fp8; };
+using NtKernel = void (*)(const GemmNT);
+#define TAV_NT_KERNEL(IN, OUT, TM, NST, NW, TNW, EPI) gemm_nt_kernel<NtElem<TAV_##IN>::type, NtElem<TAV_##OUT>::type, TM, NST, NW, TNW, NT_##EPI>,
+static const NtKernel nt_kernels[] = {TAV_NT_KERNELS(TAV_NT_KERNEL)};
+#undef TAV_NT_KERNEL
+static_assert(sizeof(nt_kernels) / sizeof(nt_kernels[0]) == plan::nt_num_keys, "one kernel per key");
 
 extern "C" int tav_gemm_nt_schedule(const tav_gemm_nt_args* a, int32_t* tile, int32_t* rows_first, int32_t* tile_rest) {
     if (!tile || !rows_first || !tile_rest) return TAV_ERR_NULL;
-    const int rc = nt_validate(a, false);
+    const int rc = plan::nt_validate(a, false);
     if (rc != 0) return rc;
     int tm, rb, tr;
-    nt_plan(a, &tm, &rb, &tr);
+    plan::nt_plan(a, &tm, &rb, &tr);
     *tile = tm; *rows_first = rb; *tile_rest = rb < a->M ? tr : 0;
+    return 0;
+}
+
+static int nt_enqueue(const tav_gemm_nt_args* a, GemmNT p, int tm, hipStream_t stream) {
+    const plan::NtLaunch L = plan::nt_launch(a, p.M, tm);
+    const int k = plan::nt_key_index(L.key);
+    if (k < 0) return TAV_ERR_DTYPE;                         // no such kernel (nt_launch returns only keys of the list: unreachable)
+    p.tiles_m = L.tiles_m; p.tiles_n = L.tiles_n;
+    hipLaunchKernelGGL(nt_kernels[k], dim3(L.grid_x, L.grid_y), dim3(L.block), L.lds, stream, p);
     return 0;
 }
 
 extern "C" int tav_gemm_nt(const tav_gemm_nt_args* a, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    { const int rc = nt_validate(a, true); if (rc != 0) return rc; }
-    const int es = a->in_dtype == TAV_FP8 ? 1 : (a->in_dtype == TAV_BF16 ? 2 : 4);
+    { const int rc = plan::nt_validate(a, true); if (rc != 0) return rc; }
     GemmNT p;
     p.A = (const char*)a->A; p.B = (const char*)a->B; p.C = (char*)a->C; p.Cpre = (char*)a->C_pre; p.bias = a->bias;
     p.gelu_in = (const char*)a->gelu_in; p.resid = a->resid;
     p.M = (int)a->M; p.N = (int)a->N; p.K = (int)a->K;
     p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ld_pre = a->ld_pre; p.ld_gelu = a->ld_gelu_in; p.ld_resid = a->ld_resid;
     p.nzg = a->nzg > 0 ? a->nzg : 1;
-    const int nzb = a->nzb > 0 ? a->nzb : 1;
     p.a_zb = a->a_zb; p.a_zg = a->a_zg; p.b_zb = a->b_zb; p.b_zg = a->b_zg; p.c_zb = a->c_zb; p.c_zg = a->c_zg; p.bias_zg = a->bias_zg;
     p.g_zb = a->gelu_zb ? a->gelu_zb : a->c_zb;
     p.act = a->act; p.accumulate = a->accumulate; p.alpha = a->alpha;
     p.sa = a->in_dtype == TAV_FP8 ? a->a_dequant : nullptr; p.sb = a->in_dtype == TAV_FP8 ? a->b_dequant : nullptr;
-    const int in_dtype = a->in_dtype, out_dtype = a->out_dtype;
-    const int hint_nst = (a->tile_m_hint >> 5) & 7;         // tuning: LDS ring depth 2..4 (0 = let the library choose)
-    auto launch = [&](GemmNT p, int tm) {
-        int nst = hint_nst;
-        const int bm = tm >= 8 ? 256 : 32 * tm, bn = tm == 16 ? 256 : 128;
-        p.tiles_m = (p.M + bm - 1) / bm;
-        p.tiles_n = (p.N + bn - 1) / bn;
-        const long wgs = (long)p.tiles_m * p.tiles_n * nzb * p.nzg;
-        // Ring depth.  Large grids run two workgroups per CU and are bound by the L2->LDS intake, where depth changes nothing: 2.
-        // A grid of at most one workgroup per CU (the text / audio / fusion branches' N = 768 GEMMs) is LATENCY bound instead -- a lone
-        // workgroup waits out every DMA round trip -- and has the whole LDS to itself: 4 buffers (3 tiles in flight).
-        if (tm == 8) nst = 3;
-        else if (tm == 16) nst = 2;
-        else if (nst < 2 || nst > 4) nst = (wgs <= 256 && in_dtype == TAV_BF16) ? 4 : 2;
-        if (in_dtype != TAV_BF16) nst = 2;
-        dim3 grid(p.tiles_m * p.tiles_n, nzb * p.nzg), block(tm >= 8 ? 512 : 256);
-        // 256x128: 3 x 48 KB (its f32 epilogue tile needs 128 KB); 256x256: 2 x 64 KB, or 3 A + 2 B images = 160 KB (bf16, R25)
-        const size_t lds = (tm == 16 && in_dtype == TAV_BF16) ? (size_t)160 * 1024 : (size_t)nst * (bm + bn) * 128;
-#define TAV_NT_LAUNCH_S(TT, TOO, NS, EP)                                                                                 \
-    do {                                                                                                                 \
-        if (tm == 4) hipLaunchKernelGGL((gemm_nt_kernel<TT, TOO, 4, NS, 4, 4, EP>), grid, block, lds, stream, p);         \
-        else if (tm == 3) hipLaunchKernelGGL((gemm_nt_kernel<TT, TOO, 3, NS, 4, 4, EP>), grid, block, lds, stream, p);    \
-        else hipLaunchKernelGGL((gemm_nt_kernel<TT, TOO, 2, NS, 4, 4, EP>), grid, block, lds, stream, p);                 \
-    } while (0)
-#define TAV_NT_LAUNCH(TT, TOO, EP)                                                                                       \
-    do {                                                                                                                 \
-        if (tm == 16) hipLaunchKernelGGL((gemm_nt_kernel<TT, TOO, 4, 2, 8, 8, EP>), grid, block, lds, stream, p);         \
-        else if (tm == 8) hipLaunchKernelGGL((gemm_nt_kernel<TT, TOO, 4, 3, 8, 4, NT_GEN>), grid, block, lds, stream, p); \
-        else if (nst == 4) TAV_NT_LAUNCH_S(TT, TOO, 4, EP);                                                               \
-        else if (nst == 3) TAV_NT_LAUNCH_S(TT, TOO, 3, NT_GEN);                                                           \
-        else TAV_NT_LAUNCH_S(TT, TOO, 2, EP);                                                                             \
-    } while (0)
-        // the epilogue flavours of the transformer layers as straight-line code; everything else takes the generic epilogue
-        const bool side = p.resid || p.Cpre || p.gelu_in || p.accumulate;
-        int epi = NT_GEN;
-        if (!side && p.act == 0) epi = NT_PLAIN;
-        else if (p.resid && !p.Cpre && !p.gelu_in && !p.accumulate && p.act == 0 && out_dtype == TAV_F32) epi = NT_RESID;
-        else if (p.Cpre && (p.act & 3) == 3 && !p.resid && !p.gelu_in && !p.accumulate && out_dtype == TAV_BF16) epi = NT_GELU_D;
-        else if (p.gelu_in && (p.act & 4) && !(p.act & 3) && !p.resid && !p.Cpre && !p.accumulate && out_dtype == TAV_BF16) epi = NT_MUL_D;
-        if (in_dtype == TAV_FP8) {
-            if (tm == 16) {                                  // (the flavours only for the tile the video stack runs on)
-                if (out_dtype == TAV_BF16) {
-                    if (epi == NT_PLAIN) hipLaunchKernelGGL((gemm_nt_kernel<fp8, bf16, 4, 2, 8, 8, NT_PLAIN>), grid, block, lds, stream, p);
-                    else if (epi == NT_GELU_D) hipLaunchKernelGGL((gemm_nt_kernel<fp8, bf16, 4, 2, 8, 8, NT_GELU_D>), grid, block, lds, stream, p);
-                    else if (epi == NT_MUL_D) hipLaunchKernelGGL((gemm_nt_kernel<fp8, bf16, 4, 2, 8, 8, NT_MUL_D>), grid, block, lds, stream, p);
-                    else hipLaunchKernelGGL((gemm_nt_kernel<fp8, bf16, 4, 2, 8, 8>), grid, block, lds, stream, p);
-                } else {
-                    if (epi == NT_PLAIN) hipLaunchKernelGGL((gemm_nt_kernel<fp8, float, 4, 2, 8, 8, NT_PLAIN>), grid, block, lds, stream, p);
-                    else if (epi == NT_RESID) hipLaunchKernelGGL((gemm_nt_kernel<fp8, float, 4, 2, 8, 8, NT_RESID>), grid, block, lds, stream, p);
-                    else hipLaunchKernelGGL((gemm_nt_kernel<fp8, float, 4, 2, 8, 8>), grid, block, lds, stream, p);
-                }
-            } else {
-                if (out_dtype == TAV_BF16) hipLaunchKernelGGL((gemm_nt_kernel<fp8, bf16, 4, 2, 4, 4>), grid, block, lds, stream, p);
-                else hipLaunchKernelGGL((gemm_nt_kernel<fp8, float, 4, 2, 4, 4>), grid, block, lds, stream, p);
-            }
-        } else if (in_dtype == TAV_BF16) {
-            if (out_dtype == TAV_BF16) {
-                if (epi == NT_PLAIN) TAV_NT_LAUNCH(bf16, bf16, NT_PLAIN);
-                else if (epi == NT_GELU_D) TAV_NT_LAUNCH(bf16, bf16, NT_GELU_D);
-                else if (epi == NT_MUL_D) TAV_NT_LAUNCH(bf16, bf16, NT_MUL_D);
-                else TAV_NT_LAUNCH(bf16, bf16, NT_GEN);
-            } else {
-                if (epi == NT_PLAIN) TAV_NT_LAUNCH(bf16, float, NT_PLAIN);
-                else if (epi == NT_RESID) TAV_NT_LAUNCH(bf16, float, NT_RESID);
-                else TAV_NT_LAUNCH(bf16, float, NT_GEN);
-            }
-        } else {
-            if (tm == 4) hipLaunchKernelGGL((gemm_nt_kernel<float, float, 4, 2, 4, 4>), grid, block, lds, stream, p);
-            else if (tm == 3) hipLaunchKernelGGL((gemm_nt_kernel<float, float, 3, 2, 4, 4>), grid, block, lds, stream, p);
-            else hipLaunchKernelGGL((gemm_nt_kernel<float, float, 2, 2, 4, 4>), grid, block, lds, stream, p);
-        }
-    };
     int tm, rows_big, tm_rest;
-    nt_plan(a, &tm, &rows_big, &tm_rest);
+    plan::nt_plan(a, &tm, &rows_big, &tm_rest);
     if (rows_big < p.M) {
         // mixed schedule: whole rounds of 256 x 256 tiles over the leading rows, then the 128-wide tile over the rest (same stream, disjoint rows)
+        const plan::NtSplit s = plan::nt_split(a, rows_big);
         GemmNT q = p;
-        const long r = rows_big, oes = out_dtype == TAV_F32 ? 4 : 2;
-        q.M = p.M - rows_big;
-        q.A = p.A + r * p.lda * es; q.C = p.C + r * p.ldc * oes;
-        if (p.Cpre) q.Cpre = p.Cpre + r * p.ld_pre * oes;
-        if (p.gelu_in) q.gelu_in = p.gelu_in + r * p.ld_gelu * es;
-        if (p.resid) q.resid = p.resid + r * p.ld_resid;
+        q.M = s.M_rest;
+        q.A = p.A + s.a_bytes; q.C = p.C + s.c_bytes;
+        if (p.Cpre) q.Cpre = p.Cpre + s.pre_bytes;
+        if (p.gelu_in) q.gelu_in = p.gelu_in + s.gelu_bytes;
+        if (p.resid) q.resid = p.resid + s.resid_elems;
         p.M = rows_big;
-        launch(p, 16);
-        launch(q, tm_rest);
+        int rc = nt_enqueue(a, p, 16, stream);
+        if (rc == 0) rc = nt_enqueue(a, q, tm_rest, stream);
+        if (rc != 0) return rc;
     } else {
-        launch(p, tm);
+        const int rc = nt_enqueue(a, p, tm, stream);
+        if (rc != 0) return rc;
     }
-#undef TAV_NT_LAUNCH
-#undef TAV_NT_LAUNCH_S
     return (int)hipGetLastError();
 }
 
-static double split_penalty() { return 0.06; }   // per extra token split (slab traffic), tuned with the four branch streams running concurrently
-
 extern "C" int tav_gemm_tn_splits(int64_t n1, int64_t n2, int64_t rows_per_batch, int64_t nbatch, int32_t* chunk_rows, int32_t* nsplit) {
     if (!chunk_rows || !nsplit || n1 <= 0 || n2 <= 0 || rows_per_batch <= 0 || nbatch <= 0) return TAV_ERR_SHAPE;
-    const long tiles = ((n1 + 127) / 128) * ((n2 + 127) / 128);
-    // The kernel is resident at 2 workgroups per CU = 512 slots.  Pick the number of token chunks per batch entry so that
-    // tiles * splits fills whole rounds of 512 (a 576-workgroup launch costs two rounds), chunks stay >= 256 tokens, and among
-    // equally efficient choices the one with fewer splits (less slab traffic) wins.
-    const long SLOTS = 512;
-    long best_cpb = 1; double best_score = -1.0;
-    const long max_cpb = (rows_per_batch + 255) / 256 > 0 ? (rows_per_batch + 255) / 256 : 1;
-    for (long cpb = 1; cpb <= max_cpb && cpb <= 64; ++cpb) {
-        long cr = (rows_per_batch + cpb - 1) / cpb;
-        cr = ((cr + 63) / 64) * 64;
-        const long real_cpb = (rows_per_batch + cr - 1) / cr;
-        const long wgs = tiles * real_cpb * nbatch;
-        const long rounds = (wgs + SLOTS - 1) / SLOTS;
-        double eff = (double)wgs / (double)(rounds * SLOTS);
-        // per-round cost grows with the chunk length; total ~ rounds * cr; smaller is better.  Normalise by the ideal.
-        const double work = (double)rounds * (double)cr;
-        const double ideal = (double)tiles * nbatch * rows_per_batch / SLOTS;
-        double score = ideal / work - split_penalty() * (double)(real_cpb * nbatch);      // penalty per split (slab bytes)
-        (void)eff;
-        if (score > best_score + 1e-9) { best_score = score; best_cpb = real_cpb; }
-    }
-    long cr = (rows_per_batch + best_cpb - 1) / best_cpb;
-    cr = ((cr + 63) / 64) * 64;
-    const long cpb = (rows_per_batch + cr - 1) / cr;
-    *chunk_rows = (int32_t)cr;
-    *nsplit = (int32_t)(cpb * nbatch);
+    plan::tn_splits(n1, n2, rows_per_batch, nbatch, chunk_rows, nsplit);
     return 0;
+}
+
+// Kernel arguments of a grouped launch from its layout; `ws` is the workspace the layout's offsets refer to.  use_ws as in tn_group_layout:
+// without it the tiles write out and dbias themselves (bias_spread = 0) and `red` is filled but not needed.
+static void tn_group_fill(const tav_gemm_tn_problem* probs, int nprob, long rows, const plan::TnGroupPlan& P, const plan::TnGroupLayout& L,
+                          bool use_ws, float* ws, GemmTNGroup* grp, TNGroupReduce* red) {
+    for (int k = 0; k < TN_GROUP_MAX; ++k) {
+        const tav_gemm_tn_problem& a = probs[k < nprob ? k : nprob - 1];
+        float* const bias_ws = L.bias_off[k] >= 0 ? ws + L.bias_off[k] : nullptr;
+        GemmTN& p = grp->p[k];
+        p.A = (const char*)a.A; p.B = (const char*)a.B; p.N1 = (int)a.N1; p.N2 = (int)a.N2; p.lda = a.lda; p.ldb = a.ldb;
+        p.rows_per_batch = (int)rows; p.a_zb = 0; p.b_zb = 0; p.chunk_rows = (int)P.chunk; p.chunks_per_batch = P.nsplit;
+        p.tiles_1 = L.tiles_1[k]; p.tiles_2 = L.tiles_2[k];
+        p.S = L.slab_off[k] >= 0 ? ws + L.slab_off[k] : a.out;
+        p.bias_part = use_ws ? bias_ws : a.dbias; p.bias_spread = use_ws ? 1 : 0;
+        grp->tile_end[k] = L.tile_end[k];
+        red->slabs[k] = p.S; red->out[k] = a.out; red->dbias[k] = a.dbias; red->N1[k] = (int)a.N1; red->n4[k] = L.n4[k];
+        red->nbias[k] = L.nbias[k]; red->bias_part[k] = bias_ws; red->end4[k] = L.end4[k];
+    }
+    grp->n = nprob; red->n = nprob; red->nsplit = P.nsplit;
 }
 
 extern "C" int tav_gemm_tn_grouped(const tav_gemm_tn_problem* probs, int32_t nprob, int64_t rows, int32_t dtype, void* stream_) {
@@ -1201,72 +1048,21 @@ extern "C" int tav_gemm_tn_grouped(const tav_gemm_tn_problem* probs, int32_t npr
     if (!probs) return TAV_ERR_NULL;
     if (nprob <= 0 || nprob > TN_GROUP_MAX || rows <= 0) return TAV_ERR_SHAPE;
     if (dtype != TAV_BF16 && dtype != TAV_F32) return TAV_ERR_DTYPE;
-    const int es = dtype == TAV_BF16 ? 2 : 4, pk = 16 / es;
+    { const int rc = plan::tn_validate_group(probs, nprob, rows, dtype); if (rc != 0) return rc; }
+    const plan::TnGroupPlan P = plan::tn_plain_plan(rows);
+    const plan::TnGroupLayout L = plan::tn_group_layout(probs, nprob, P, false);
     GemmTNGroup grp;
-    int total = 0;
-    for (int k = 0; k < TN_GROUP_MAX; ++k) {
-        const tav_gemm_tn_problem& a = probs[k < nprob ? k : nprob - 1];
-        if (k < nprob) {
-            if (!a.A || !a.B || !a.out) return TAV_ERR_NULL;
-            if (a.N1 <= 0 || a.N2 <= 0) return TAV_ERR_SHAPE;
-            if (a.N1 % pk || a.N2 % pk || a.N2 % 4) return TAV_ERR_SHAPE;
-            if (a.lda % pk || a.ldb % pk) return TAV_ERR_ALIGN;
-            if ((rows + 64) * (a.lda > a.ldb ? a.lda : a.ldb) * es >= (1ll << 32)) return TAV_ERR_SHAPE;   // 32-bit staging offsets
-        }
-        GemmTN& p = grp.p[k];
-        p.A = (const char*)a.A; p.B = (const char*)a.B; p.S = a.out; p.bias_part = a.dbias; p.bias_spread = 0;
-        p.N1 = (int)a.N1; p.N2 = (int)a.N2; p.lda = a.lda; p.ldb = a.ldb;
-        p.rows_per_batch = (int)rows; p.a_zb = 0; p.b_zb = 0;
-        p.chunk_rows = (int)(((rows + 63) / 64) * 64); p.chunks_per_batch = 1;
-        p.tiles_1 = (p.N1 + 127) / 128; p.tiles_2 = (p.N2 + 127) / 128;
-        if (k < nprob) total += p.tiles_1 * p.tiles_2;
-        grp.tile_end[k] = total;
-    }
-    grp.n = nprob;
-    dim3 grid(total), block(256);
+    TNGroupReduce red;                                                  // (not used: nothing to reduce)
+    tn_group_fill(probs, nprob, rows, P, L, false, nullptr, &grp, &red);
+    dim3 grid(L.total), block(256);
     if (dtype == TAV_BF16) hipLaunchKernelGGL((gemm_tn_grouped_kernel<bf16>), grid, block, 4 * 64 * 256, stream, grp);
     else hipLaunchKernelGGL((gemm_tn_grouped_kernel<float>), grid, block, 4 * 64 * 512, stream, grp);
     return (int)hipGetLastError();
 }
 
-// Plan of a grouped launch: 256-wide tiles + `nsplit` token chunks when the problems are large enough to pay for the slabs, else the
-// 128-wide kernel (every tile sums over all rows, no workspace).  flags: bit 0 forces the 256-wide form, bit 1 the 128-wide one,
-// bits 8..11 an explicit split count (tests / tuning).
-static bool tn_big_plan(const tav_gemm_tn_problem* probs, int nprob, long rows, int dtype, int flags, int* nsplit, long* ws_floats) {
-    *nsplit = 1; *ws_floats = 0;
-    const bool can_big = dtype == TAV_BF16 && !(flags & 2);
-    long tiles = 0, elems = 0;
-    for (int k = 0; k < nprob; ++k) {
-        tiles += ((probs[k].N1 + 255) / 256) * ((probs[k].N2 + 255) / 256);
-        elems += probs[k].N1 * probs[k].N2;
-    }
-    bool big = can_big && ((flags & 1) || (rows >= 12288 && tiles >= 48));  // below: the 128-wide tiles (slab traffic, 84 % fill) are as fast or faster
-    if (big) {
-        int best = 1; double best_score = -1.0;
-        for (int s2 = 1; s2 <= 4; ++s2) {
-            if (s2 > 1 && rows / s2 < 2048) break;
-            const long wgs = tiles * s2;
-            const double fill = (double)wgs / (double)(((wgs + 255) / 256) * 256);
-            const double score = fill - 0.04 * (s2 - 1);             // each extra split writes and re-reads one more f32 copy of the gradients
-            if (score > best_score + 1e-9) { best_score = score; best = s2; }
-        }
-        if ((flags >> 8) & 15) best = (flags >> 8) & 15;
-        *nsplit = best;
-    }
-    // workspace: the slabs of a split launch, then the bias partials [nsplit][tiles_2][N1] of every problem that wants a bias gradient
-    const int tw = big ? 256 : 128;
-    long wsf = *nsplit > 1 ? (long)*nsplit * elems : 0;
-    for (int k = 0; k < nprob; ++k)
-        if (probs[k].dbias) wsf += (long)*nsplit * ((probs[k].N2 + tw - 1) / tw) * probs[k].N1;
-    *ws_floats = wsf;
-    return big;
-}
-
 extern "C" int64_t tav_gemm_tn_grouped_ws_bytes(const tav_gemm_tn_problem* probs, int32_t nprob, int64_t rows, int32_t dtype, int32_t flags) {
     if (!probs || nprob <= 0 || nprob > TN_GROUP_MAX || rows <= 0) return 0;
-    int ns; long wsf;
-    tn_big_plan(probs, nprob, rows, dtype, flags, &ns, &wsf);
-    return wsf * 4;
+    return plan::tn_big_plan(probs, nprob, rows, dtype, flags).ws_floats * 4;
 }
 
 extern "C" int tav_gemm_tn_grouped_ws(const tav_gemm_tn_problem* probs, int32_t nprob, int64_t rows, int32_t dtype, void* workspace,
@@ -1275,64 +1071,30 @@ extern "C" int tav_gemm_tn_grouped_ws(const tav_gemm_tn_problem* probs, int32_t 
     if (!probs) return TAV_ERR_NULL;
     if (nprob <= 0 || nprob > TN_GROUP_MAX || rows <= 0) return TAV_ERR_SHAPE;
     if (dtype != TAV_BF16 && dtype != TAV_F32) return TAV_ERR_DTYPE;
-    int nsplit; long wsf;
-    const bool big = tn_big_plan(probs, nprob, rows, dtype, flags, &nsplit, &wsf);
-    if (wsf > 0 && (!workspace || workspace_bytes < wsf * 4)) return tav_gemm_tn_grouped(probs, nprob, rows, dtype, stream_);   // no room: the workspace-free form
-    const int es = dtype == TAV_BF16 ? 2 : 4, pk = 16 / es, tw = big ? 256 : 128;
+    const plan::TnGroupPlan P = plan::tn_big_plan(probs, nprob, rows, dtype, flags);
+    if (P.ws_floats > 0 && (!workspace || workspace_bytes < P.ws_floats * 4)) return tav_gemm_tn_grouped(probs, nprob, rows, dtype, stream_);   // no room: the workspace-free form
+    // Preserved, not designed: the empty split is refused BEFORE the problems are looked at (a NULL operand in the same call reports
+    // TAV_ERR_SHAPE), and a call that took the fallback above is never asked.
+    if (plan::tn_has_empty_split(P, rows)) return TAV_ERR_SHAPE;
+    { const int rc = plan::tn_validate_group(probs, nprob, rows, dtype); if (rc != 0) return rc; }
+    const plan::TnGroupLayout L = plan::tn_group_layout(probs, nprob, P, true);
     GemmTNGroup grp;
     TNGroupReduce red;
-    int total = 0, total_n1 = 0;
-    bool any_bias = false;
-    const long chunk = ((rows + nsplit - 1) / nsplit + 63) / 64 * 64;
-    if ((long)(nsplit - 1) * chunk >= rows) return TAV_ERR_SHAPE;      // (an empty split would leave its slab unwritten)
-    float* ws = (float*)workspace;
-    long ws_off = 0, end4 = 0;
-    for (int k = 0; k < TN_GROUP_MAX; ++k) {
-        const tav_gemm_tn_problem& a = probs[k < nprob ? k : nprob - 1];
-        if (k < nprob) {
-            if (!a.A || !a.B || !a.out) return TAV_ERR_NULL;
-            if (a.N1 <= 0 || a.N2 <= 0 || a.N1 % pk || a.N2 % pk || a.N2 % 4) return TAV_ERR_SHAPE;
-            if (a.lda % pk || a.ldb % pk) return TAV_ERR_ALIGN;
-            if ((rows + 64) * (a.lda > a.ldb ? a.lda : a.ldb) * es >= (1ll << 32)) return TAV_ERR_SHAPE;   // 32-bit staging offsets
-        }
-        GemmTN& p = grp.p[k];
-        p.A = (const char*)a.A; p.B = (const char*)a.B; p.N1 = (int)a.N1; p.N2 = (int)a.N2; p.lda = a.lda; p.ldb = a.ldb;
-        p.rows_per_batch = (int)rows; p.a_zb = 0; p.b_zb = 0; p.chunk_rows = (int)chunk; p.chunks_per_batch = nsplit;
-        p.tiles_1 = (p.N1 + tw - 1) / tw; p.tiles_2 = (p.N2 + tw - 1) / tw;
-        if (nsplit > 1) { p.S = ws + ws_off; if (k < nprob) ws_off += (long)nsplit * a.N1 * a.N2; }
-        else p.S = a.out;
-        p.bias_part = nullptr; p.bias_spread = 1;
-        if (k < nprob) total += p.tiles_1 * p.tiles_2;
-        grp.tile_end[k] = total;
-        red.slabs[k] = p.S; red.out[k] = a.out; red.dbias[k] = a.dbias; red.N1[k] = (int)a.N1; red.n4[k] = a.N1 * a.N2 / 4;
-        red.nbias[k] = nsplit * p.tiles_2; red.bias_part[k] = nullptr;
-        if (k < nprob) { end4 += red.n4[k]; total_n1 += (int)a.N1; any_bias |= a.dbias != nullptr; }
-        red.end4[k] = end4;
-    }
-    for (int k = 0; k < nprob; ++k) {                                   // bias partials behind all slabs
-        if (!probs[k].dbias) continue;
-        grp.p[k].bias_part = ws + ws_off; red.bias_part[k] = ws + ws_off;
-        ws_off += (long)red.nbias[k] * probs[k].N1;
-    }
-    grp.n = nprob; red.n = nprob; red.nsplit = nsplit;
-    if (big) hipLaunchKernelGGL((gemm_tn_grouped_big_kernel<bf16>), dim3(total, nsplit), dim3(512), 5 * 2 * 64 * 256, stream, grp);
-    else if (dtype == TAV_BF16) hipLaunchKernelGGL((gemm_tn_grouped_kernel<bf16>), dim3(total), dim3(256), 4 * 64 * 256, stream, grp);
-    else hipLaunchKernelGGL((gemm_tn_grouped_kernel<float>), dim3(total), dim3(256), 4 * 64 * 512, stream, grp);
-    if (nsplit > 1) hipLaunchKernelGGL(tn_group_reduce_kernel, dim3((unsigned)((end4 + 255) / 256)), dim3(256), 0, stream, red);
-    else if (any_bias) hipLaunchKernelGGL(tn_group_bias_reduce_kernel, dim3((unsigned)((total_n1 + 255) / 256)), dim3(256), 0, stream, red, total_n1);
+    tn_group_fill(probs, nprob, rows, P, L, true, (float*)workspace, &grp, &red);
+    if (P.big) hipLaunchKernelGGL((gemm_tn_grouped_big_kernel<bf16>), dim3(L.total, P.nsplit), dim3(512), 5 * 2 * 64 * 256, stream, grp);
+    else if (dtype == TAV_BF16) hipLaunchKernelGGL((gemm_tn_grouped_kernel<bf16>), dim3(L.total), dim3(256), 4 * 64 * 256, stream, grp);
+    else hipLaunchKernelGGL((gemm_tn_grouped_kernel<float>), dim3(L.total), dim3(256), 4 * 64 * 512, stream, grp);
+    if (P.nsplit > 1) hipLaunchKernelGGL(tn_group_reduce_kernel, dim3((unsigned)((L.end4[TN_GROUP_MAX - 1] + 255) / 256)), dim3(256), 0, stream, red);
+    else if (L.any_bias) hipLaunchKernelGGL(tn_group_bias_reduce_kernel, dim3((unsigned)((L.total_n1 + 255) / 256)), dim3(256), 0, stream, red, L.total_n1);
     return (int)hipGetLastError();
 }
 
 extern "C" int tav_gemm_tn(const tav_gemm_tn_args* a, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!a || !a->A || !a->B || !a->slabs || !a->out) return TAV_ERR_NULL;
-    if (a->N1 <= 0 || a->N2 <= 0 || a->rows_per_batch <= 0 || a->nbatch <= 0) return TAV_ERR_SHAPE;
-    if (a->dtype != TAV_BF16 && a->dtype != TAV_F32) return TAV_ERR_DTYPE;
-    const int es = a->dtype == TAV_BF16 ? 2 : 4, pk = 16 / es;
-    if (a->N1 % pk || a->N2 % pk || a->N2 % 4) return TAV_ERR_SHAPE;
-    if (a->lda % pk || a->ldb % pk || a->a_zb % pk || a->b_zb % pk) return TAV_ERR_ALIGN;
+    if (!a || !a->slabs) return TAV_ERR_NULL;
+    { const int rc = plan::tn_validate_problem(a->A, a->B, a->out, a->N1, a->N2, a->lda, a->ldb, a->a_zb, a->b_zb, a->rows_per_batch, a->nbatch, a->dtype);
+      if (rc != 0) return rc; }
     if (a->chunk_rows <= 0 || a->chunk_rows % 64) return TAV_ERR_SHAPE;
-    if ((a->rows_per_batch + 64) * (a->lda > a->ldb ? a->lda : a->ldb) * es >= (1ll << 32)) return TAV_ERR_SHAPE;   // 32-bit staging offsets
     GemmTN p;
     p.A = (const char*)a->A; p.B = (const char*)a->B; p.S = a->slabs;
     p.bias_part = a->dbias ? a->bias_partials : nullptr; p.bias_spread = 0;

@@ -2049,6 +2049,35 @@ def check_gemm_tn_grouped_bounded(dtype, rows):
     return rs
 
 
+def check_gemm_tn_grouped_fallback(dtype, rows, flags=0):
+    """tav_gemm_tn_grouped_ws with a workspace that is too small -- NULL with 0 bytes, and the planned size less 4 bytes -- is
+    tav_gemm_tn_grouped: dW and db of four problems of ragged widths, bit for bit against the direct call."""
+    import ctypes as C
+    pairs = [(_rnd(rows, n1, dtype=dtype, seed=70 + k), _rnd(rows, n2, dtype=dtype, seed=80 + k)) for k, (n1, n2) in enumerate(_GROUP_SHAPES)]
+    want = _grouped_run(pairs, None)
+    n = len(pairs)
+    rs = []
+    for form in ("NULL", "4 bytes short"):
+        probs, outs = (ops.L.GemmTNProblem * n)(), []
+        for k, (a, b) in enumerate(pairs):
+            dW, db = _blank((a.shape[1], b.shape[1]), torch.float32), _blank((a.shape[1],), torch.float32)
+            pr = probs[k]
+            pr.A, pr.B, pr.out, pr.dbias = ops.ptr(a), ops.ptr(b), ops.ptr(dW), ops.ptr(db)
+            pr.N1, pr.N2, pr.lda, pr.ldb = a.shape[1], b.shape[1], a.stride(0), b.stride(0)
+            outs.append((dW, db))
+        nbytes = ops.lib().tav_gemm_tn_grouped_ws_bytes(probs, n, rows, ops.dt(pairs[0][0]), flags)
+        assert nbytes > 4, "the plan needs no workspace: nothing to fall back from"
+        ws = _blank((nbytes,), torch.uint8) if form != "NULL" else None
+        ops.check(ops.lib().tav_gemm_tn_grouped_ws(probs, n, rows, ops.dt(pairs[0][0]), ops.ptr(ws), nbytes - 4 if ws is not None else 0, flags,
+                                                   ops.stream()), "gemm_tn_grouped_ws")
+        tag = f"gemm_tn_grouped.fallback[{_GDT[dtype]},rows{rows},flags{flags:#x},workspace {form}]"
+        for k, ((dW, db), (wW, wb)) in enumerate(zip(outs, want)):
+            rs += [_exact(f"{tag}.dW{k}", dW, wW), _exact(f"{tag}.db{k}", db, wb)]
+        if ws is not None:                                              # ... and the workspace it was offered stays untouched
+            rs.append(_all_ff(f"{tag}.workspace untouched", ws))
+    return rs
+
+
 def check_gemm_tn_grouped_int(dtype, rows):
     assert GR.int_exact_ok(rows)
     pairs = [(_int_dev((rows, n1), 9100 + k, dtype), _int_dev((rows, n2), 9200 + k, dtype)) for k, (n1, n2) in enumerate(_GROUP_SHAPES)]
@@ -2079,6 +2108,12 @@ def gemm_fp64_checks():
             out.append(lambda d=dtype, r=rows: check_gemm_tn_grouped_int(d, r))
         out.append(lambda d=dtype: check_gemm_tn_grouped_int(d, 5000))
     out.append(check_gemm_nt_int_mixed_schedule)
+    # a workspace too small for the plan: tav_gemm_tn_grouped_ws answers with tav_gemm_tn_grouped's bits (at 5000 rows the forced 256-wide
+    # form, with bias partials alone and with two slabs per gradient, is what it falls back from)
+    for dtype in (torch.float32, torch.bfloat16):
+        out.append(lambda d=dtype: check_gemm_tn_grouped_fallback(d, 777))
+    for flags in (1, 1 | (2 << 8)):
+        out.append(lambda f=flags: check_gemm_tn_grouped_fallback(torch.bfloat16, 5000, f))
     for M, N, K, tm in ((333, 384, 256, 0), (333, 384, 256, 16), (130, 132, 128, 4), (257, 260, 3072, 16)):
         out.append(lambda a=(M, N, K, tm): check_fp8_int(*a))
     out.append(check_wgrad_fp8_int)
