@@ -488,7 +488,7 @@ TAV_DEV void gemm_tn_body(const GemmTN& p, const int tile, const int split) {
     char* sA = smem;                      // [NST][KT][ROWB]  dY  (n1 along the row)
     char* sB = smem + NST * TILE_BYTES;   // [NST][KT][ROWB]  X   (n2 along the row)
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (scalar: the w2 tests are branches, not masks)
     const int g = lane >> 4, i = lane & 15;
     const int w1 = wave >> 1, w2 = wave & 1;
 
@@ -543,52 +543,60 @@ TAV_DEV void gemm_tn_body(const GemmTN& p, const int tile, const int split) {
         offB[j] = (unsigned)(trow * p.ldb * ES + cb * 16);
     }
     const unsigned strideA = (unsigned)(KT * p.lda * ES), strideB = (unsigned)(KT * p.ldb * ES);
-    // Every stage() issues exactly 2 * NINST vector-memory instructions per wave when the tile is full (the counted waits below rely on
-    // it); the ragged tile -- always the LAST one -- goes through registers and is complete when stage() returns.
+    // A whole K-tile goes by LDS-DMA: exactly 2 * NINST vector-memory instructions per wave (the counted waits below rely on it).  The
+    // ragged tile -- always the LAST one -- goes through registers and is complete when stage_ragged() returns.
     auto stage = [&](int kt, int buf) {
-        const int base_row = row_begin + kt * KT + wave * WROWS;
-        const bool full = (kt + 1) * KT <= nrows;               // block-uniform
-        if (full) {
-            const unsigned ka = kt * strideA, kb = kt * strideB;
+        const unsigned ka = kt * strideA, kb = kt * strideB;
 #pragma unroll
-            for (int j = 0; j < NINST; ++j) {
-                glds16_m0(Ab0 + ka, offA[j], ldsA + buf * TILE_BYTES + j * 1024);      // (K offset on the scalar base, no M0 save / restore: common.h)
-                glds16_m0(Bb0 + kb, offB[j], ldsB + buf * TILE_BYTES + j * 1024);
-            }
-        } else {                                                    // ragged last K-tile: ordinary loads, zero fill
-#pragma unroll 1
-            for (int j = 0; j < NINST; ++j) {
-                const int r = j * RPI + lrow;
-                const int trow = wave * WROWS + r;
-                const int ca = TT::sw(trow, lslot), cb = TT::sw(trow, lslot);
-                const bool ok = (kt * KT + trow) < nrows;
-                uint4 va = make_uint4(0, 0, 0, 0), vb = va;
-                if (ok && ca < a_cmax) va = *reinterpret_cast<const uint4*>(Ab + ((long)(base_row + r) * p.lda + n1_0) * ES + ca * 16);
-                if (ok && cb < b_cmax) vb = *reinterpret_cast<const uint4*>(Bb + ((long)(base_row + r) * p.ldb + n2_0) * ES + cb * 16);
-                *reinterpret_cast<uint4*>(sA + buf * TILE_BYTES + trow * ROWB + lslot * 16) = va;
-                *reinterpret_cast<uint4*>(sB + buf * TILE_BYTES + trow * ROWB + lslot * 16) = vb;
-            }
+        for (int j = 0; j < NINST; ++j) {
+            glds16_m0(Ab0 + ka, offA[j], ldsA + buf * TILE_BYTES + j * 1024);      // (K offset on the scalar base, no M0 save / restore: common.h)
+            glds16_m0(Bb0 + kb, offB[j], ldsB + buf * TILE_BYTES + j * 1024);
         }
     };
-    auto compute = [&](int cur, int kt_now) {
+    auto stage_ragged = [&](int kt, int buf) {                  // ordinary loads, zero fill
+        const int base_row = row_begin + kt * KT + wave * WROWS;
+#pragma unroll 1
+        for (int j = 0; j < NINST; ++j) {
+            const int r = j * RPI + lrow;
+            const int trow = wave * WROWS + r;
+            const int ca = TT::sw(trow, lslot), cb = TT::sw(trow, lslot);
+            const bool ok = (kt * KT + trow) < nrows;
+            uint4 va = make_uint4(0, 0, 0, 0), vb = va;
+            if (ok && ca < a_cmax) va = *reinterpret_cast<const uint4*>(Ab + ((long)(base_row + r) * p.lda + n1_0) * ES + ca * 16);
+            if (ok && cb < b_cmax) vb = *reinterpret_cast<const uint4*>(Bb + ((long)(base_row + r) * p.ldb + n2_0) * ES + cb * 16);
+            *reinterpret_cast<uint4*>(sA + buf * TILE_BYTES + trow * ROWB + lslot * 16) = va;
+            *reinterpret_cast<uint4*>(sB + buf * TILE_BYTES + trow * ROWB + lslot * 16) = vb;
+        }
+    };
+    // bias_cnt: K-tiles until the next one whose column sums this tile takes (kt % bias_mod == bias_rem without the division)
+    int bias_cnt = bias_rem;
+    auto compute = [&](int cur) {
         const char* cA = sA + cur * TILE_BYTES;
         const char* cB = sB + cur * TILE_BYTES;
-        const bool bias_now = do_bias && (kt_now % bias_mod) == bias_rem;
+        const bool bias_now = do_bias && bias_cnt == 0;
+        bias_cnt = bias_cnt == 0 ? bias_mod - 1 : bias_cnt - 1;
+        // bf16: both k-steps' fragments (64 registers) are requested before the K-tile's first MFMA; f32 (four k-steps): one at a time
+        constexpr int NS = KT / KSTEP, G = ES == 2 ? NS : 1;
 #pragma unroll
-        for (int s = 0; s < KT / KSTEP; ++s) {
-            uint4 f1[4], f2[4];
+        for (int s0 = 0; s0 < NS; s0 += G) {
+            uint4 f1[G][4], f2[G][4];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                f1[t] = tn_frag<T>(cA, s * KSTEP, w1 * 64 + t * 16, lane);
-                f2[t] = tn_frag<T>(cB, s * KSTEP, w2 * 64 + t * 16, lane);
-            }
+            for (int s = 0; s < G; ++s)
 #pragma unroll
-            for (int a = 0; a < 4; ++a)
+                for (int t = 0; t < 4; ++t) {
+                    f1[s][t] = tn_frag<T>(cA, (s0 + s) * KSTEP, w1 * 64 + t * 16, lane);
+                    f2[s][t] = tn_frag<T>(cB, (s0 + s) * KSTEP, w2 * 64 + t * 16, lane);
+                }
 #pragma unroll
-                for (int b = 0; b < 4; ++b) mma16<T>(f2[b], f1[a], acc[a][b]);   // rows(regs) = n2, cols(lanes) = n1
-            if (bias_now) {                                      // (block-uniform; w2 wave-uniform)
-                if (w2 == 0) { mma16<T>(ones, f1[0], bacc[0]); mma16<T>(ones, f1[1], bacc[1]); }
-                else { mma16<T>(ones, f1[2], bacc[0]); mma16<T>(ones, f1[3], bacc[1]); }
+            for (int s = 0; s < G; ++s) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) mma16<T>(f2[s][b], f1[s][a], acc[a][b]);   // rows(regs) = n2, cols(lanes) = n1
+                if (bias_now) {                                  // (block-uniform; w2 wave-uniform)
+                    if (w2 == 0) { mma16<T>(ones, f1[s][0], bacc[0]); mma16<T>(ones, f1[s][1], bacc[1]); }
+                    else { mma16<T>(ones, f1[s][2], bacc[0]); mma16<T>(ones, f1[s][3], bacc[1]); }
+                }
             }
         }
     };
@@ -596,22 +604,31 @@ TAV_DEV void gemm_tn_body(const GemmTN& p, const int tile, const int split) {
     // NST-deep ring: while tile kt is multiplied, tiles kt+1 .. kt+NST-2 are in flight and tile kt+NST-1 is issued right after the
     // barrier (its buffer held tile kt-1, which every wave has finished).  vmcnt retires in issue order: tile kt has landed once at
     // most (NST-2) younger tiles x 2*NINST instructions are outstanding; the last NST-2 tiles (fewer in flight, possibly the ragged
-    // one) wait for everything.
+    // one) wait for everything.  Whether the last tile is ragged is decided here, once: the steady loop stages whole tiles only.
+    const int nd = nrows / KT;                                  // whole K-tiles: 0 .. nd-1 go by DMA, tile nd (if nk > nd) is the ragged one
 #pragma unroll
     for (int t = 0; t < NST - 1; ++t)
-        if (t < nk) stage(t, t);
+        if (t < nk) { if (t < nd) stage(t, t); else stage_ragged(t, t); }
     int cur = 0, kt = 0;
-    for (; kt + NST - 1 < nk; ++kt) {
+    for (; kt + NST - 1 < nd; ++kt) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * 2 * NINST) : "memory");
         __syncthreads();
         stage(kt + NST - 1, cur == 0 ? NST - 1 : cur - 1);
-        compute(cur, kt);
+        compute(cur);
         cur = cur + 1 == NST ? 0 : cur + 1;
+    }
+    if (kt + NST - 1 < nk) {                                    // the ragged tile's turn to be staged
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * 2 * NINST) : "memory");
+        __syncthreads();
+        stage_ragged(kt + NST - 1, cur == 0 ? NST - 1 : cur - 1);
+        compute(cur);
+        cur = cur + 1 == NST ? 0 : cur + 1;
+        ++kt;
     }
     for (; kt < nk; ++kt) {
         wait_vmcnt0();
         __syncthreads();
-        compute(cur, kt);
+        compute(cur);
         cur = cur + 1 == NST ? 0 : cur + 1;
     }
     __syncthreads();
@@ -677,7 +694,7 @@ TAV_DEV void gemm_tn_big_body(const GemmTN& p, const int tile, const int split) 
     constexpr int STAGE = 4 * SUB;                          // A0 A1 B0 B1
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (scalar: the w2 tests are branches, not masks)
     const int g = lane >> 4, i = lane & 15;
     const int w1 = wave >> 1, w2 = wave & 1;                // n1 block of 64 (0..3), n2 block of 128 (0..1)
 
@@ -760,48 +777,69 @@ TAV_DEV void gemm_tn_big_body(const GemmTN& p, const int tile, const int split) 
     // after the barrier they cost every wave of the CU ~1000 cycles of issue time at the same moment, with nothing on the matrix pipe.
     // Iteration kt issues X(kt+1) and dY(kt+2); issue order X then dY, so at the next wait the 4 youngest pieces are dY's and may stay
     // in flight.
-    constexpr int AHEAD_A = 2;
-    if (nk > 0) { stage_a(0, 0); stage_b(0, 0); if (nk > 1) stage_a(1, 1); }
-    int ca = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const int cb = kt & 1;
-        if (is_dma(kt + 1)) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    // One K-tile, compiled three times like the NT kernel's ktile25 (ISSUE_B: X(kt+1) is a whole tile and goes out by DMA, ISSUE_A: so does
+    // dY(kt+2); TAIL: one of them may be the ragged last tile, staged through registers right after the barrier).  The steady body
+    // <true, true, false> decides nothing at run time but the bias MFMAs.  K-step 1's fragments are requested while K-step 0 is multiplied:
+    // X fragment b right after the MFMA group that was the last reader of K-step 0's, the four dY fragments (16 registers of their own)
+    // after the fourth group -- the second K-step starts with its reads landed or in flight instead of with an empty matrix pipe.
+    // bias_cnt: K-tiles until the next one whose column sums this tile takes (kt % bias_mod == bias_rem without the division).
+    int ca = 0, cb = 0, bias_cnt = bias_rem;
+    auto ktile = [&](int kt, auto issue_b, auto issue_a, auto tail) {
+        constexpr bool IB = decltype(issue_b)::value, IA = decltype(issue_a)::value, TAIL = decltype(tail)::value;
+        if constexpr (IB) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");          // dY(kt+1) was issued after X(kt): it may still fly
         else wait_vmcnt0();
         __syncthreads();
-        const int na = ca == 0 ? 2 : ca - 1, nb = cb ^ 1;      // slots of dY(kt + AHEAD_A), X(kt + 1)
-        const bool dma_b = is_dma(kt + 1), dma_a = is_dma(kt + AHEAD_A);          // block-uniform
-        if (kt + 1 < nk && !dma_b) stage_b(kt + 1, nb);                            // (ragged last tile: through registers, up front)
-        if (kt + AHEAD_A < nk && !dma_a) stage_a(kt + AHEAD_A, na);
-        const unsigned ka = (unsigned)(kt + AHEAD_A) * strideA, kb = (unsigned)(kt + 1) * strideB;
+        const int na = ca == 0 ? 2 : ca - 1, nb = cb ^ 1;      // slots of dY(kt + 2), X(kt + 1)
+        if constexpr (TAIL) {                                   // (block-uniform; at most once per operand and workgroup)
+            if (last_ragged && kt + 1 == nk - 1) stage_ragged(kt + 1, nb, true);
+            if (last_ragged && kt + 2 == nk - 1) stage_ragged(kt + 2, na, false);
+        }
+        const unsigned ka = (unsigned)(kt + 2) * strideA, kb = (unsigned)(kt + 1) * strideB;
         const char* cA = smem + ca * IMG + (w1 >> 1) * SUB;
         const char* cB = smem + OFF_B + cb * IMG + w2 * SUB;
-        const bool bias_now = do_bias && (kt % bias_mod) == bias_rem;
+        const bool bias_now = do_bias && bias_cnt == 0;
+        uint4 f1[4], f2[8], g1[4];
 #pragma unroll
-        for (int s2 = 0; s2 < KT / KSTEP; ++s2) {
-            uint4 f1[4], f2[8];
+        for (int t = 0; t < 4; ++t) f1[t] = tn_frag<T>(cA, 0, (w1 & 1) * 64 + t * 16, lane);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) f1[t] = tn_frag<T>(cA, s2 * KSTEP, (w1 & 1) * 64 + t * 16, lane);
+        for (int t = 0; t < 8; ++t) f2[t] = tn_frag<T>(cB, 0, t * 16, lane);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < 8; ++t) f2[t] = tn_frag<T>(cB, s2 * KSTEP, t * 16, lane);
+        for (int b = 0; b < 8; ++b) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) mma16<T>(f2[b], f1[a], acc[a][b]);       // rows(regs) = n2, cols(lanes) = n1
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (IB) { if (b < 4) piece_b(b, kb, nb); }
+            if constexpr (IA) { if (b >= 4) piece_a(b - 4, ka, na); }
+            f2[b] = tn_frag<T>(cB, KSTEP, b * 16, lane);
+            if (b == 3) {
 #pragma unroll
-            for (int b = 0; b < 8; ++b) {
+                for (int t = 0; t < 4; ++t) g1[t] = tn_frag<T>(cA, KSTEP, (w1 & 1) * 64 + t * 16, lane);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (bias_now) {
+            if (w2 == 0) { mma16<T>(ones, f1[0], bacc[0]); mma16<T>(ones, f1[1], bacc[1]); }
+            else { mma16<T>(ones, f1[2], bacc[0]); mma16<T>(ones, f1[3], bacc[1]); }
+        }
 #pragma unroll
-                for (int a = 0; a < 4; ++a) mma16<T>(f2[b], f1[a], acc[a][b]);   // rows(regs) = n2, cols(lanes) = n1
-                if (s2 == 0) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (b < 4) { if (dma_b) piece_b(b, kb, nb); }
-                    else { if (dma_a) piece_a(b - 4, ka, na); }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            if (bias_now) {
-                if (w2 == 0) { mma16<T>(ones, f1[0], bacc[0]); mma16<T>(ones, f1[1], bacc[1]); }
-                else { mma16<T>(ones, f1[2], bacc[0]); mma16<T>(ones, f1[3], bacc[1]); }
-            }
+        for (int b = 0; b < 8; ++b)
+#pragma unroll
+            for (int a = 0; a < 4; ++a) mma16<T>(f2[b], g1[a], acc[a][b]);
+        if (bias_now) {
+            if (w2 == 0) { mma16<T>(ones, g1[0], bacc[0]); mma16<T>(ones, g1[1], bacc[1]); }
+            else { mma16<T>(ones, g1[2], bacc[0]); mma16<T>(ones, g1[3], bacc[1]); }
         }
         ca = ca == 2 ? 0 : ca + 1;
-    }
+        cb ^= 1;
+        bias_cnt = bias_cnt == 0 ? bias_mod - 1 : bias_cnt - 1;
+    };
+    if (nk > 0) { stage_a(0, 0); stage_b(0, 0); if (nk > 1) stage_a(1, 1); }
+    const int nd = last_ragged ? nk - 1 : nk;               // whole K-tiles: 0 .. nd-1 go by DMA
+    int kt = 0;
+    for (; kt + 2 < nd; ++kt) ktile(kt, std::true_type{}, std::true_type{}, std::false_type{});
+    if (kt + 1 < nd) { ktile(kt, std::true_type{}, std::false_type{}, std::true_type{}); ++kt; }
+    for (; kt < nk; ++kt) ktile(kt, std::false_type{}, std::false_type{}, std::true_type{});
     __syncthreads();
 
     if (do_bias && g == 0) {
