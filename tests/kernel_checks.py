@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import attn_ref as AR
+import front_ref as FR
 import gemm_ref as GR
 import guarded
 import norm_ref as NR
@@ -2620,6 +2621,431 @@ def norm_fp64_checks():
     return out
 
 
+# ================================================================================================= front-end, pooling, head, loss against fp64
+# tests/front_ref.py: per-element bounds at operands of spread magnitude and integer cases with ONE right answer for the kernels the chains
+# above judge only through later stages: the rest of csrc/audio_frontend.hip, tav_colsum, the stand-alone GELU pair, the pools, the head, tanh,
+# the cross entropy and the index kernels.  The C ABI is called directly: accumulation, NULL outputs and workspaces at exactly the advertised
+# size are things the ops wrappers cannot express.  Every output starts as 0xFF.
+_F32 = torch.float32
+
+
+def _fb(rs, tag, got, ref, names):
+    for n in names:
+        if got.get(n) is not None:
+            rs.append(_bounded(f"{tag}.{n}", got[n], ref[n], ref[n + "_b"]))
+
+
+def _fx(rs, tag, got, want, dtype=torch.float32):
+    want = np.asarray(want)
+    rs.append(_exact(tag, got, _want(want.reshape(tuple(got.shape)) if want.size == got.numel() else want, dtype)))
+
+
+def _ints_dev(a, dtype):
+    return _in(torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(DEV))
+
+
+def _conv0_fwd_abi(p, bias, dtype):
+    wave, w = _dev(p["wave"], _F32), _dev(p["w"], _F32)
+    b = _dev(p["bias"], _F32) if bias else None
+    y = _blank((p["B"], p["T_out"], p["C"]), dtype)
+    ops.check(ops.lib().tav_conv0_fwd(ops.ptr(wave), ops.ptr(w), ops.ptr(b), ops.ptr(y), ops.dt(dtype), p["B"], p["T_in"], p["T_out"], p["C"], p["K"],
+                                      p["stride"], ops.stream()), "conv0_fwd")
+    return dict(y=y)
+
+
+def check_conv0_fwd_fp64(dt):
+    """tav_conv0_fwd: C = 4 (one quad), 12 (85 time groups and an idle thread), 512 (the model's), 1028 (a second quad pass) x T_out = 1, 127,
+    128, 129, 257 (around one and two blocks of C0_TT), (K, stride) cycling through (10, 5), (16, 8), (1, 1), (3, 2), B = 1 | 3, bias on | off,
+    T_in exact | 7 longer; every fourth shape also on integers (one right answer)."""
+    rs, i = [], 0
+    for C in (4, 12, 512, 1028):
+        for T_out in (1, 127, 128, 129, 257):
+            K, s = ((10, 5), (16, 8), (1, 1), (3, 2))[i % 4]
+            B, bias, extra = (1, 3)[i % 2], i % 3 != 0, 7 * ((i // 2) % 2)
+            for exact in (False, True) if i % 4 == 1 else (False,):
+                p = FR.conv0_inputs(B, T_out, C, K, s, extra=extra, exact=exact)
+                tag = f"conv0.fwd[{dt},B{B},T{T_out},C{C},K{K},s{s},bias{int(bias)},+{extra}{',int' if exact else ''}]"
+                got, ref = _conv0_fwd_abi(p, bias, _TDT[dt]), FR.conv0_ref_fwd(p, bias, dt)
+                if exact:
+                    _fx(rs, tag + ".y", got["y"], FR.held(ref["y"], dt), _TDT[dt])
+                else:
+                    _fb(rs, tag, got, ref, ("y",))
+            i += 1
+    return rs
+
+
+def _conv0_bwd_abi(p, want_bias, accumulate):
+    B, T_out, C, K = p["B"], p["T_out"], p["C"], p["K"]
+    wave, dy = _dev(p["wave"], _F32), _dev(p["dy"], _TDT[p["dydt"]])
+    n = ops.lib().tav_conv0_bwd_partials(B, T_out, C, K)
+    assert n == B * -(-T_out // FR.C0_BT) * C * (K + 1)
+    part = _blank((n,), _F32)                                                       # exactly the advertised size, under guard
+    dw = _filled(p["prev_w"]) if accumulate else _blank((C, K), _F32)
+    db = None if not want_bias else (_filled(p["prev_b"]) if accumulate else _blank((C,), _F32))
+    ops.check(ops.lib().tav_conv0_bwd_w(ops.ptr(wave), ops.ptr(dy), ops.dt(dy), ops.ptr(dw), ops.ptr(db), ops.ptr(part), B, p["T_in"], T_out, C, K,
+                                        p["stride"], int(accumulate), ops.stream()), "conv0_bwd_w")
+    return dict(dw=dw, dbias=db)
+
+
+def check_conv0_bwd_fp64(dydt, Cs):
+    """tav_conv0_bwd_w at two of the widths C = 8, 64 (threads idle in the channel loop), 512, 520 (a second, ragged pass of it) x T_out = 1, 3,
+    511, 512, 513, 1025, 1537, 2050 (one chunk of C0_BT, a ragged second one, up to five: t0 > 0 and the cross-chunk reduce), B in {1, 3, 5} and
+    K in {1, 3, 10} cycling -- nblocks % 4 takes all four values: 1537 with B = 1 gives 4 blocks, which no odd B reaches at the other lengths --,
+    dbias NULL | given, accumulate 0 | 1; T_out = 513 and the extremes also on integers."""
+    rs, i = [], 0
+    for C in Cs:
+        for T_out in (1, 3, 511, 512, 513, 1025, 1537, 2050):
+            B = 1 if T_out == 1537 else (1, 3, 5)[i % 3]
+            K = (1, 3, 10)[(i + i // 3) % 3]
+            s = {1: 1, 3: 2, 10: 5}[K]
+            want_bias, acc = i % 2 == 0, (i // 2) % 2 == 1
+            p = FR.conv0_inputs(B, T_out, C, K, s, dydt=dydt)
+            tag = f"conv0.bwd[dy {dydt},B{B},T{T_out},C{C},K{K},db{int(want_bias)},acc{int(acc)}]"
+            _fb(rs, tag, _conv0_bwd_abi(p, want_bias, acc), FR.conv0_ref_bwd_w(p, acc), ("dw", "dbias"))
+            if T_out == 513 or (C, T_out) in ((8, 2050), (520, 3)):
+                q = FR.conv0_inputs(B, T_out, C, K, s, dydt=dydt, exact=True)
+                got, ref = _conv0_bwd_abi(q, True, True), FR.conv0_ref_bwd_w(q, True)
+                _fx(rs, tag + ".int dw", got["dw"], ref["dw"])
+                _fx(rs, tag + ".int dbias", got["dbias"], ref["dbias"])
+            i += 1
+    return rs
+
+
+def _wn_fwd_abi(p, dtype, which, v, g):
+    H, Cg, K = p["H"], p["Cg"], p["K"]
+    nb = ops.lib().tav_weight_norm_partials(H, Cg)
+    assert nb == FR.wn_blocks(H, Cg)[0]
+    norms, part = _blank((K,), _F32), _blank((nb * K,), _F32)
+    w = _blank((p["G"], Cg, K, Cg), dtype) if which != "w_flip" else None
+    wf = _blank((p["G"], Cg, K, Cg), dtype) if which != "w" else None
+    ops.check(ops.lib().tav_weight_norm_fwd(ops.ptr(v), ops.ptr(g), ops.ptr(norms), ops.ptr(part), ops.ptr(w), ops.ptr(wf), ops.dt(dtype), H, Cg, K,
+                                            ops.stream()), "weight_norm_fwd")
+    return dict(norms=norms, w=w, w_flip=wf)
+
+
+def _wn_bwd_abi(p, norms, accumulate, v, g):
+    H, Cg, K = p["H"], p["Cg"], p["K"]
+    ws = _blank((FR.wn_bwd_workspace_floats(H, Cg, K),), _F32)
+    dv, dg = (_filled(p["prev_v"]), _filled(p["prev_g"])) if accumulate else (_blank((H, Cg, K), _F32), _blank((K,), _F32))
+    ops.check(ops.lib().tav_weight_norm_bwd(ops.ptr(v), ops.ptr(g), ops.ptr(norms), ops.ptr(_dev(p["dw"], _F32)), ops.ptr(ws), ops.ptr(dv), ops.ptr(dg),
+                                            H, Cg, K, int(accumulate), ops.stream()), "weight_norm_bwd")
+    return dict(dv=dv, dg=dg)
+
+
+def check_weight_norm_fp64(H, Cg, K, parts="fb"):
+    """tav_weight_norm_fwd / _bwd at one (H, Cg, K): norms, w, w_flip (w only, w_flip only, both; both dtypes) and -- fed the reference's norms
+    rounded to f32 (isolated) and the kernel's own (chained) -- dv, dg, accumulating and not; then the construction with ||v|| = 2^k, bit for bit.
+    parts: "f" the forward, "b" the backward (the model's shape is split in two groups)."""
+    rs = []
+    big = H * Cg * K > 1 << 20
+    p, q = FR.wn_inputs(H, Cg, K), FR.wn_inputs(H, Cg, K, exact=True)
+    v, g = _dev(p["v"], _F32), _dev(p["g"], _F32)
+    qv, qg = _dev(q["v"], _F32), _dev(q["g"], _F32)
+    tag = f"wn[H{H},Cg{Cg},K{K}]"
+    if "f" in parts:
+        for dt in ("f32", "bf16"):
+            ref = FR.wn_ref_fwd(p, dt)
+            for which in (("w", "w_flip") if dt == "f32" else ("both",)) if big else ("w", "w_flip", "both"):
+                _fb(rs, f"{tag}.fwd[{dt},{which}]", _wn_fwd_abi(p, _TDT[dt], which, v, g), ref, ("norms", "w", "w_flip"))
+            got, want = _wn_fwd_abi(q, _TDT[dt], "both", qv, qg), FR.wn_ref_fwd(q, dt)
+            _fx(rs, f"{tag}.int norms[{dt}]", got["norms"], want["norms"])
+            _fx(rs, f"{tag}.int w[{dt}]", got["w"], FR.held(want["w"], dt), _TDT[dt])
+            _fx(rs, f"{tag}.int w_flip[{dt}]", got["w_flip"], FR.held(want["w_flip"], dt), _TDT[dt])
+    if "b" in parts:
+        ref = FR.wn_ref_fwd(p, "f32")
+        nv, n32 = FR.fed(ref["norms"])
+        fed = _dev(n32, _F32)
+        for acc in ((True,) if big else (False, True)):                              # (a big shape: isolated accumulating, chained not)
+            _fb(rs, f"{tag}.bwd[acc{int(acc)}]", _wn_bwd_abi(p, fed, acc, v, g), FR.wn_ref_bwd(p, nv, acc), ("dv", "dg"))
+        own = _wn_fwd_abi(p, _F32, "w", v, g)["norms"]
+        acc = not big and (H // Cg) % 2 == 0
+        _fb(rs, f"{tag}.bwd.chained[acc{int(acc)}]", _wn_bwd_abi(p, own, acc, v, g), FR.wn_ref_bwd(p, ref["_norms"], acc), ("dv", "dg"))
+        got, want = _wn_bwd_abi(q, _dev(FR.wn_ref_fwd(q, "f32")["norms"], _F32), True, qv, qg), FR.wn_ref_bwd(q, FR.V(FR.wn_ref_fwd(q, "f32")["norms"]), True)
+        _fx(rs, f"{tag}.int dv", got["dv"], want["dv"])
+        _fx(rs, f"{tag}.int dg", got["dg"], want["dg"])
+    return rs
+
+
+def check_group_pad_fp64():
+    """tav_group_pad is a copy with zero frames: bit for bit in all three dtype pairs (f32 -> bf16 with its round-to-nearest-even), at the smallest
+    launch, the positional conv's forward (64, 64) and backward (63, 64) frames, sixteen groups with a short right frame, and no left frame."""
+    rs = []
+    for B, T, H, G, pl, pr in ((1, 1, 8, 2, 0, 0), (2, 49, 256, 4, 64, 64), (2, 49, 256, 4, 63, 64), (3, 5, 768, 16, 64, 63), (2, 3, 16, 2, 0, 5), (1, 70, 16, 1, 1, 0)):
+        for sdt, ddt in (("f32", "bf16"), ("f32", "f32"), ("bf16", "bf16")):
+            x = FR.gp_inputs(B, T, H, sdt)
+            xt = _dev(x, _TDT[sdt])
+            xg = _blank((B, G, pl + T + pr, H // G), _TDT[ddt])
+            ops.check(ops.lib().tav_group_pad(ops.ptr(xt), ops.dt(xt), ops.ptr(xg), ops.dt(xg), B, T, H, G, pl, pr, ops.stream()), "group_pad")
+            _fx(rs, f"group_pad[{sdt}->{ddt},B{B},T{T},H{H},G{G},{pl}+{pr}]", xg, FR.gp_ref(x, G, pl, pr, ddt), _TDT[ddt])
+    return rs
+
+
+def check_col2im_fp64(dt):
+    """tav_col2im_1d on its own: (K, stride) = (3, 2), (2, 2), (10, 5), (3, 1), T_in exact and 3 longer (rows no tap reaches: exactly zero), with
+    and without the gelu' product, one and many workgroups; on integers with pre in [16, 48], where gelu' is exactly 1."""
+    rs, i = [], 0
+    dtype = _TDT[dt]
+    for K, s in ((3, 2), (2, 2), (10, 5), (3, 1)):
+        for extra in (0, 3):
+            for with_pre in (False, True):
+                B, T_out, C = ((1, 1, 4), (2, 7, 8), (2, 130, 68))[i % 3]
+                for exact in (False, True) if i % 2 == 0 else (False,):
+                    p = FR.c2i_inputs(B, T_out, C, K, s, extra, dt, exact=exact)
+                    dcol, pre = _dev(p["dcol"], dtype), _dev(p["pre"], dtype) if with_pre else None
+                    dx = _blank((B, p["T_in"], C), dtype)
+                    ops.check(ops.lib().tav_col2im_1d(ops.ptr(dcol), ops.ptr(dx), ops.ptr(pre), ops.dt(dtype), B, p["T_in"], T_out, C, K, s, ops.stream()), "col2im_1d")
+                    tag = f"col2im[{dt},B{B},T{T_out},C{C},K{K},s{s},+{extra},pre{int(with_pre)}{',int' if exact else ''}]"
+                    ref = FR.c2i_ref(p, with_pre and not exact)
+                    if exact:
+                        _fx(rs, tag, dx, FR.held(ref["dx"], dt), dtype)
+                    else:
+                        _fb(rs, tag, dict(dx=dx), ref, ("dx",))
+                i += 1
+    return rs
+
+
+def check_gelu_tanh_fp64():
+    """tav_gelu_fwd (no other caller in the tests) and tav_gelu_bwd per element over [-12, 12], +-0 and +-40 at n = 4, 1020, 1028, both dtypes;
+    tav_tanh_fwd / _bwd over [-10, 10], +-0 and +-90."""
+    rs = []
+    for dt in ("f32", "bf16"):
+        for n in (4, 1020, 1028):
+            p = FR.gelu_inputs(n, dt)
+            x, dy = _dev(p["x"], _TDT[dt]), _dev(p["dy"], _TDT[dt])
+            y, dx = _blank((n,), _TDT[dt]), _blank((n,), _TDT[dt])
+            ops.check(ops.lib().tav_gelu_fwd(ops.ptr(x), ops.ptr(y), ops.dt(x), n, ops.stream()), "gelu_fwd")
+            ops.check(ops.lib().tav_gelu_bwd(ops.ptr(x), ops.ptr(dy), ops.ptr(dx), ops.dt(x), n, ops.stream()), "gelu_bwd")
+            _fb(rs, f"gelu[{dt},n{n}]", dict(y=y, dx=dx), FR.gelu_ref(p), ("y", "dx"))
+    for n in (5, 260, 1029):
+        p = FR.tanh_inputs(n)
+        x, yin, dy = _dev(p["x"], _F32), _dev(p["y"], _F32), _dev(p["dy"], _F32)
+        y, dx = _blank((n,), _F32), _blank((n,), _F32)
+        ops.check(ops.lib().tav_tanh_fwd(ops.ptr(x), ops.ptr(y), n, ops.stream()), "tanh_fwd")
+        ops.check(ops.lib().tav_tanh_bwd(ops.ptr(yin), ops.ptr(dy), ops.ptr(dx), n, ops.stream()), "tanh_bwd")
+        _fb(rs, f"tanh[n{n}]", dict(y=y, dx=dx), FR.tanh_ref(p), ("y", "dx"))
+    return rs
+
+
+def _colsum_abi(p, nparts, accumulate, pitch):
+    M, N = p["M"], p["N"]
+    x = _dev(p["x"], _TDT[p["dt"]], pitch)
+    part = _blank((nparts * N,), _F32)
+    out = _filled(p["prev"]) if accumulate else _blank((N,), _F32)
+    ops.check(ops.lib().tav_colsum(ops.ptr(x), ops.dt(x), M, N, x.stride(0), ops.ptr(part), nparts, ops.ptr(out), int(accumulate), ops.stream()), "colsum")
+    return dict(out=out)
+
+
+def check_colsum_fp64(dt):
+    """tav_colsum: M = 1, 15, 17, 1000, 4097 x N = 1, 255, 257, 768, dense and with ld = N + 8, accumulating and not, nparts what ops.colsum
+    computes, 1 (one block takes every row) and 256 (blocks without a row); M = 17 and 4097 also on integers."""
+    rs, i = [], 0
+    for M in (1, 15, 17, 1000, 4097):
+        for N in (1, 255, 257, 768):
+            nparts = (FR.colsum_nparts(M), 1, 256)[i % 3]
+            pitch, acc = 8 * (i % 2), (i // 2) % 2 == 1
+            p = FR.colsum_inputs(M, N, dt)
+            tag = f"colsum[{dt},M{M},N{N},nparts{nparts},ld+{pitch},acc{int(acc)}]"
+            _fb(rs, tag, _colsum_abi(p, nparts, acc, pitch), FR.colsum_ref(p, nparts, acc), ("out",))
+            if M in (17, 4097):
+                q = FR.colsum_inputs(M, N, dt, exact=True)
+                _fx(rs, tag + ".int", _colsum_abi(q, nparts, True, pitch)["out"], FR.colsum_ref(q, nparts, True)["out"])
+            i += 1
+    return rs
+
+
+def _pool_abi(p, lens, want32, lp):
+    B, S, W = p["B"], p["S"], p["W"]
+    x, dy = _dev(p["x"], _F32), _dev(p["dy"], _F32)
+    y = _blank((B, W), _F32)
+    dx = _blank((B, S, W), _F32) if want32 else None
+    dl = _blank((B, S, W), torch.bfloat16) if lp else None
+    lpd = ops.dt(torch.bfloat16) if lp else 0
+    if lens is None:
+        ops.check(ops.lib().tav_mean_pool_fwd(ops.ptr(x), ops.ptr(y), B, S, W, ops.stream()), "mean_pool_fwd")
+        ops.check(ops.lib().tav_mean_pool_bwd(ops.ptr(dy), ops.ptr(dx), ops.ptr(dl), lpd, B, S, W, ops.stream()), "mean_pool_bwd")
+    else:
+        lt = _ints_dev(np.asarray(lens), torch.int32)
+        ops.check(ops.lib().tav_mean_pool_fwd_len(ops.ptr(x), ops.ptr(y), ops.ptr(lt), B, S, W, ops.stream()), "mean_pool_fwd_len")
+        ops.check(ops.lib().tav_mean_pool_bwd_len(ops.ptr(dy), ops.ptr(dx), ops.ptr(dl), lpd, ops.ptr(lt), B, S, W, ops.stream()), "mean_pool_bwd_len")
+    return dict(y=y, dx_f32=dx, dx_lp=dl)
+
+
+def check_mean_pool_fp64():
+    """The mean pools, plain and length-aware: W = 4, 68 (the c < W guard of the last block decides), 768 x S = 1, 15, 16, 17, 77 x B = 1 | 3,
+    lens among 0, 1, S and S + 5 (clamped), backward into f32 only, bf16 only and both; S = 16 | 64 and L_b powers of two on integers."""
+    rs, i = [], 0
+    for W in (4, 68, 768):
+        for S in (1, 15, 16, 17, 77):
+            B = (1, 3)[i % 2]
+            want32, lp = ((True, False), (False, True), (True, True))[i % 3]
+            for lens in (None, ((S + 5,), (0, 1, S + 5), (S,), (S, max(1, S // 2), 0))[(i % 2) + 2 * ((i // 2) % 2)]):
+                p = FR.pool_inputs(B, S, W)
+                tag = f"pool[B{B},S{S},W{W},lens{lens},f32{int(want32)},bf16{int(lp)}]"
+                _fb(rs, tag, _pool_abi(p, lens, want32, lp), FR.pool_ref(p, lens), ("y", "dx_f32", "dx_lp"))
+            i += 1
+        for S, lens in ((16, None), (64, (16, 64, 0)), (64, (1, 69, 32))):
+            q = FR.pool_inputs(3, S, W, exact=True)
+            got, ref = _pool_abi(q, lens, True, True), FR.pool_ref(q, lens)
+            tag = f"pool.int[S{S},W{W},lens{lens}]"
+            _fx(rs, tag + ".y", got["y"], ref["y"])
+            _fx(rs, tag + ".dx_f32", got["dx_f32"], ref["dx_f32"])
+            _fx(rs, tag + ".dx_lp", got["dx_lp"], FR.held(ref["dx_lp"], "bf16"), torch.bfloat16)
+    return rs
+
+
+def _head_abi(p, bias, need_dx, need_db, accumulate):
+    B, K, N = p["B"], p["K"], p["N"]
+    x, W, dy = _dev(p["x"], _F32), _dev(p["W"], _F32), _dev(p["dy"], _F32)
+    b = _dev(p["bias"], _F32) if bias else None
+    y = _blank((B, N), _F32)
+    ops.check(ops.lib().tav_head_fwd(ops.ptr(x), ops.ptr(W), ops.ptr(b), ops.ptr(y), B, K, N, ops.stream()), "head_fwd")
+    dx = _blank((B, K), _F32) if need_dx else None
+    dW = _filled(p["prev_W"]) if accumulate else _blank((N, K), _F32)
+    db = None if not need_db else (_filled(p["prev_b"]) if accumulate else _blank((N,), _F32))
+    ops.check(ops.lib().tav_head_bwd(ops.ptr(x), ops.ptr(W), ops.ptr(dy), ops.ptr(dx), ops.ptr(dW), ops.ptr(db), B, K, N, int(accumulate), ops.stream()), "head_bwd")
+    return dict(y=y, dx=dx, dW=dW, db=db)
+
+
+def check_head_fp64():
+    """tav_head_fwd / _bwd: K = 1, 63, 65 (lanes idle in the dot product), 3072 x N = 1, 7, 256 x B = 1 | 5; bias NULL; the backward without
+    dx, without db, and accumulating; half of the shapes also on integers."""
+    rs, i = [], 0
+    for K in (1, 63, 65, 3072):
+        for N in (1, 7, 256):
+            for B in (1, 5):
+                bias = i % 3 != 1
+                need_dx, need_db, acc = ((True, True, False), (False, True, False), (True, False, False), (True, True, True))[i % 4]
+                for exact in (False, True) if i % 2 == 0 else (False,):
+                    p = FR.head_inputs(B, K, N, exact=exact)
+                    tag = f"head[B{B},K{K},N{N},bias{int(bias)},dx{int(need_dx)},db{int(need_db)},acc{int(acc)}{',int' if exact else ''}]"
+                    got, ref = _head_abi(p, bias, need_dx, need_db, acc), FR.head_ref(p, bias, acc)
+                    if exact:
+                        for n in ("y", "dx", "dW", "db"):
+                            if got[n] is not None:
+                                _fx(rs, f"{tag}.{n}", got[n], ref[n])
+                    else:
+                        _fb(rs, tag, got, ref, ("y", "dx", "dW", "db"))
+                i += 1
+    return rs
+
+
+def check_cross_entropy_fp64():
+    """tav_cross_entropy: C = 1, 2, 7, 64 x B = 1, 3, 255, 257, 600 (the loop over B > 256), rows of randn 2^(r % 5), rows offset by +-80 and
+    +-3e4, rows with one logit 60 above the rest; class weights 2^-3 .. 2^3 or none, grad_scale 1, 1 / 8, 3, loss only, dlogits only, both."""
+    rs, i = [], 0
+    for C in (1, 2, 7, 64):
+        for B in (1, 3, 255, 257, 600):
+            weighted, gs = i % 2 == 0, (1.0, 0.125, 3.0)[i % 3]
+            want_loss, want_grad = ((True, True), (True, False), (False, True))[(i // 2) % 3]
+            p = FR.ce_inputs(B, C)
+            z, t = _dev(p["z"], _F32), _ints_dev(p["t"], torch.int64)
+            cw = _dev(p["cw"], _F32) if weighted else None
+            loss = _blank((1,), _F32) if want_loss else None
+            dl = _blank((B, C), _F32) if want_grad else None
+            ops.check(ops.lib().tav_cross_entropy(ops.ptr(z), ops.ptr(t), ops.ptr(cw), ops.ptr(loss), ops.ptr(dl), B, C, gs, ops.stream()), "cross_entropy")
+            _fb(rs, f"ce[B{B},C{C},cw{int(weighted)},gs{gs},loss{int(want_loss)},grad{int(want_grad)}]", dict(loss=loss, dlogits=dl), FR.ce_ref(p, weighted, gs),
+                ("loss", "dlogits"))
+            i += 1
+    return rs
+
+
+def check_text_index_fp64():
+    """text_pos_ids_kernel and the three-table sum on integers: S = 63, 64, 65, 512, 513, 1024 (the scan width changes at 64, 128, ... 1024),
+    pads at the front, in the interior, as a suffix, a row of all pads and one without, pad_id = 1, 0, -1: pos_ids and pre bit for bit."""
+    rs = []
+    one, zero = np.ones(8), np.zeros(8)
+    for S in (63, 64, 65, 512, 513, 1024):
+        for pad_id in (1, 0, -1):
+            p = FR.text_inputs(5, S, pad_id)
+            ref = FR.text_ref(p)
+            _, _, pre, pos_ids, _, _ = ops.text_embed_fwd(_ints_dev(p["ids"], torch.int64), _dev(p["word"], _F32), _dev(p["pos"], _F32), _dev(p["type"], _F32),
+                                                          _dev(one, _F32), _dev(zero, _F32), 1e-5, pad_id)
+            rs += [_exact(f"text.pos_ids[S{S},pad{pad_id}]", pos_ids, torch.from_numpy(ref["pos_ids"]).to(DEV)),
+                   _exact(f"text.pre[S{S},pad{pad_id}]", pre, _want(ref["pre"], _F32))]
+    return rs
+
+
+def check_embed_add_fp64():
+    """tav_embed_add_fwd / _bwd on integers: ntable = 1, 3, 8 (the register array's size), rows = 1, 257, 65536 + 300 (past the 256-part cap),
+    accumulating and not."""
+    rs, i = [], 0
+    for ntable in (1, 3, 8):
+        for rows in (1, 257, 65536 + 300):
+            W = 4 if rows > 1000 else 260
+            acc = i % 2 == 0
+            p = FR.embed_inputs(rows, W, ntable)
+            ref = FR.embed_ref(p, acc)
+            ids, x, table, dy = _ints_dev(p["ids"], torch.int64), _dev(p["x"], _F32), _dev(p["table"], _F32), _dev(p["dy"], _F32)
+            out = _blank((rows, W), _F32)
+            ops.check(ops.lib().tav_embed_add_fwd(ops.ptr(x), ops.ptr(ids), ops.ptr(table), ops.ptr(out), rows, W, ntable, ops.stream()), "embed_add_fwd")
+            nparts = ops.lib().tav_embed_add_bwd_parts(rows)
+            assert nparts == FR.embed_parts(rows)
+            part = _blank((nparts * ntable * W,), _F32)
+            d = _filled(p["prev"]) if acc else _blank((ntable, W), _F32)
+            ops.check(ops.lib().tav_embed_add_bwd(ops.ptr(dy), ops.ptr(ids), ops.ptr(d), ops.ptr(part), rows, W, ntable, int(acc), ops.stream()), "embed_add_bwd")
+            tag = f"embed_add[rows{rows},W{W},ntable{ntable},acc{int(acc)}]"
+            _fx(rs, tag + ".fwd", out, ref["out"])
+            _fx(rs, tag + ".dtable", d, ref["dtable"])
+            i += 1
+    return rs
+
+
+def check_scatter_add_fp64():
+    """tav_scatter_add_rows on integers onto integer contents: rows = 1, 17, 1025, 4096 x W = 4, 132, 1024, one index carried by 1, 16, 17 rows
+    and by a quarter of them (one wave, sixteen waves, a second round of the waves)."""
+    rs = []
+    for rows in (1, 17, 1025, 4096):
+        for W in (4, 132, 1024):
+            p = FR.scatter_inputs(rows, W)
+            d, idx, table = _dev(p["d"], _F32), _ints_dev(p["idx"], torch.int64), _filled(p["prev"])
+            ops.check(ops.lib().tav_scatter_add_rows(ops.ptr(d), ops.ptr(idx), ops.ptr(table), rows, W, p["ntable"], ops.stream()), "scatter_add_rows")
+            _fx(rs, f"scatter_add[rows{rows},W{W}]", table, FR.scatter_ref(p)["dtable"])
+    return rs
+
+
+def check_index_copies_fp64():
+    """mask_to_index at n = 255, 256, 257, 1568 with nkeep = 1 and nkeep = n, both keep values, a row without a kept token; gather_rows and
+    patchify on spread data with indices past both ends (clamped): every one a copy with one right answer."""
+    rs = []
+    rng = np.random.default_rng(5)
+    for n in (255, 256, 257, 1568):
+        mask = (rng.random((3, n)) < 0.4).astype(np.uint8)
+        mask[2] = 0
+        mask[0, -1] = 1
+        for keep in (1, 0):
+            for nkeep in (1, n):
+                idx, counts = ops.mask_to_index(_ints_dev(mask, torch.uint8), keep, nkeep)
+                wi, wc = FR.mask_to_index_ref(mask, keep, nkeep)
+                rs += [_exact(f"mask_to_index[n{n},keep{keep},nkeep{nkeep}].idx", idx, torch.from_numpy(wi).to(DEV)),
+                       _exact(f"mask_to_index[n{n},keep{keep},nkeep{nkeep}].counts", counts, torch.from_numpy(wc).to(DEV))]
+    table = FR.gp_inputs(1, 37, 260, "f32")[0]
+    gi = np.concatenate([rng.integers(0, 37, size=300), [-3, 37, 1 << 20, 0, 36]]).astype(np.int32)
+    _fx(rs, "gather_rows", ops.gather_rows(_dev(table, _F32), _ints_dev(gi, torch.int32)), FR.gather_ref(table, gi))
+    video = FR.f32(rng.standard_normal((2, 4, 3, 32, 48)) * 2.0 ** (np.arange(48) % 7 - 3.0))
+    keep = np.array([[0, 5, 11, 3], [7, 1 << 20, -1, 6]], dtype=np.int32)
+    for dt in ("f32", "bf16"):
+        got = ops.patchify(_dev(video, _F32), _ints_dev(keep, torch.int32), _TDT[dt])
+        _fx(rs, f"patchify[{dt}]", got, FR.held(FR.patchify_ref(video, keep), dt), _TDT[dt])
+    return rs
+
+
+def front_fp64_checks():
+    """The front-end, pooling, head, loss and index cases against fp64, in the order all_checks() appends them."""
+    out = []
+    for dt_ in ("f32", "bf16"):
+        out.append(lambda d=dt_: check_conv0_fwd_fp64(d))
+        for Cs in ((8, 64), (512, 520)):
+            out.append(lambda d=dt_, c=Cs: check_conv0_bwd_fp64(d, c))
+        out.append(lambda d=dt_: check_col2im_fp64(d))
+        out.append(lambda d=dt_: check_colsum_fp64(d))
+    for shape in ((8, 4, 3), (256, 64, 128), (260, 4, 1), (1024, 256, 4)):
+        out.append(lambda s=shape: check_weight_norm_fp64(*s))
+    out += [lambda: check_weight_norm_fp64(768, 48, 128, "f"), lambda: check_weight_norm_fp64(768, 48, 128, "b")]
+    out += [check_group_pad_fp64, check_gelu_tanh_fp64, check_mean_pool_fp64, check_head_fp64, check_cross_entropy_fp64, check_text_index_fp64,
+            check_embed_add_fp64, check_scatter_add_fp64, check_index_copies_fp64]
+    return out
+
+
 def all_checks():
     out = []
     for dtype in (torch.float32, torch.bfloat16):
@@ -2742,4 +3168,6 @@ def all_checks():
     out += attention_fp64_checks()
     # the normalisation family against fp64: per-element bounds, exact integer cases, the group norm's pivot on an atypical first row
     out += norm_fp64_checks()
+    # the audio front-end, colsum, the GELU pair, pools, head, tanh, cross entropy and the index kernels against fp64
+    out += front_fp64_checks()
     return out
