@@ -106,6 +106,15 @@ TAV_DEV uint2 lds_read_tr16(const char* p) {
     s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(p));
     return __builtin_bit_cast(uint2, v);
 }
+// The same read through an LDS pointer: `p + constant` lands in the instruction's 16-bit offset field, no address arithmetic per read.
+// Two of them make one bf16 k-strided operand (rows r .. and r + 16 ..), returned as the MFMA's own vector type: a fragment that stays
+// in registers from one K-tile body to the next is then one 128-bit value to the compiler and not four scalars it has to put together again.
+typedef __attribute__((address_space(3))) const char lds_cchar;
+TAV_DEV bf16x8_t lds_read_tr16_pair(lds_cchar* lo, lds_cchar* hi) {
+    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(lo));
+    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(hi));
+    return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
 
 // k-strided operand fragment from a "natural" LDS tile: tile[krow][col] with `pitch` bytes per row.
 // Returns, for lane (g, i), the PK/… values {tile[k][col0 + i]} over this lane group's k-set (see header).

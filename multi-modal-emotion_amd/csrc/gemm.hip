@@ -726,10 +726,13 @@ TAV_DEV void gemm_tn_big_body(const GemmTN& p, const int tile, const int split) 
     const unsigned strideA = (unsigned)(KT * p.lda * ES), strideB = (unsigned)(KT * p.ldb * ES);
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr(smem) + wave * 8 * ROWB);
     // LDS: FIVE 32 KB images (two [64][128] sub-images each) -- three dY slots and two X slots (the NT kernel's ring, see R25 there):
-    // dY(kt+2) is issued while tile kt is multiplied, X(kt+1) goes out first in the iteration.
-    constexpr int NSA = 3;
-    constexpr int IMG = 2 * SUB;                            // one operand's K-tile image (halves 0 / 1)
-    constexpr int OFF_B = NSA * IMG;                        // X images behind the dY images
+    // dY(kt+2) is issued while K-step 0 of tile kt is multiplied, X(kt+2) behind the barrier inside its K-step 1, which ends the reads of
+    // X(kt)'s slot.  The sub-images are ordered [operand][half][slot]:
+    // the ring slots of the half a wave reads lie SUB apart, so slot, K-step and 16-row offsets of a fragment read all fit the 16-bit offset
+    // field of ds_read (dY: at most 2 * 16 KB + 12 KB).
+    constexpr int NSA = 3, NSB = 2;
+    constexpr int HALF_A = NSA * SUB, HALF_B = NSB * SUB;   // distance of an operand's halves 0 / 1
+    constexpr int OFF_B = 2 * HALF_A;                       // X images behind the dY images
     // ragged last K-tile of one operand: ordinary loads, zero fill (block-uniform condition at the call sites)
     auto stage_ragged = [&](int kt, int slot, bool is_b) {
 #pragma unroll 1
@@ -742,12 +745,12 @@ TAV_DEV void gemm_tn_big_body(const GemmTN& p, const int tile, const int split) 
             uint4 v = make_uint4(0, 0, 0, 0);
             if (!is_b) { if (ok && c < a_cmax) v = *reinterpret_cast<const uint4*>(p.A + (grow * p.lda + n1_0) * ES + c * 16); }
             else { if (ok && c < b_cmax) v = *reinterpret_cast<const uint4*>(p.B + (grow * p.ldb + n2_0) * ES + c * 16); }
-            *reinterpret_cast<uint4*>(smem + (is_b ? OFF_B : 0) + slot * IMG + h * SUB + trow * ROWB + lslot * 16) = v;
+            *reinterpret_cast<uint4*>(smem + (is_b ? OFF_B + h * HALF_B : h * HALF_A) + slot * SUB + trow * ROWB + lslot * 16) = v;
         }
     };
     // piece pc (0..3 = [half][instruction]) of an operand's K-tile image by LDS-DMA
-    auto piece_a = [&](int pc, unsigned ka, int slot) { glds16_m0(Ab0 + ka, offA[pc >> 1][pc & 1], lds0 + slot * IMG + (pc >> 1) * SUB + (pc & 1) * 1024); };
-    auto piece_b = [&](int pc, unsigned kb, int slot) { glds16_m0(Bb0 + kb, offB[pc >> 1][pc & 1], lds0 + OFF_B + slot * IMG + (pc >> 1) * SUB + (pc & 1) * 1024); };
+    auto piece_a = [&](int pc, unsigned ka, int slot) { glds16_m0(Ab0 + ka, offA[pc >> 1][pc & 1], lds0 + (pc >> 1) * HALF_A + slot * SUB + (pc & 1) * 1024); };
+    auto piece_b = [&](int pc, unsigned kb, int slot) { glds16_m0(Bb0 + kb, offB[pc >> 1][pc & 1], lds0 + OFF_B + (pc >> 1) * HALF_B + slot * SUB + (pc & 1) * 1024); };
     const bool last_ragged = nk > 0 && nk * KT > nrows;     // only the last K-tile can be short
     auto is_dma = [&](int kt) { return kt < nk && !(last_ragged && kt == nk - 1); };
     auto stage_a = [&](int kt, int slot) {                  // whole image, up front (prologue / ragged tile)
@@ -771,75 +774,149 @@ TAV_DEV void gemm_tn_big_body(const GemmTN& p, const int tile, const int split) 
     const bool do_bias = p.bias_part != nullptr && (p.bias_spread || t2 == 0);
     const int bias_mod = p.bias_spread ? p.tiles_2 : 1, bias_rem = p.bias_spread ? t2 : 0;
     f32x4 bacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};      // (see ones_frag: w2 = 0 / 1 take two dY fragments each)
-    const uint4 ones = ones_frag<T>();
+    const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, ones_frag<T>());
 
-    // The DMA pieces of later K-tiles (8 per wave and iteration) are issued between the MFMA groups of the first K-step: back to back right
-    // after the barrier they cost every wave of the CU ~1000 cycles of issue time at the same moment, with nothing on the matrix pipe.
-    // Iteration kt issues X(kt+1) and dY(kt+2); issue order X then dY, so at the next wait the 4 youngest pieces are dY's and may stay
-    // in flight.
-    // One K-tile, compiled three times like the NT kernel's ktile25 (ISSUE_B: X(kt+1) is a whole tile and goes out by DMA, ISSUE_A: so does
-    // dY(kt+2); TAIL: one of them may be the ragged last tile, staged through registers right after the barrier).  The steady body
-    // <true, true, false> decides nothing at run time but the bias MFMAs.  K-step 1's fragments are requested while K-step 0 is multiplied:
-    // X fragment b right after the MFMA group that was the last reader of K-step 0's, the four dY fragments (16 registers of their own)
-    // after the fourth group -- the second K-step starts with its reads landed or in flight instead of with an empty matrix pipe.
+    // The DMA pieces of later K-tiles (8 per wave and steady iteration) are issued between the MFMA groups: back to back right after the
+    // barrier they cost every wave of the CU ~1000 cycles of issue time at the same moment, with nothing on the matrix pipe.  The steady
+    // iteration kt issues dY(kt+2) in its K-step 0 and X(kt+2) in its K-step 1, behind its barrier (below); the prologue issues dY(0), X(0),
+    // dY(1), X(1).  At every wait the youngest pieces belong to later tiles and may stay in flight.
+    // One K-tile, compiled three times like the NT kernel's ktile25: steady <IB, IA> (tile kt+2 is whole, both its images go out by DMA),
+    // penultimate <IB> and last <>; the two TAIL bodies issue no DMA, one of the tiles behind theirs may be the ragged last tile, staged
+    // through registers right after their barrier.  The steady body decides nothing at run time but the bias MFMAs.  K-step 1's fragments
+    // are requested while K-step 0 is multiplied: X fragment b right after the MFMA group that was the last reader of K-step 0's, the four
+    // dY fragments (16 registers of their own) after the fourth group -- the second K-step starts with its reads landed or in flight.
     // bias_cnt: K-tiles until the next one whose column sums this tile takes (kt % bias_mod == bias_rem without the division).
-    int ca = 0, cb = 0, bias_cnt = bias_rem;
-    auto ktile = [&](int kt, auto issue_b, auto issue_a, auto tail) {
+    // Fragment addresses (tn_frag<bf16>'s, split into a lane part and a constant): the lane reads token row r = 4g + q (+ K-step, + 16) of
+    // feature chunk (2c | p >> 1) ^ ((r & 7) << 1), c = the fragment's 16-column index in its sub-image.  The XOR term does not depend on the
+    // K-step or the 16-row half (both multiples of 8 rows) but it does on c, so one lane address per fragment column -- 4 for dY, 8 for X,
+    // constant for the whole kernel, the wave's half included -- and slot, K-step and row half are constants in the instruction.  The steady
+    // body is compiled once per slot phase (3 dY x 2 X slots: period 6) for that; the two tail bodies take the slots at run time.
+    lds_cchar* fa[4];
+    lds_cchar* fb[8];
+    {
+        const int r = 4 * g + (i >> 2), pp = i & 3;
+        lds_cchar* const l0 = (lds_cchar*)smem + r * ROWB + ((pp >> 1) << 4) + (pp & 1) * 8;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) fa[t] = l0 + (w1 >> 1) * HALF_A + ((((w1 & 1) * 4 + t) ^ (r & 7)) << 5);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) fb[t] = l0 + OFF_B + w2 * HALF_B + ((t ^ (r & 7)) << 5);
+    }
+    auto frag = [&](lds_cchar* base, int off) { return lds_read_tr16_pair(base + off, base + off + 16 * ROWB); };
+    auto mma = [&](const bf16x8_t& a, const bf16x8_t& b, f32x4& c) { c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); };
+    // K-step 0 of tile kt+1 under K-step 1 of tile kt: the steady body is entered with its tile's images landed, the workgroup past the
+    // barrier that says so, and its K-step-0 fragments requested into f1 / f2 -- by the hand-in below for tile 0, by the steady body before
+    // it otherwise, which waits and meets the barrier after MFMA group NEXT_AT of its K-step 1 and then requests X fragment b of the next
+    // tile after group b (its registers are free from there on) and the dY fragments into f1 (dead since K-step 0's bias MFMAs).  The same
+    // barrier frees the X slot of tile kt, so X(kt+2) goes out right behind it, a whole K-tile time before its own wait (issued in K-step 0
+    // of body kt+1 it has half a K-tile and the wait stalls: 4-8 % slower than no overlap at all, profiles/tn_ladder.txt section 2).  The
+    // penultimate and last bodies begin with their own wait, barrier and reads as before; the last steady body's requests for the
+    // penultimate tile are made again there (24 reads per workgroup) so that no fragment register is live into the tail bodies.
+    constexpr int NEXT_AT = 1;
+    bf16x8_t f1[4], f2[8], g1[4];
+    int bias_cnt = bias_rem;
+    auto ktile = [&](int kt, auto issue_b, auto issue_a, auto tail, auto slot_a, auto slot_b) __attribute__((always_inline)) {
         constexpr bool IB = decltype(issue_b)::value, IA = decltype(issue_a)::value, TAIL = decltype(tail)::value;
-        if constexpr (IB) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");          // dY(kt+1) was issued after X(kt): it may still fly
-        else wait_vmcnt0();
-        __syncthreads();
+        const int ca = slot_a, cb = slot_b;                     // (std::integral_constant in the steady body)
         const int na = ca == 0 ? 2 : ca - 1, nb = cb ^ 1;      // slots of dY(kt + 2), X(kt + 1)
+        const int oa = ca * SUB, ob = cb * SUB;
+        if constexpr (!IA) {
+            if constexpr (IB) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // dY(kt+1) and X(kt+1) were issued after tile kt's: they may fly
+            else wait_vmcnt0();
+            __syncthreads();
+        }
         if constexpr (TAIL) {                                   // (block-uniform; at most once per operand and workgroup)
             if (last_ragged && kt + 1 == nk - 1) stage_ragged(kt + 1, nb, true);
             if (last_ragged && kt + 2 == nk - 1) stage_ragged(kt + 2, na, false);
         }
-        const unsigned ka = (unsigned)(kt + 2) * strideA, kb = (unsigned)(kt + 1) * strideB;
-        const char* cA = smem + ca * IMG + (w1 >> 1) * SUB;
-        const char* cB = smem + OFF_B + cb * IMG + w2 * SUB;
+        const unsigned ka = (unsigned)(kt + 2) * strideA, kb = (unsigned)(kt + 2) * strideB;
         const bool bias_now = do_bias && bias_cnt == 0;
-        uint4 f1[4], f2[8], g1[4];
+        if constexpr (!IA) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) f1[t] = tn_frag<T>(cA, 0, (w1 & 1) * 64 + t * 16, lane);
+            for (int t = 0; t < 4; ++t) f1[t] = frag(fa[t], oa);
 #pragma unroll
-        for (int t = 0; t < 8; ++t) f2[t] = tn_frag<T>(cB, 0, t * 16, lane);
+            for (int t = 0; t < 8; ++t) f2[t] = frag(fb[t], ob);
+        }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
 #pragma unroll
-            for (int a = 0; a < 4; ++a) mma16<T>(f2[b], f1[a], acc[a][b]);       // rows(regs) = n2, cols(lanes) = n1
+            for (int a = 0; a < 4; ++a) mma(f2[b], f1[a], acc[a][b]);       // rows(regs) = n2, cols(lanes) = n1
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (IB) { if (b < 4) piece_b(b, kb, nb); }
             if constexpr (IA) { if (b >= 4) piece_a(b - 4, ka, na); }
-            f2[b] = tn_frag<T>(cB, KSTEP, b * 16, lane);
+            f2[b] = frag(fb[b], ob + KSTEP * ROWB);
             if (b == 3) {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) g1[t] = tn_frag<T>(cA, KSTEP, (w1 & 1) * 64 + t * 16, lane);
+                for (int t = 0; t < 4; ++t) g1[t] = frag(fa[t], oa + KSTEP * ROWB);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
         if (bias_now) {
-            if (w2 == 0) { mma16<T>(ones, f1[0], bacc[0]); mma16<T>(ones, f1[1], bacc[1]); }
-            else { mma16<T>(ones, f1[2], bacc[0]); mma16<T>(ones, f1[3], bacc[1]); }
+            if (w2 == 0) { mma(ones, f1[0], bacc[0]); mma(ones, f1[1], bacc[1]); }
+            else { mma(ones, f1[2], bacc[0]); mma(ones, f1[3], bacc[1]); }
         }
 #pragma unroll
-        for (int b = 0; b < 8; ++b)
+        for (int b = 0; b < 8; ++b) {
 #pragma unroll
-            for (int a = 0; a < 4; ++a) mma16<T>(f2[b], g1[a], acc[a][b]);
+            for (int a = 0; a < 4; ++a) mma(f2[b], g1[a], acc[a][b]);
+            if constexpr (IA) if (b >= NEXT_AT) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (b == NEXT_AT) {
+                    // Tile kt+1's images: this wave's DMA pieces in flight are, oldest first, dY(kt+1) (K-step 0 of body kt-1, or the
+                    // prologue), X(kt+1) (K-step 1 of body kt-1, or the prologue) and dY(kt+2) (K-step 0 of this body) -- vmcnt retires in
+                    // order, the four youngest may fly.
+                    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                    // Ring invariant at this barrier, B(kt).  __syncthreads() waits for the wave's own LDS reads (lgkmcnt(0)) first, so every
+                    // read a wave issued before B(kt) has returned when any wave is past it.  Every read of tile kt's slots is issued
+                    // before B(kt) -- K-step 0's behind B(kt-1) (or in the hand-in), K-step 1's in K-step 0 of this body -- and behind
+                    // B(kt) a wave reads only tile kt+1's slots until B(kt+1).  A slot is refilled only behind the barrier that ends its
+                    // tile's reads: X(kt+2) into X(kt)'s slot right behind B(kt), below; dY(kt+3) into dY(kt)'s slot in K-step 0 of body
+                    // kt+1, behind B(kt) as well; a ragged tile's stores behind a tail body's own barrier, which follows B(kt).  What this
+                    // body issued before B(kt), dY(kt+2) into dY(kt-1)'s slot, lay behind B(kt-1) in the same way.
+                    __syncthreads();
+                    constexpr int pa = ((decltype(slot_a)::value + 1) % 3) * SUB, pb = (decltype(slot_b)::value ^ 1) * SUB;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) f1[t] = frag(fa[t], pa);
+#pragma unroll
+                    for (int t = 0; t <= NEXT_AT; ++t) f2[t] = frag(fb[t], pb);
+                } else {
+                    if (b - NEXT_AT - 1 < 4) piece_b(b - NEXT_AT - 1, kb, cb);
+                    f2[b] = frag(fb[b], (decltype(slot_b)::value ^ 1) * SUB);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
         if (bias_now) {
-            if (w2 == 0) { mma16<T>(ones, g1[0], bacc[0]); mma16<T>(ones, g1[1], bacc[1]); }
-            else { mma16<T>(ones, g1[2], bacc[0]); mma16<T>(ones, g1[3], bacc[1]); }
+            if (w2 == 0) { mma(ones, g1[0], bacc[0]); mma(ones, g1[1], bacc[1]); }
+            else { mma(ones, g1[2], bacc[0]); mma(ones, g1[3], bacc[1]); }
         }
-        ca = ca == 2 ? 0 : ca + 1;
-        cb ^= 1;
         bias_cnt = bias_cnt == 0 ? bias_mod - 1 : bias_cnt - 1;
     };
-    if (nk > 0) { stage_a(0, 0); stage_b(0, 0); if (nk > 1) stage_a(1, 1); }
     const int nd = last_ragged ? nk - 1 : nk;               // whole K-tiles: 0 .. nd-1 go by DMA
+    if (nk > 0) { stage_a(0, 0); stage_b(0, 0); if (nk > 1) stage_a(1, 1); if (nd > 1) stage_b(1, 1); }
+    const int ns = nd - 2;                                  // steady tiles: 0 .. ns-1 (tile kt + 2 is whole); tile kt in slots kt % 3 (dY), kt % 2 (X)
     int kt = 0;
-    for (; kt + 2 < nd; ++kt) ktile(kt, std::true_type{}, std::true_type{}, std::false_type{});
-    if (kt + 1 < nd) { ktile(kt, std::true_type{}, std::false_type{}, std::true_type{}); ++kt; }
-    for (; kt < nk; ++kt) ktile(kt, std::false_type{}, std::false_type{}, std::true_type{});
+    if (ns > 0) {                                           // dY(0), X(0), dY(1), X(1) went out by DMA in that order: the steady loop's hand-in
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) f1[t] = frag(fa[t], 0);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) f2[t] = frag(fb[t], 0);
+    }
+    if (ns > 0) {
+        const auto steady = [&](auto sa, auto sb) __attribute__((always_inline)) { ktile(kt, std::true_type{}, std::true_type{}, std::false_type{}, sa, sb); return ++kt == ns; };
+        using std::integral_constant;
+        for (;;) {
+            if (steady(integral_constant<int, 0>{}, integral_constant<int, 0>{})) break;
+            if (steady(integral_constant<int, 1>{}, integral_constant<int, 1>{})) break;
+            if (steady(integral_constant<int, 2>{}, integral_constant<int, 0>{})) break;
+            if (steady(integral_constant<int, 0>{}, integral_constant<int, 1>{})) break;
+            if (steady(integral_constant<int, 1>{}, integral_constant<int, 0>{})) break;
+            if (steady(integral_constant<int, 2>{}, integral_constant<int, 1>{})) break;
+        }
+    }
+    if (kt + 1 < nd) { ktile(kt, std::true_type{}, std::false_type{}, std::true_type{}, kt % 3, kt & 1); ++kt; }
+    for (; kt < nk; ++kt) ktile(kt, std::false_type{}, std::false_type{}, std::true_type{}, kt % 3, kt & 1);
     __syncthreads();
 
     if (do_bias && g == 0) {
