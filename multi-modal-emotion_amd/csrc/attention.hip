@@ -26,6 +26,8 @@
 // per SIMD; without it the kernel fits three at 165 and is 4-9 % faster) and measured -1 % in the two backward kernels.
 
 namespace tav {
+// defined with the host decisions (entry_plan.h)
+using plan::ATT_FWD_NQ;
 
 struct AttnP {
     const char* q; const char* k; const char* v; char* o; char* o_soft;
@@ -245,7 +247,6 @@ constexpr float ATT_LAZY_THR = 12.0f;
 //     accumulators come out as s - m and p = exp2(acc): no fma per score;
 //   * O / l are rescaled only when the tile maximum passes the reference by ATT_LAZY_THR (rare after the first tile);
 //   * ring slot, LDS addresses and the DMA source walk are compile-time / scalar: the loop body is instantiated once per slot.
-constexpr int ATT_FWD_NQ = 2;        // 16-query tiles per wave: 32 queries per wave, 128 per workgroup
 template <typename T, int MODE, bool PRE, bool LEN = false>
 __global__ __launch_bounds__(256, ATT_FWD_OCC) void attn_fwd_kernel(const AttnArg<LEN> p) {
     constexpr int NQ = ATT_FWD_NQ;
@@ -1150,30 +1151,18 @@ __global__ void head_scale_kernel(const T* __restrict__ a, const T* __restrict__
     st4(out + row * ldo + 4 * col4, v);
 }
 
-static int check(const tav_attn_args* a, bool bwd) {
-    if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse) return TAV_ERR_NULL;
-    if (a->B <= 0 || a->S <= 0 || a->nheads <= 0) return TAV_ERR_SHAPE;
-    if (((a->S + 63) / 64) * a->nheads * a->B >= (1ll << 31)) return TAV_ERR_SHAPE;      // the grid is one-dimensional (attn_tile)
-    if (a->dtype != TAV_BF16 && a->dtype != TAV_F32) return TAV_ERR_DTYPE;
-    if (a->mask_mode < 0 || a->mask_mode > 2) return TAV_ERR_SHAPE;
-    if (a->mask_mode != 0 && !a->key_mask) return TAV_ERR_NULL;
-    if (a->mask_mode == 2 && (!a->corr || !a->o_soft)) return TAV_ERR_NULL;
-    const int pk = a->dtype == TAV_BF16 ? 8 : 4;
-    if (a->ld_q % pk || a->ld_k % pk || a->ld_v % pk || a->ld_o % 4) return TAV_ERR_ALIGN;
-    if (a->ld_q < a->nheads * 64 || a->ld_k < a->nheads * 64 || a->ld_v < a->nheads * 64 || a->ld_o < a->nheads * 64) return TAV_ERR_SHAPE;
-    {   // the streamed tiles are addressed with 32-bit byte offsets inside one batch entry's slice
-        const int64_t es = a->dtype == TAV_BF16 ? 2 : 4;
-        int64_t ld = a->ld_q > a->ld_k ? a->ld_q : a->ld_k;
-        ld = ld > a->ld_v ? ld : a->ld_v;
-        if (bwd && a->ld_do > ld) ld = a->ld_do;
-        if ((a->S + 64) * ld * es >= (1ll << 32)) return TAV_ERR_SHAPE;
-    }
-    if (bwd) {
-        if (!a->dout || !a->dq || !a->dk || !a->dv || !a->delta) return TAV_ERR_NULL;
-        if (a->ld_do % pk || a->ld_dq % 4 || a->ld_dk % 4 || a->ld_dv % 4) return TAV_ERR_ALIGN;
-    }
-    return 0;
+// entry_plan.h states the LDS sizes without HD<T>
+static_assert(fwd_lds<bf16>() == plan::attn_fwd_lds(2) && fwd_lds<float>() == plan::attn_fwd_lds(4) && dq_lds<bf16>() == plan::attn_dq_lds(2) &&
+              dq_lds<float>() == plan::attn_dq_lds(4), "entry_plan.h mirrors these");
+template <typename T, int MODE, bool PRE> constexpr bool dkdv_mirrored() {
+    return dkdv_bq<T, MODE, PRE>() == plan::attn_dkdv_bq(sizeof(T), MODE, PRE) && dkdv_lds<T, MODE, PRE>() == plan::attn_dkdv_lds(sizeof(T), MODE, PRE);
 }
+template <typename T> constexpr bool dkdv_mirrored_all() {
+    return dkdv_mirrored<T, 0, false>() && dkdv_mirrored<T, 0, true>() && dkdv_mirrored<T, 1, false>() && dkdv_mirrored<T, 1, true>() && dkdv_mirrored<T, 2, false>() &&
+           dkdv_mirrored<T, 2, true>();
+}
+static_assert(dkdv_mirrored_all<bf16>() && dkdv_mirrored_all<float>(), "entry_plan.h mirrors these");
+
 static AttnP pack(const tav_attn_args* a) {
     AttnP p;
     p.q = (const char*)a->q; p.k = (const char*)a->k; p.v = (const char*)a->v; p.o = (char*)a->o; p.o_soft = (char*)a->o_soft;
@@ -1188,106 +1177,70 @@ static AttnP pack(const tav_attn_args* a) {
     return p;
 }
 
-template <typename T, int MODE, bool PRE, bool LEN> static int launch_fwd(const AttnArg<LEN>& p, hipStream_t st) {
-    constexpr int QW = 64 * ATT_FWD_NQ;                      // queries per workgroup
-    AttnArg<LEN> pl = p; pl.tiles = (p.S + QW - 1) / QW;
-    hipLaunchKernelGGL((attn_fwd_kernel<T, MODE, PRE, LEN>), dim3((unsigned)pl.tiles * p.nh * p.B), dim3(256), fwd_lds<T>(), st, pl);
-    return (int)hipGetLastError();
+template <typename T, int MODE, bool PRE, bool LEN> static int launch_fwd(const tav_attn_args* a, const AttnArg<LEN>& p, hipStream_t st) {
+    AttnArg<LEN> pl = p; pl.tiles = plan::attn_tiles(a->S, false);
+    TAV_LAUNCH((attn_fwd_kernel<T, MODE, PRE, LEN>), plan::attn_launch(a, false, fwd_lds<T>()), st, pl);
+    return 0;
 }
 // (length-aware launches keep the grid of the padded problem, sized by S: workgroups past L_b zero their rows and leave)
-template <typename T, int MODE, bool PRE, bool LEN> static int launch_bwd(const AttnArg<LEN>& p, hipStream_t st) {
-    AttnArg<LEN> pl = p; pl.tiles = (p.S + 127) / 128;
-    const dim3 grid((unsigned)pl.tiles * p.nh * p.B);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, MODE, PRE, LEN>), grid, dim3(256), dq_lds<T>(), st, pl);        // also writes delta [B][nh][S]
-    constexpr size_t lds_dkdv = dkdv_lds<T, MODE, PRE>();
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, MODE, PRE, LEN>), grid, dim3(256), lds_dkdv, st, pl);    // reads it
-    return (int)hipGetLastError();
+template <typename T, int MODE, bool PRE, bool LEN> static int launch_bwd(const tav_attn_args* a, const AttnArg<LEN>& p, hipStream_t st) {
+    AttnArg<LEN> pl = p; pl.tiles = plan::attn_tiles(a->S, true);
+    TAV_LAUNCH((attn_bwd_dq_kernel<T, MODE, PRE, LEN>), plan::attn_launch(a, true, dq_lds<T>()), st, pl);        // also writes delta [B][nh][S]
+    TAV_LAUNCH((attn_bwd_dkdv_kernel<T, MODE, PRE, LEN>), plan::attn_launch(a, true, dkdv_lds<T, MODE, PRE>()), st, pl);    // reads it
+    return 0;
 }
-template <typename T, bool PRE, bool LEN> static int dispatch_fwd(const AttnArg<LEN>& p, int mode, hipStream_t st) {
-    switch (mode) {
-        case 0: return launch_fwd<T, 0, PRE, LEN>(p, st);
-        case 1: return launch_fwd<T, 1, PRE, LEN>(p, st);
-        default: return launch_fwd<T, 2, PRE, LEN>(p, st);
+// one of the 24 (48) kernels of a direction: element type x mask mode x pre-scaled q x length-aware
+template <bool BWD, typename T, bool PRE, bool LEN> static int dispatch_mode(const tav_attn_args* a, const AttnArg<LEN>& p, hipStream_t st) {
+    if constexpr (BWD) {
+        switch (a->mask_mode) {
+            case 0: return launch_bwd<T, 0, PRE, LEN>(a, p, st);
+            case 1: return launch_bwd<T, 1, PRE, LEN>(a, p, st);
+            default: return launch_bwd<T, 2, PRE, LEN>(a, p, st);
+        }
+    } else {
+        switch (a->mask_mode) {
+            case 0: return launch_fwd<T, 0, PRE, LEN>(a, p, st);
+            case 1: return launch_fwd<T, 1, PRE, LEN>(a, p, st);
+            default: return launch_fwd<T, 2, PRE, LEN>(a, p, st);
+        }
     }
 }
-template <typename T, bool PRE, bool LEN> static int dispatch_bwd(const AttnArg<LEN>& p, int mode, hipStream_t st) {
-    switch (mode) {
-        case 0: return launch_bwd<T, 0, PRE, LEN>(p, st);
-        case 1: return launch_bwd<T, 1, PRE, LEN>(p, st);
-        default: return launch_bwd<T, 2, PRE, LEN>(p, st);
-    }
-}
-template <bool LEN> static int run_fwd(const tav_attn_args* a, const int32_t* seq_lens, hipStream_t st) {
+template <bool BWD, bool LEN> static int run(const tav_attn_args* a, const int32_t* seq_lens, void* stream) {
+    if (const int rc = plan::attn_validate(a, BWD ? plan::ATTN_BWD : plan::ATTN_FWD, !LEN || seq_lens)) return rc;
     AttnArg<LEN> p;
     static_cast<AttnP&>(p) = pack(a);
     if constexpr (LEN) p.lens = seq_lens;
-    if (a->dtype == TAV_BF16) return p.pre ? dispatch_fwd<bf16, true, LEN>(p, a->mask_mode, st) : dispatch_fwd<bf16, false, LEN>(p, a->mask_mode, st);
-    return p.pre ? dispatch_fwd<float, true, LEN>(p, a->mask_mode, st) : dispatch_fwd<float, false, LEN>(p, a->mask_mode, st);
-}
-template <bool LEN> static int run_bwd(const tav_attn_args* a, const int32_t* seq_lens, hipStream_t st) {
-    AttnArg<LEN> p;
-    static_cast<AttnP&>(p) = pack(a);
-    if constexpr (LEN) p.lens = seq_lens;
-    if (a->dtype == TAV_BF16) return p.pre ? dispatch_bwd<bf16, true, LEN>(p, a->mask_mode, st) : dispatch_bwd<bf16, false, LEN>(p, a->mask_mode, st);
-    return p.pre ? dispatch_bwd<float, true, LEN>(p, a->mask_mode, st) : dispatch_bwd<float, false, LEN>(p, a->mask_mode, st);
+    return floats::dispatch(a->dtype, [&](auto t) {
+        using T = decltype(t);
+        return p.pre ? dispatch_mode<BWD, T, true, LEN>(a, p, (hipStream_t)stream) : dispatch_mode<BWD, T, false, LEN>(a, p, (hipStream_t)stream);
+    });
 }
 
 }  // namespace tav
 
 using namespace tav;
 
-extern "C" int tav_attn_fwd(const tav_attn_args* a, void* stream) {
-    int e = check(a, false);
-    if (e) return e;
-    return run_fwd<false>(a, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int tav_attn_bwd(const tav_attn_args* a, void* stream) {
-    int e = check(a, true);
-    if (e) return e;
-    return run_bwd<false>(a, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int tav_attn_fwd_len(const tav_attn_args* a, const int32_t* seq_lens, void* stream) {
-    int e = check(a, false);
-    if (e) return e;
-    if (!seq_lens) return TAV_ERR_NULL;
-    return run_fwd<true>(a, seq_lens, (hipStream_t)stream);
-}
-
-extern "C" int tav_attn_bwd_len(const tav_attn_args* a, const int32_t* seq_lens, void* stream) {
-    int e = check(a, true);
-    if (e) return e;
-    if (!seq_lens) return TAV_ERR_NULL;
-    return run_bwd<true>(a, seq_lens, (hipStream_t)stream);
-}
+extern "C" int tav_attn_fwd(const tav_attn_args* a, void* stream) { return run<false, false>(a, nullptr, stream); }
+extern "C" int tav_attn_bwd(const tav_attn_args* a, void* stream) { return run<true, false>(a, nullptr, stream); }
+extern "C" int tav_attn_fwd_len(const tav_attn_args* a, const int32_t* seq_lens, void* stream) { return run<false, true>(a, seq_lens, stream); }
+extern "C" int tav_attn_bwd_len(const tav_attn_args* a, const int32_t* seq_lens, void* stream) { return run<true, true>(a, seq_lens, stream); }
 
 extern "C" int tav_attn_probs(const tav_attn_args* a, float* probs, const float* head_scale, int64_t hs_bstride, void* stream) {
-    if (!a || !a->q || !a->k || !a->lse || !probs) return TAV_ERR_NULL;
-    if (a->B <= 0 || a->S <= 0 || a->nheads <= 0 || hs_bstride < 0) return TAV_ERR_SHAPE;
-    if (a->dtype != TAV_BF16 && a->dtype != TAV_F32) return TAV_ERR_DTYPE;
-    if (a->mask_mode < 0 || a->mask_mode > 2) return TAV_ERR_SHAPE;
-    if (a->mask_mode != 0 && !a->key_mask) return TAV_ERR_NULL;
-    const int pk = a->dtype == TAV_BF16 ? 8 : 4;
-    if (a->ld_q % pk || a->ld_k % pk) return TAV_ERR_ALIGN;
+    if (const int rc = plan::attn_validate(a, plan::ATTN_PROBS, probs, hs_bstride)) return rc;
     const AttnP p = pack(a);
-    const long rows = (long)p.B * p.nh * p.S;
-    hipStream_t st = (hipStream_t)stream;
-    if (a->dtype == TAV_BF16) hipLaunchKernelGGL((attn_probs_kernel<bf16>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p, probs, head_scale, (int)hs_bstride, (int)a->mask_mode);
-    else hipLaunchKernelGGL((attn_probs_kernel<float>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p, probs, head_scale, (int)hs_bstride, (int)a->mask_mode);
-    return (int)hipGetLastError();
+    return floats::dispatch(a->dtype, [&](auto t) {
+        TAV_LAUNCH((attn_probs_kernel<decltype(t)>), plan::attn_probs_launch(a), stream, p, probs, head_scale, (int)hs_bstride, (int)a->mask_mode);
+        return 0;
+    });
 }
 
 extern "C" int tav_head_scale(const void* a, const void* b, void* out, int32_t dtype, const float* head_scale, int64_t hs_bstride, float c0, int64_t B,
                               int64_t S, int64_t nheads, int64_t lda, int64_t ldb, int64_t ldo, void* stream) {
-    if (!b || !out) return TAV_ERR_NULL;
-    if (B <= 0 || S <= 0 || nheads <= 0 || hs_bstride < 0) return TAV_ERR_SHAPE;
-    if (dtype != TAV_BF16 && dtype != TAV_F32) return TAV_ERR_DTYPE;
-    if (lda % 4 || ldb % 4 || ldo % 4) return TAV_ERR_ALIGN;
+    if (const int rc = plan::head_scale_validate(b && out, dtype, hs_bstride, B, S, nheads, lda, ldb, ldo)) return rc;
     const long n4 = B * S * nheads * 16;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((n4 + 255) / 256)), block(256);
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((head_scale_kernel<bf16>), grid, block, 0, st, (const bf16*)a, (const bf16*)b, (bf16*)out, head_scale, (int)hs_bstride, c0, n4, (int)S, (int)nheads, (long)lda, (long)ldb, (long)ldo);
-    else hipLaunchKernelGGL((head_scale_kernel<float>), grid, block, 0, st, (const float*)a, (const float*)b, (float*)out, head_scale, (int)hs_bstride, c0, n4, (int)S, (int)nheads, (long)lda, (long)ldb, (long)ldo);
-    return (int)hipGetLastError();
+    return floats::dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((head_scale_kernel<T>), plan::grid1(n4), stream, (const T*)a, (const T*)b, (T*)out, head_scale, (int)hs_bstride, c0, n4, (int)S, (int)nheads, (long)lda, (long)ldb, (long)ldo);
+        return 0;
+    });
 }

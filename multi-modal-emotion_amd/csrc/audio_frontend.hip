@@ -6,10 +6,8 @@
 #include "tavhip_internal.h"
 
 namespace tav {
-
-constexpr int C0_TT = 128;     // output steps per workgroup (conv0 forward): enough stores to amortise the weight loads of the prologue
-constexpr int C0_BT = 512;     // output steps per workgroup of the conv0 weight gradient (4 time groups x 128 steps): half the partial blocks of 256 for the final reduce
-constexpr int C0_MAXK = 16;
+// defined with the host decisions (entry_plan.h)
+using plan::C0_TT, plan::C0_BT, plan::C0_MAXK;
 
 // y[b][t][c] = sum_j x[b][s*t + j] * w[c][j] + bias[c];  thread owns 4 consecutive channels {4q .. 4q+3, q = tid, tid + 256, ...} of the output
 // steps of its time group (one 8-B / 16-B store per step and thread; one channel per thread -- 2-byte stores -- wrote the 524 MB at 1.7 TB/s)
@@ -255,83 +253,72 @@ __global__ void wn_bwd_apply_kernel(const float* __restrict__ v, const float* __
 
 }  // namespace tav
 using namespace tav;
-#define ST ((hipStream_t)stream)
-#define G1(n) dim3(tav_cdiv((n), 256)), dim3(256), 0, ST
 
 extern "C" int tav_conv0_fwd(const float* wave, const float* w, const float* bias, void* y, int32_t dt, int64_t B, int64_t T_in, int64_t T_out, int64_t C,
                              int64_t K, int64_t stride, void* stream) {
-    if (!wave || !w || !y) return TAV_ERR_NULL;
-    if (B <= 0 || T_in <= 0 || T_out <= 0 || C <= 0 || C % 4 || K <= 0 || K > C0_MAXK || stride <= 0 || stride > 8) return TAV_ERR_SHAPE;
-    if ((T_out - 1) * stride + K > T_in) return TAV_ERR_SHAPE;
-    dim3 grid(tav_cdiv(T_out, C0_TT), (unsigned)B);
-    if (dt == TAV_BF16) hipLaunchKernelGGL((conv0_fwd_kernel<bf16>), grid, dim3(256), 0, ST, wave, w, bias, (bf16*)y, (int)T_in, (int)T_out, (int)C, (int)K, (int)stride);
-    else if (dt == TAV_F32) hipLaunchKernelGGL((conv0_fwd_kernel<float>), grid, dim3(256), 0, ST, wave, w, bias, (float*)y, (int)T_in, (int)T_out, (int)C, (int)K, (int)stride);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    if (const int rc = plan::conv0_fwd_validate(wave && w && y, dt, B, T_in, T_out, C, K, stride)) return rc;
+    return floats::dispatch(dt, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((conv0_fwd_kernel<T>), plan::conv0_fwd_launch(B, T_out), stream, wave, w, bias, (T*)y, (int)T_in, (int)T_out, (int)C, (int)K, (int)stride);
+        return 0;
+    });
 }
-extern "C" int tav_conv0_bwd_partials(int64_t B, int64_t T_out, int64_t C, int64_t K) { return (int)(B * ((T_out + C0_BT - 1) / C0_BT) * C * (K + 1)); }
+extern "C" int tav_conv0_bwd_partials(int64_t B, int64_t T_out, int64_t C, int64_t K) { return plan::conv0_bwd_partials(B, T_out, C, K); }
 extern "C" int tav_conv0_bwd_w(const float* wave, const void* dy, int32_t dt, float* dw, float* dbias, float* partials, int64_t B, int64_t T_in, int64_t T_out,
                                int64_t C, int64_t K, int64_t stride, int32_t accumulate, void* stream) {
-    if (!wave || !dy || !dw || !partials) return TAV_ERR_NULL;
-    if (B <= 0 || T_in <= 0 || T_out <= 0 || C <= 0 || C % 8 || K <= 0 || K > 10 || stride <= 0 || stride > 8) return TAV_ERR_SHAPE;
-    const int nchunks = (int)((T_out + C0_BT - 1) / C0_BT);
-    dim3 grid(nchunks, (unsigned)B);
-    if (dt == TAV_BF16) hipLaunchKernelGGL((conv0_bwd_w_kernel<bf16>), grid, dim3(256), 0, ST, wave, (const bf16*)dy, partials, (int)T_in, (int)T_out, (int)C, (int)K, (int)stride, nchunks);
-    else if (dt == TAV_F32) hipLaunchKernelGGL((conv0_bwd_w_kernel<float>), grid, dim3(256), 0, ST, wave, (const float*)dy, partials, (int)T_in, (int)T_out, (int)C, (int)K, (int)stride, nchunks);
-    else return TAV_ERR_DTYPE;
-    hipLaunchKernelGGL(conv0_bwd_w_final_kernel, dim3(tav_cdiv(C * (K + 1), 64)), dim3(256), 0, ST, partials, dw, dbias, nchunks * (int)B, (int)C, (int)K, accumulate);
-    return tav_last_error();
+    if (const int rc = plan::conv0_bwd_validate(wave && dy && dw && partials, dt, B, T_in, T_out, C, K, stride)) return rc;
+    const plan::Conv0BwdPlan P = plan::conv0_bwd_plan(B, T_out, C, K);
+    return floats::dispatch(dt, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((conv0_bwd_w_kernel<T>), P.partial, stream, wave, (const T*)dy, partials, (int)T_in, (int)T_out, (int)C, (int)K, (int)stride, P.chunks);
+        TAV_LAUNCH(conv0_bwd_w_final_kernel, P.final_, stream, partials, dw, dbias, P.blocks, (int)C, (int)K, accumulate);
+        return 0;
+    });
 }
 extern "C" int tav_col2im_1d(const void* dcol, void* dx, const void* pre_act, int32_t dt, int64_t B, int64_t T_in, int64_t T_out, int64_t C, int64_t K,
                              int64_t stride, void* stream) {
-    if (!dcol || !dx) return TAV_ERR_NULL;
-    if (B <= 0 || T_in <= 0 || T_out <= 0 || C <= 0 || C % 4 || K <= 0 || stride <= 0) return TAV_ERR_SHAPE;
+    if (const int rc = plan::col2im_validate(dcol && dx, dt, B, T_in, T_out, C, K, stride)) return rc;
     const long n4 = B * T_in * C / 4;
-    if (dt == TAV_BF16) hipLaunchKernelGGL((col2im_kernel<bf16>), G1(n4), (const bf16*)dcol, (bf16*)dx, (const bf16*)pre_act, n4, (int)T_in, (int)T_out, (int)C, (int)K, (int)stride);
-    else if (dt == TAV_F32) hipLaunchKernelGGL((col2im_kernel<float>), G1(n4), (const float*)dcol, (float*)dx, (const float*)pre_act, n4, (int)T_in, (int)T_out, (int)C, (int)K, (int)stride);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    return floats::dispatch(dt, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((col2im_kernel<T>), plan::grid1(n4), stream, (const T*)dcol, (T*)dx, (const T*)pre_act, n4, (int)T_in, (int)T_out, (int)C, (int)K, (int)stride);
+        return 0;
+    });
 }
 extern "C" int tav_group_pad(const void* x, int32_t sdt, void* xg, int32_t ddt, int64_t B, int64_t T, int64_t H, int64_t G, int64_t pad_l, int64_t pad_r,
                              void* stream) {
-    if (!x || !xg) return TAV_ERR_NULL;
-    if (B <= 0 || T <= 0 || H <= 0 || G <= 0 || H % G || (H / G) % 4 || pad_l < 0 || pad_r < 0) return TAV_ERR_SHAPE;
+    if (const int rc = plan::group_pad_validate(x && xg, sdt, ddt, B, T, H, G, pad_l, pad_r)) return rc;
     const int TP = (int)(pad_l + T + pad_r);
     const long n4 = B * G * TP * (H / G) / 4;
-    if (sdt == TAV_F32 && ddt == TAV_BF16) hipLaunchKernelGGL((group_pad_kernel<float, bf16>), G1(n4), (const float*)x, (bf16*)xg, n4, (int)T, (int)H, (int)G, (int)pad_l, TP);
-    else if (sdt == TAV_F32 && ddt == TAV_F32) hipLaunchKernelGGL((group_pad_kernel<float, float>), G1(n4), (const float*)x, (float*)xg, n4, (int)T, (int)H, (int)G, (int)pad_l, TP);
-    else if (sdt == TAV_BF16 && ddt == TAV_BF16) hipLaunchKernelGGL((group_pad_kernel<bf16, bf16>), G1(n4), (const bf16*)x, (bf16*)xg, n4, (int)T, (int)H, (int)G, (int)pad_l, TP);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    using cases = dtypes<on<TAV_F32, TAV_BF16>, on<TAV_F32, TAV_F32>, on<TAV_BF16, TAV_BF16>>;
+    return cases::dispatch(sdt, ddt, [&](auto ts, auto td) {
+        using S = decltype(ts); using D = decltype(td);
+        TAV_LAUNCH((group_pad_kernel<S, D>), plan::grid1(n4), stream, (const S*)x, (D*)xg, n4, (int)T, (int)H, (int)G, (int)pad_l, TP);
+        return 0;
+    });
 }
-extern "C" int tav_weight_norm_partials(int64_t H, int64_t Cg) { long r = H * Cg; long nb = (r + 255) / 256; return (int)(nb > 512 ? 512 : nb); }
+extern "C" int tav_weight_norm_partials(int64_t H, int64_t Cg) { return plan::weight_norm_partials(H, Cg); }
 extern "C" int tav_weight_norm_fwd(const float* v, const float* g, float* norms, float* partials, void* w, void* w_flip, int32_t dt, int64_t H, int64_t Cg,
                                    int64_t K, void* stream) {
-    if (!v || !g || !norms || !partials || (!w && !w_flip)) return TAV_ERR_NULL;
-    if (H <= 0 || Cg <= 0 || K <= 0 || K > 128 || H % Cg) return TAV_ERR_SHAPE;
-    const long rows = H * Cg;
-    const int nb = tav_weight_norm_partials(H, Cg);
-    const int rpb = (int)((rows + nb - 1) / nb);
-    hipLaunchKernelGGL(wn_colsum_partial_kernel, dim3(nb), dim3(128), 0, ST, v, (const float*)nullptr, partials, rows, (int)K, rpb);
-    hipLaunchKernelGGL(wn_colsum_final_kernel, dim3(1), dim3(128), 0, ST, partials, norms, nb, (int)K, 1);
-    const long n = rows * K;
-    if (dt == TAV_BF16) hipLaunchKernelGGL((wn_apply_kernel<bf16>), G1(n), v, g, norms, (bf16*)w, (bf16*)w_flip, (int)H, (int)Cg, (int)K);
-    else if (dt == TAV_F32) hipLaunchKernelGGL((wn_apply_kernel<float>), G1(n), v, g, norms, (float*)w, (float*)w_flip, (int)H, (int)Cg, (int)K);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    if (const int rc = plan::weight_norm_validate(v && g && norms && partials && (w || w_flip), dt, H, Cg, K)) return rc;
+    const plan::WnPlan P = plan::weight_norm_plan(H, Cg, K);
+    TAV_LAUNCH(wn_colsum_partial_kernel, P.partial, stream, v, (const float*)nullptr, partials, (long)P.rows, (int)K, P.rows_per_part);
+    TAV_LAUNCH(wn_colsum_final_kernel, P.final_, stream, partials, norms, P.parts, (int)K, 1);
+    return floats::dispatch(dt, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((wn_apply_kernel<T>), P.apply, stream, v, g, norms, (T*)w, (T*)w_flip, (int)H, (int)Cg, (int)K);
+        return 0;
+    });
 }
 // workspace: dw_nat (H*Cg*K) + partials (tav_weight_norm_partials * K) + dots (K) floats
 extern "C" int tav_weight_norm_bwd(const float* v, const float* g, const float* norms, const float* dw_gemm, float* workspace, float* dv, float* dg,
                                    int64_t H, int64_t Cg, int64_t K, int32_t accumulate, void* stream) {
-    if (!v || !g || !norms || !dw_gemm || !workspace || !dv || !dg) return TAV_ERR_NULL;
-    if (H <= 0 || Cg <= 0 || K <= 0 || K > 128 || H % Cg) return TAV_ERR_SHAPE;
-    const long rows = H * Cg, n = rows * K;
-    const int nb = tav_weight_norm_partials(H, Cg);
-    const int rpb = (int)((rows + nb - 1) / nb);
-    float* dw_nat = workspace; float* partials = workspace + n; float* dots = partials + (long)nb * K;
-    hipLaunchKernelGGL(wn_dw_to_nat_kernel, G1(n), dw_gemm, dw_nat, (int)H, (int)Cg, (int)K);
-    hipLaunchKernelGGL(wn_colsum_partial_kernel, dim3(nb), dim3(128), 0, ST, (const float*)dw_nat, v, partials, rows, (int)K, rpb);
-    hipLaunchKernelGGL(wn_colsum_final_kernel, dim3(1), dim3(128), 0, ST, partials, dots, nb, (int)K, 0);
-    hipLaunchKernelGGL(wn_bwd_apply_kernel, G1(n), v, g, norms, (const float*)dw_nat, (const float*)dots, dv, dg, n, (int)K, accumulate);
-    return tav_last_error();
+    if (const int rc = plan::weight_norm_validate(v && g && norms && dw_gemm && workspace && dv && dg, TAV_F32, H, Cg, K)) return rc;
+    const plan::WnPlan P = plan::weight_norm_plan(H, Cg, K);
+    float* dw_nat = workspace + P.ws_dw; float* partials = workspace + P.ws_partials; float* dots = workspace + P.ws_dots;
+    TAV_LAUNCH(wn_dw_to_nat_kernel, P.apply, stream, dw_gemm, dw_nat, (int)H, (int)Cg, (int)K);
+    TAV_LAUNCH(wn_colsum_partial_kernel, P.partial, stream, (const float*)dw_nat, v, partials, (long)P.rows, (int)K, P.rows_per_part);
+    TAV_LAUNCH(wn_colsum_final_kernel, P.final_, stream, partials, dots, P.parts, (int)K, 0);
+    TAV_LAUNCH(wn_bwd_apply_kernel, P.apply, stream, v, g, norms, (const float*)dw_nat, (const float*)dots, dv, dg, (long)P.n, (int)K, accumulate);
+    return 0;
 }

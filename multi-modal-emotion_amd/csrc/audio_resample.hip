@@ -13,19 +13,8 @@
 #include "tavhip_internal.h"
 
 namespace tav {
-
-constexpr int AR_THREADS = 256;
-constexpr int AR_MAX_PER_THREAD = 4;      // a tile is 256, 512, 768 or 1024 outputs: the largest whose input span fits AR_SPAN_MAX
-constexpr int AR_SPAN_MAX = 8192;         // f32 elements of LDS for the channel mean of a tile's input span (32 KiB)
-constexpr int AR_TABLE_MAX = 6144;        // f32 elements of LDS for the compact table (24 KiB): 441/160 needs 160 x 35, 441/320 320 x 17
-
-// Row pitch of the table in LDS.  The lanes of a wave make consecutive outputs, hence consecutive phases p at the same k: lane l reads
-// p_l * pitch + k.  ds_read_b32 serves 32 lanes per cycle from 32 four-byte banks, so an odd pitch puts them on 32 different banks (ntap = 34
-// itself would pair them up).
-static inline int ar_pitch(int ntap) { return ntap | 1; }
-
-// the most input positions `tile` consecutive outputs read: they span at most (tile + n - 2) / n + 1 values of q
-static inline long ar_span(long tile, long o, long n, long width) { return ((tile + n - 2) / n + 1) * o + 2 * width; }
+// defined with the host decisions (entry_plan.h)
+using plan::AR_THREADS, plan::AR_SPAN_MAX, plan::AR_TABLE_MAX;
 
 TAV_DEV float ar_load(const float* p) { return *p; }
 TAV_DEV float ar_load(const int16_t* p) { return (float)*p * 0x1p-15f; }          // exact: what torchaudio.load makes of a 16-bit file
@@ -93,36 +82,16 @@ __global__ __launch_bounds__(AR_THREADS) void audio_resample_kernel(const TS* __
 }  // namespace tav
 using namespace tav;
 
-// outputs per workgroup for a rate pair, 0 when not even 256 outputs' input span fits the LDS buffer (o / n beyond about 30)
-extern "C" int tav_audio_resample_tile(int32_t o, int32_t n, int32_t width) {
-    if (o < 1 || n < 1 || width < 0) return 0;
-    for (int m = AR_MAX_PER_THREAD; m >= 1; --m)
-        if (ar_span((long)m * AR_THREADS, o, n, width) <= AR_SPAN_MAX) return m * AR_THREADS;
-    return 0;
-}
+extern "C" int tav_audio_resample_tile(int32_t o, int32_t n, int32_t width) { return plan::audio_resample_tile(o, n, width); }
 
 extern "C" int tav_audio_resample(const void* src, const float* table, const int32_t* first, float* values, float* mask,
                                   const tav_resample_args* a, void* stream) {
-    if (!src || !values || !table || !first || !a) return TAV_ERR_NULL;
-    if (a->src_dtype != TAV_F32 && a->src_dtype != TAV_I16) return TAV_ERR_DTYPE;
-    if (a->C < 1 || a->C > 32 || a->L < 1 || a->L > (1L << 40) || a->sC < 0 || a->sL < 0) return TAV_ERR_SHAPE;
-    if (a->o < 1 || a->n < 1 || a->ntap < 1 || a->width < 0 || a->o > (1 << 20) || a->n > (1 << 20) || a->width > (1 << 24)) return TAV_ERR_SHAPE;
-    if ((long)a->n * a->ntap > (1L << 24)) return TAV_ERR_SHAPE;
-    if (a->first_max < 0 || (long)a->first_max + a->ntap > 2L * a->width + a->o) return TAV_ERR_SHAPE;
-    const long L_out = ((long)a->n * a->L + a->o - 1) / a->o;
-    if (a->T_row < L_out || a->T_row > (1L << 40)) return TAV_ERR_SHAPE;
-    const int tile = tav_audio_resample_tile(a->o, a->n, a->width);
-    if (tile == 0) return TAV_ERR_SHAPE;
-    const long blocks = (a->T_row + tile - 1) / tile;
-    if (blocks > 0x7fffffffL) return TAV_ERR_SHAPE;
-    const int in_lds = (long)a->n * ar_pitch(a->ntap) <= AR_TABLE_MAX;
+    plan::ResamplePlan P;
+    if (const int rc = plan::audio_resample_validate(src && values && table && first && a, a, &P)) return rc;
     const float inv_c = 1.0f / (float)a->C;
-    const hipStream_t st = (hipStream_t)stream;
-    if (a->src_dtype == TAV_I16)
-        hipLaunchKernelGGL(audio_resample_kernel<int16_t>, dim3((unsigned)blocks), dim3(AR_THREADS), 0, st, (const int16_t*)src, table, first,
-                           values, mask, *a, L_out, tile, in_lds, inv_c);
-    else
-        hipLaunchKernelGGL(audio_resample_kernel<float>, dim3((unsigned)blocks), dim3(AR_THREADS), 0, st, (const float*)src, table, first, values,
-                           mask, *a, L_out, tile, in_lds, inv_c);
-    return tav_last_error();
+    return dtypes<on<TAV_I16>, on<TAV_F32>>::dispatch(a->src_dtype, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH(audio_resample_kernel<T>, P.launch, stream, (const T*)src, table, first, values, mask, *a, (long)P.L_out, P.tile, P.table_in_lds, inv_c);
+        return 0;
+    });
 }

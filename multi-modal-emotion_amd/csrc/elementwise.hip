@@ -5,6 +5,8 @@
 #include "tavhip_internal.h"
 
 namespace tav {
+// defined with the host decisions (entry_plan.h)
+using plan::SCAT_T, plan::SUMSQ_BLOCKS, plan::OPT_CHUNK, plan::OPT_MAX_GROUPS;
 
 // ------------------------------------------------------------------------------------------------ weight casts
 template <typename TD>
@@ -213,7 +215,6 @@ __global__ void text_embed_sum_kernel(const int64_t* __restrict__ ids, const int
 // ascending order, the rows that carry the same index (rows <= a few thousand: rows/1024 compares per thread); only the workgroup
 // of the FIRST such row goes on and adds their sum to the table row.  Wave w sums matches w, w+16, ... (fixed order), the 16
 // partial rows meet in LDS in wave order.  A padding token shared by a quarter of the batch costs rows/64 serial row reads.
-constexpr int SCAT_T = 1024, SCAT_MAXW = 1024;
 __global__ __launch_bounds__(SCAT_T) void scatter_add_rows_kernel(const float* __restrict__ d, const int64_t* __restrict__ idx, float* __restrict__ dtable,
                                                                   int rows, int W, long ntable) {
     extern __shared__ __attribute__((aligned(16))) char scat_smem[];
@@ -587,7 +588,6 @@ __global__ void dropout_bwd_kernel(const float* __restrict__ dy, const uint8_t* 
 }
 
 // ------------------------------------------------------------------------------------------------ optimiser
-constexpr int SUMSQ_BLOCKS = 96;
 __global__ __launch_bounds__(256) void sumsq_multi_kernel(const float* const* __restrict__ ptrs, const int64_t* __restrict__ sizes, float* __restrict__ partials) {
     __shared__ float red[256];
     const int t = blockIdx.y;
@@ -649,7 +649,6 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(float* const* __restri
 // ---- chunked forms: block c handles chunk c of the concatenation of all tensors (chunk_prefix[t] = first chunk of tensor t, built once
 // on the host since the sizes are static).  Every block has OPT_CHUNK elements of work (except a tensor's last chunk): no empty blocks
 // for the ~400 small tensors, enough parallelism for the large ones, float4 accesses.
-constexpr int OPT_CHUNK = 16384;
 TAV_DEV int chunk_owner(const int32_t* __restrict__ prefix, int ntensors, int c) {
     int lo = 0, hi = ntensors - 1;
     while (lo < hi) {                               // last t with prefix[t] <= c
@@ -753,7 +752,6 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(float* const* __restri
 }
 // Parameter groups: the same walk; tensor t belongs to group group_of[t] (clamped into the table) and takes that group's {lr, wd} from the
 // device table `hyper` -- three more block-uniform loads per chunk, all of them before the element loops.
-constexpr int OPT_MAX_GROUPS = 64;
 __global__ __launch_bounds__(256) void adamw_chunk_groups_kernel(float* const* __restrict__ params, const float* const* __restrict__ grads,
                                                                  float* const* __restrict__ m1, float* const* __restrict__ m2,
                                                                  const int64_t* __restrict__ sizes, const int32_t* __restrict__ prefix, int ntensors,
@@ -775,9 +773,6 @@ __global__ __launch_bounds__(256) void adamw_chunk_groups_kernel(float* const* _
 }  // namespace tav
 using namespace tav;
 
-#define ST ((hipStream_t)stream)
-#define G1(n) dim3(tav_cdiv((n), 256)), dim3(256), 0, ST
-
 extern "C" int tav_version(void) { return TAV_ABI_VERSION; }
 extern "C" const char* tav_error_string(int code) {
     switch (code) {
@@ -792,32 +787,28 @@ extern "C" const char* tav_error_string(int code) {
 }
 
 extern "C" int tav_cast_weight(const float* src, int64_t R, int64_t C, void* dst, int64_t ld_dst, void* dst_t, int64_t ld_dst_t, int32_t dt, void* stream) {
-    if (!src || (!dst && !dst_t)) return TAV_ERR_NULL;
-    if (R <= 0 || C <= 0) return TAV_ERR_SHAPE;
+    if (const int rc = plan::cast_weight_validate(src && (dst || dst_t), dt, R, C)) return rc;
     const long ld_n = ld_dst > 0 ? ld_dst : C, ld_t = ld_dst_t > 0 ? ld_dst_t : R;
-    dim3 grid(tav_cdiv(C, 32), tav_cdiv(R, 32));
-    if (dt == TAV_BF16) hipLaunchKernelGGL((cast_weight_kernel<bf16>), grid, dim3(256), 0, ST, src, (bf16*)dst, ld_n, (bf16*)dst_t, ld_t, (int)R, (int)C);
-    else if (dt == TAV_F32) hipLaunchKernelGGL((cast_weight_kernel<float>), grid, dim3(256), 0, ST, src, (float*)dst, ld_n, (float*)dst_t, ld_t, (int)R, (int)C);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    return floats::dispatch(dt, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((cast_weight_kernel<T>), plan::tile32_launch(R, C), stream, src, (T*)dst, ld_n, (T*)dst_t, ld_t, (int)R, (int)C);
+        return 0;
+    });
 }
 extern "C" int tav_cast_weights_multi(const void* descs_dev, int32_t n, int32_t blocks_per_tensor, void* stream) {
-    if (!descs_dev) return TAV_ERR_NULL;
-    if (n <= 0 || n > 65535 || blocks_per_tensor <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(cast_weight_multi_kernel, dim3(blocks_per_tensor, n), dim3(256), 0, ST, (const CastDesc*)descs_dev);
-    return tav_last_error();
+    if (const int rc = plan::cast_weights_multi_validate(descs_dev, n, blocks_per_tensor)) return rc;
+    TAV_LAUNCH(cast_weight_multi_kernel, (plan::Launch{blocks_per_tensor, n, 1, 256, 0}), stream, (const CastDesc*)descs_dev);
+    return 0;
 }
 extern "C" int tav_cast_conv_weight(const float* src, int64_t co, int64_t ci, int64_t k, void* dst, void* dst_t, void* dst_phase, int64_t conv_stride,
                                     int32_t dt, void* stream) {
-    if (!src || (!dst && !dst_t && !dst_phase)) return TAV_ERR_NULL;
-    if (co <= 0 || ci <= 0 || k <= 0) return TAV_ERR_SHAPE;
-    if (dst_phase && (conv_stride <= 0 || conv_stride > k)) return TAV_ERR_SHAPE;     // (stride > k would leave phases without a tap)
-    const long n = co * ci * k;
+    if (const int rc = plan::cast_conv_weight_validate(src && (dst || dst_t || dst_phase), dst_phase, dt, co, ci, k, conv_stride)) return rc;
     const int cs = dst_phase ? (int)conv_stride : 1;
-    if (dt == TAV_BF16) hipLaunchKernelGGL((cast_conv_weight_kernel<bf16>), G1(n), src, (bf16*)dst, (bf16*)dst_t, (bf16*)dst_phase, (int)co, (int)ci, (int)k, cs);
-    else if (dt == TAV_F32) hipLaunchKernelGGL((cast_conv_weight_kernel<float>), G1(n), src, (float*)dst, (float*)dst_t, (float*)dst_phase, (int)co, (int)ci, (int)k, cs);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    return floats::dispatch(dt, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((cast_conv_weight_kernel<T>), plan::grid1(co * ci * k), stream, src, (T*)dst, (T*)dst_t, (T*)dst_phase, (int)co, (int)ci, (int)k, cs);
+        return 0;
+    });
 }
 // v5: zero rows [0, pad) and [pad + T, T + 2 pad) of every [T + 2 pad][C] batch entry (the zero frame around a padded gradient buffer)
 template <typename T> __global__ void zero_pad_rows_kernel(T* __restrict__ buf, long n4, int Tn, int C, int pad) {
@@ -832,268 +823,230 @@ template <typename T> __global__ void zero_pad_rows_kernel(T* __restrict__ buf, 
     st4(buf + trow * C + col, f32x4{0.f, 0.f, 0.f, 0.f});
 }
 extern "C" int tav_zero_pad_rows(void* buf, int32_t dt, int64_t B, int64_t T, int64_t C, int64_t pad, void* stream) {
-    if (!buf) return TAV_ERR_NULL;
-    if (B <= 0 || T <= 0 || C <= 0 || C % 4 || pad <= 0) return TAV_ERR_SHAPE;
+    if (const int rc = plan::zero_pad_rows_validate(buf, dt, B, T, C, pad)) return rc;
     const long n4 = B * 2 * pad * (C / 4);
-    if (dt == TAV_BF16) hipLaunchKernelGGL((zero_pad_rows_kernel<bf16>), G1(n4), (bf16*)buf, n4, (int)T, (int)C, (int)pad);
-    else if (dt == TAV_F32) hipLaunchKernelGGL((zero_pad_rows_kernel<float>), G1(n4), (float*)buf, n4, (int)T, (int)C, (int)pad);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    return floats::dispatch(dt, [&](auto t) {
+        using E = decltype(t);
+        TAV_LAUNCH((zero_pad_rows_kernel<E>), plan::grid1(n4), stream, (E*)buf, n4, (int)T, (int)C, (int)pad);
+        return 0;
+    });
 }
 extern "C" int tav_cast2d(const void* src, int32_t sdt, int64_t ld_src, void* dst, int32_t ddt, int64_t ld_dst, int64_t R, int64_t C, void* stream) {
-    if (!src || !dst) return TAV_ERR_NULL;
-    if (R <= 0 || C <= 0 || C % 4) return TAV_ERR_SHAPE;
-    if (ld_src % 4 || ld_dst % 4) return TAV_ERR_ALIGN;
-    const long n = R * (C / 4);
-    if (sdt == TAV_F32 && ddt == TAV_BF16) hipLaunchKernelGGL((cast2d_kernel<float, bf16>), G1(n), (const float*)src, (long)ld_src, (bf16*)dst, (long)ld_dst, (long)R, (int)(C / 4));
-    else if (sdt == TAV_BF16 && ddt == TAV_F32) hipLaunchKernelGGL((cast2d_kernel<bf16, float>), G1(n), (const bf16*)src, (long)ld_src, (float*)dst, (long)ld_dst, (long)R, (int)(C / 4));
-    else if (sdt == TAV_F32 && ddt == TAV_F32) hipLaunchKernelGGL((cast2d_kernel<float, float>), G1(n), (const float*)src, (long)ld_src, (float*)dst, (long)ld_dst, (long)R, (int)(C / 4));
-    else if (sdt == TAV_BF16 && ddt == TAV_BF16) hipLaunchKernelGGL((cast2d_kernel<bf16, bf16>), G1(n), (const bf16*)src, (long)ld_src, (bf16*)dst, (long)ld_dst, (long)R, (int)(C / 4));
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    if (const int rc = plan::cast2d_validate(src && dst, sdt, ddt, ld_src, ld_dst, R, C)) return rc;
+    using cases = dtypes<on<TAV_F32, TAV_BF16>, on<TAV_BF16, TAV_F32>, on<TAV_F32, TAV_F32>, on<TAV_BF16, TAV_BF16>>;
+    return cases::dispatch(sdt, ddt, [&](auto ts, auto td) {
+        using S = decltype(ts); using D = decltype(td);
+        TAV_LAUNCH((cast2d_kernel<S, D>), plan::grid1(R * (C / 4)), stream, (const S*)src, (long)ld_src, (D*)dst, (long)ld_dst, (long)R, (int)(C / 4));
+        return 0;
+    });
 }
 extern "C" int tav_transpose2d(const void* src, void* dst, int32_t dt, int64_t R, int64_t C, int64_t nbatch, void* stream) {
-    if (!src || !dst) return TAV_ERR_NULL;
-    if (R <= 0 || C <= 0 || nbatch <= 0 || nbatch > 65535) return TAV_ERR_SHAPE;
-    dim3 grid(tav_cdiv(C, 32), tav_cdiv(R, 32), (unsigned)nbatch);
-    if (dt == TAV_BF16) hipLaunchKernelGGL((transpose2d_kernel<bf16>), grid, dim3(256), 0, ST, (const bf16*)src, (bf16*)dst, (int)R, (int)C);
-    else if (dt == TAV_F32) hipLaunchKernelGGL((transpose2d_kernel<float>), grid, dim3(256), 0, ST, (const float*)src, (float*)dst, (int)R, (int)C);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    if (const int rc = plan::transpose2d_validate(src && dst, dt, R, C, nbatch)) return rc;
+    return floats::dispatch(dt, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((transpose2d_kernel<T>), plan::tile32_launch(R, C, nbatch), stream, (const T*)src, (T*)dst, (int)R, (int)C);
+        return 0;
+    });
 }
 extern "C" int tav_add_f32(const float* a, const float* b, float* y, void* y_lp, int32_t lp, int64_t n, void* stream) {
-    if (!a || !b || (!y && !y_lp)) return TAV_ERR_NULL;
-    if (n <= 0 || n % 4) return TAV_ERR_SHAPE;
-    if (y_lp && lp == TAV_BF16) hipLaunchKernelGGL((add_f32_kernel<bf16>), G1(n / 4), a, b, y, (bf16*)y_lp, n / 4);
-    else hipLaunchKernelGGL((add_f32_kernel<float>), G1(n / 4), a, b, y, (float*)y_lp, n / 4);
-    return tav_last_error();
+    if (const int rc = plan::add_f32_validate(a && b && (y || y_lp), n)) return rc;
+    return floats::dispatch(plan::lp_code(y_lp, lp), [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((add_f32_kernel<T>), plan::grid1(n / 4), stream, a, b, y, (T*)y_lp, n / 4);
+        return 0;
+    });
 }
 extern "C" int tav_fill_f32(float* p, float v, int64_t n, void* stream) {
-    if (!p) return TAV_ERR_NULL;
-    if (n <= 0) return TAV_ERR_SHAPE;
-    const long blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(fill_f32_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, ST, p, v, (long)n);
-    return tav_last_error();
+    if (const int rc = plan::count_validate(p, n)) return rc;
+    TAV_LAUNCH(fill_f32_kernel, plan::fill_launch(n), stream, p, v, (long)n);
+    return 0;
 }
 extern "C" int tav_embed_add_fwd(const float* x, const int64_t* ids, const float* table, float* out, int64_t rows, int64_t W, int64_t ntable, void* stream) {
-    if (!x || !ids || !table || !out) return TAV_ERR_NULL;
-    if (rows <= 0 || W <= 0 || W % 4 || ntable <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(embed_add_fwd_kernel, G1(rows * (W / 4)), x, ids, table, out, (long)rows, (int)(W / 4));
-    return tav_last_error();
+    if (const int rc = plan::table_rows_validate(x && ids && table && out, rows, W, ntable)) return rc;
+    TAV_LAUNCH(embed_add_fwd_kernel, plan::grid1(rows * (W / 4)), stream, x, ids, table, out, (long)rows, (int)(W / 4));
+    return 0;
 }
-extern "C" int tav_embed_add_bwd_parts(int64_t rows) { long p = (rows + 255) / 256; return (int)(p > 256 ? 256 : p); }
+extern "C" int tav_embed_add_bwd_parts(int64_t rows) { return plan::embed_add_bwd_parts(rows); }
 extern "C" int tav_embed_add_bwd(const float* dy, const int64_t* ids, float* dtable, float* partials, int64_t rows, int64_t W, int64_t ntable,
                                  int32_t accumulate, void* stream) {
-    if (!dy || !ids || !dtable || !partials) return TAV_ERR_NULL;
-    if (rows <= 0 || W <= 0 || ntable <= 0 || ntable > 8) return TAV_ERR_SHAPE;
-    const int nparts = tav_embed_add_bwd_parts(rows);
-    const int rpb = (int)((rows + nparts - 1) / nparts);
-    hipLaunchKernelGGL(embed_add_bwd_partial_kernel, dim3(tav_cdiv(W, 256), nparts), dim3(256), 0, ST, dy, ids, partials, (long)rows, (int)W, (int)ntable, rpb);
-    hipLaunchKernelGGL(embed_add_bwd_final_kernel, G1(ntable * W), partials, dtable, nparts, (int)ntable, (int)W, accumulate);
-    return tav_last_error();
+    if (const int rc = plan::embed_add_bwd_validate(dy && ids && dtable && partials, rows, W, ntable)) return rc;
+    const plan::PartsPlan P = plan::embed_add_bwd_plan(rows, W, ntable);
+    TAV_LAUNCH(embed_add_bwd_partial_kernel, P.partial, stream, dy, ids, partials, (long)rows, (int)W, (int)ntable, P.rows_per_part);
+    TAV_LAUNCH(embed_add_bwd_final_kernel, P.final_, stream, partials, dtable, P.parts, (int)ntable, (int)W, accumulate);
+    return 0;
 }
 extern "C" int tav_ln_fwd(const tav_ln_args* a, void* stream);
 extern "C" int tav_text_embed_fwd(const tav_text_embed_args* a, void* stream) {
-    if (!a || !a->ids || !a->word || !a->pos || !a->type || !a->gamma || !a->beta || !a->pre || !a->pos_ids) return TAV_ERR_NULL;
-    if (a->B <= 0 || a->S <= 0 || a->S > 1024 || a->W <= 0 || a->W % 4) return TAV_ERR_SHAPE;
-    int threads = 64; while (threads < a->S) threads <<= 1;
-    hipLaunchKernelGGL(text_pos_ids_kernel, dim3((unsigned)a->B), dim3(threads), 0, ST, a->ids, a->pos_ids, (int)a->S, a->pad_id);
-    const long rows = a->B * a->S;
-    hipLaunchKernelGGL(text_embed_sum_kernel, G1(rows * (a->W / 4)), a->ids, a->pos_ids, a->word, a->pos, a->type, a->pre, rows, (int)(a->W / 4));
-    int e = tav_last_error();
-    if (e) return e;
-    tav_ln_args ln = {};
-    ln.x = a->pre; ln.x_dtype = TAV_F32; ln.gamma = a->gamma; ln.beta = a->beta; ln.y_f32 = a->y_f32; ln.y_lp = a->y_lp; ln.lp_dtype = a->lp_dtype;
-    ln.mean = a->mean; ln.rstd = a->rstd; ln.rows = rows; ln.W = a->W; ln.ld_x = a->W; ln.ld_y = a->W; ln.eps = a->eps;
+    if (const int rc = plan::text_embed_validate(a)) return rc;
+    const tav_ln_args ln = plan::text_embed_ln(a);
+    TAV_LAUNCH(text_pos_ids_kernel, (plan::Launch{a->B, 1, 1, plan::text_pos_threads(a->S), 0}), stream, a->ids, a->pos_ids, (int)a->S, a->pad_id);
+    TAV_LAUNCH(text_embed_sum_kernel, plan::grid1(ln.rows * (a->W / 4)), stream, a->ids, a->pos_ids, a->word, a->pos, a->type, a->pre, (long)ln.rows, (int)(a->W / 4));
     return tav_ln_fwd(&ln, stream);
 }
 extern "C" int tav_scatter_add_rows(const float* d, const int64_t* idx, float* dtable, int64_t rows, int64_t W, int64_t ntable, void* stream) {
-    if (!d || !idx || !dtable) return TAV_ERR_NULL;
-    if (rows <= 0 || W <= 0 || ntable <= 0 || W % 4 || W > SCAT_MAXW) return TAV_ERR_SHAPE;
-    const size_t lds = 256 + (((size_t)rows * 4 + 15) & ~(size_t)15) + (size_t)16 * W * 4;  // header + match list + 16 partial rows
-    if (lds > 150 * 1024) return TAV_ERR_SHAPE;                                           // rows <= ~22 k tokens per call at W = 768
-    hipLaunchKernelGGL(scatter_add_rows_kernel, dim3((unsigned)rows), dim3(SCAT_T), lds, ST, d, idx, dtable, (int)rows, (int)W, (long)ntable);
-    return tav_last_error();
+    if (const int rc = plan::scatter_add_validate(d && idx && dtable, rows, W, ntable)) return rc;
+    TAV_LAUNCH(scatter_add_rows_kernel, (plan::Launch{rows, 1, 1, SCAT_T, plan::scatter_add_lds(rows, W)}), stream, d, idx, dtable, (int)rows, (int)W, (long)ntable);
+    return 0;
 }
 extern "C" int tav_gather_rows(const float* table, const int32_t* idx, float* out, int64_t rows, int64_t W, int64_t ntable, void* stream) {
-    if (!table || !idx || !out) return TAV_ERR_NULL;
-    if (rows <= 0 || W <= 0 || W % 4 || ntable <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(gather_rows_kernel, G1(rows * (W / 4)), table, idx, out, (long)rows, (int)(W / 4), (int)ntable);
-    return tav_last_error();
+    if (const int rc = plan::table_rows_validate(table && idx && out, rows, W, ntable)) return rc;
+    TAV_LAUNCH(gather_rows_kernel, plan::grid1(rows * (W / 4)), stream, table, idx, out, (long)rows, (int)(W / 4), (int)ntable);
+    return 0;
 }
 extern "C" int tav_patchify(const float* video, const int32_t* keep_idx, void* patches, int32_t dt, int64_t B, int64_t F, int64_t H, int64_t W, int64_t nkeep,
                             void* stream) {
-    if (!video || !keep_idx || !patches) return TAV_ERR_NULL;
-    if (B <= 0 || F <= 0 || F % 2 || H % 16 || W % 16 || nkeep <= 0) return TAV_ERR_SHAPE;
-    dim3 grid((unsigned)nkeep, (unsigned)B);
-    if (dt == TAV_BF16) hipLaunchKernelGGL((patchify_kernel<bf16>), grid, dim3(256), 0, ST, video, keep_idx, (bf16*)patches, (int)F, (int)H, (int)W, (int)nkeep);
-    else if (dt == TAV_F32) hipLaunchKernelGGL((patchify_kernel<float>), grid, dim3(256), 0, ST, video, keep_idx, (float*)patches, (int)F, (int)H, (int)W, (int)nkeep);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    if (const int rc = plan::patchify_validate(video && keep_idx && patches, dt, B, F, H, W, nkeep)) return rc;
+    return floats::dispatch(dt, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((patchify_kernel<T>), (plan::Launch{nkeep, B, 1, 256, 0}), stream, video, keep_idx, (T*)patches, (int)F, (int)H, (int)W, (int)nkeep);
+        return 0;
+    });
 }
 extern "C" int tav_mask_to_index(const uint8_t* mask, int32_t keep_value, int32_t* keep_idx, int32_t* counts, int64_t B, int64_t n, int64_t nkeep, void* stream) {
-    if (!mask || !keep_idx) return TAV_ERR_NULL;
-    if (B <= 0 || n <= 0 || nkeep <= 0 || nkeep > n) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(mask_to_index_kernel, dim3((unsigned)B), dim3(256), 0, ST, mask, keep_value, keep_idx, counts, (int)n, (int)nkeep);
-    return tav_last_error();
+    if (const int rc = plan::mask_to_index_validate(mask && keep_idx, B, n, nkeep)) return rc;
+    TAV_LAUNCH(mask_to_index_kernel, (plan::Launch{B, 1, 1, 256, 0}), stream, mask, keep_value, keep_idx, counts, (int)n, (int)nkeep);
+    return 0;
 }
 extern "C" int tav_ragged_lens(const uint8_t* mask, int32_t* true_cnt, int32_t* vid_lens, int32_t* av_lens, int32_t* status, int64_t B, int64_t ntok,
                                int64_t cap_true, int64_t cap_keep, int64_t base, void* stream) {
-    if (!mask || !true_cnt || !vid_lens || !av_lens || !status) return TAV_ERR_NULL;
-    if (B <= 0 || ntok <= 0 || cap_true <= 0 || cap_true > ntok || cap_keep <= 0 || cap_keep > ntok || base < 0) return TAV_ERR_SHAPE;
-    if (ntok > INT32_MAX / 2 || base > INT32_MAX / 2) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(ragged_lens_kernel, dim3((unsigned)B), dim3(256), 0, ST, mask, true_cnt, vid_lens, av_lens, status, (int)ntok, (int)cap_true,
-                       (int)cap_keep, (int)base);
-    return tav_last_error();
+    if (const int rc = plan::ragged_lens_validate(mask && true_cnt && vid_lens && av_lens && status, B, ntok, cap_true, cap_keep, base)) return rc;
+    TAV_LAUNCH(ragged_lens_kernel, (plan::Launch{B, 1, 1, 256, 0}), stream, mask, true_cnt, vid_lens, av_lens, status, (int)ntok, (int)cap_true, (int)cap_keep, (int)base);
+    return 0;
 }
 extern "C" int tav_mean_pool_fwd(const float* x, float* y, int64_t B, int64_t S, int64_t W, void* stream) {
-    if (!x || !y) return TAV_ERR_NULL;
-    if (B <= 0 || S <= 0 || W <= 0) return TAV_ERR_SHAPE;
-    if (W % 4) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(mean_pool_fwd_kernel, dim3(tav_cdiv(W, 64), (unsigned)B), dim3(256), 0, ST, x, y, (int)S, (int)W);
-    return tav_last_error();
+    if (const int rc = plan::mean_pool_validate(x && y, B, S, W)) return rc;
+    TAV_LAUNCH(mean_pool_fwd_kernel, plan::mean_pool_fwd_launch(B, W), stream, x, y, (int)S, (int)W);
+    return 0;
 }
 extern "C" int tav_mean_pool_bwd(const float* dy, float* dx, void* dx_lp, int32_t lp, int64_t B, int64_t S, int64_t W, void* stream) {
-    if (!dy || (!dx && !dx_lp)) return TAV_ERR_NULL;
-    if (B <= 0 || S <= 0 || W <= 0 || W % 4) return TAV_ERR_SHAPE;
+    if (const int rc = plan::mean_pool_validate(dy && (dx || dx_lp), B, S, W)) return rc;
     const long n4 = B * S * W / 4;
-    if (dx_lp && lp == TAV_BF16) hipLaunchKernelGGL((mean_pool_bwd_kernel<bf16>), G1(n4), dy, dx, (bf16*)dx_lp, n4, (int)S, (int)(W / 4));
-    else hipLaunchKernelGGL((mean_pool_bwd_kernel<float>), G1(n4), dy, dx, (float*)dx_lp, n4, (int)S, (int)(W / 4));
-    return tav_last_error();
+    return floats::dispatch(plan::lp_code(dx_lp, lp), [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((mean_pool_bwd_kernel<T>), plan::grid1(n4), stream, dy, dx, (T*)dx_lp, n4, (int)S, (int)(W / 4));
+        return 0;
+    });
 }
 extern "C" int tav_mean_pool_fwd_len(const float* x, float* y, const int32_t* seq_lens, int64_t B, int64_t S, int64_t W, void* stream) {
-    if (!x || !y || !seq_lens) return TAV_ERR_NULL;
-    if (B <= 0 || S <= 0 || W <= 0) return TAV_ERR_SHAPE;
-    if (W % 4) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(mean_pool_fwd_len_kernel, dim3(tav_cdiv(W, 64), (unsigned)B), dim3(256), 0, ST, x, y, seq_lens, (int)S, (int)W);
-    return tav_last_error();
+    if (const int rc = plan::mean_pool_validate(x && y && seq_lens, B, S, W)) return rc;
+    TAV_LAUNCH(mean_pool_fwd_len_kernel, plan::mean_pool_fwd_launch(B, W), stream, x, y, seq_lens, (int)S, (int)W);
+    return 0;
 }
 extern "C" int tav_mean_pool_bwd_len(const float* dy, float* dx, void* dx_lp, int32_t lp, const int32_t* seq_lens, int64_t B, int64_t S, int64_t W,
                                      void* stream) {
-    if (!dy || (!dx && !dx_lp) || !seq_lens) return TAV_ERR_NULL;
-    if (B <= 0 || S <= 0 || W <= 0 || W % 4) return TAV_ERR_SHAPE;
+    if (const int rc = plan::mean_pool_validate(dy && (dx || dx_lp) && seq_lens, B, S, W)) return rc;
     const long n4 = B * S * W / 4;
-    if (dx_lp && lp == TAV_BF16) hipLaunchKernelGGL((mean_pool_bwd_len_kernel<bf16>), G1(n4), dy, dx, (bf16*)dx_lp, seq_lens, n4, (int)S, (int)(W / 4));
-    else hipLaunchKernelGGL((mean_pool_bwd_len_kernel<float>), G1(n4), dy, dx, (float*)dx_lp, seq_lens, n4, (int)S, (int)(W / 4));
-    return tav_last_error();
+    return floats::dispatch(plan::lp_code(dx_lp, lp), [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((mean_pool_bwd_len_kernel<T>), plan::grid1(n4), stream, dy, dx, (T*)dx_lp, seq_lens, n4, (int)S, (int)(W / 4));
+        return 0;
+    });
 }
 extern "C" int tav_head_fwd(const float* x, const float* W, const float* b, float* y, int64_t B, int64_t K, int64_t N, void* stream) {
-    if (!x || !W || !y) return TAV_ERR_NULL;
-    if (B <= 0 || K <= 0 || N <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(head_fwd_kernel, dim3(tav_cdiv(B * N, 4)), dim3(256), 0, ST, x, W, b, y, (int)B, (int)K, (int)N);
-    return tav_last_error();
+    if (const int rc = plan::head_validate(x && W && y, B, K, N, INT64_MAX)) return rc;
+    TAV_LAUNCH(head_fwd_kernel, plan::grid1(B * N, 4), stream, x, W, b, y, (int)B, (int)K, (int)N);      // one wave per output
+    return 0;
 }
 extern "C" int tav_head_bwd(const float* x, const float* W, const float* dy, float* dx, float* dW, float* db, int64_t B, int64_t K, int64_t N,
                             int32_t accumulate, void* stream) {
-    if (!x || !W || !dy || !dW) return TAV_ERR_NULL;
-    if (B <= 0 || K <= 0 || N <= 0 || N > 256) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(head_bwd_kernel, G1(K), x, W, dy, dx, dW, db, (int)B, (int)K, (int)N, accumulate);
-    return tav_last_error();
+    if (const int rc = plan::head_validate(x && W && dy && dW, B, K, N, 256)) return rc;
+    TAV_LAUNCH(head_bwd_kernel, plan::grid1(K), stream, x, W, dy, dx, dW, db, (int)B, (int)K, (int)N, accumulate);
+    return 0;
 }
 extern "C" int tav_tanh_fwd(const float* x, float* y, int64_t n, void* stream) {
-    if (!x || !y) return TAV_ERR_NULL;
-    if (n <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(tanh_fwd_kernel, G1(n), x, y, (long)n);
-    return tav_last_error();
+    if (const int rc = plan::count_validate(x && y, n)) return rc;
+    TAV_LAUNCH(tanh_fwd_kernel, plan::grid1(n), stream, x, y, (long)n);
+    return 0;
 }
 extern "C" int tav_tanh_bwd(const float* y, const float* dy, float* dx, int64_t n, void* stream) {
-    if (!y || !dy || !dx) return TAV_ERR_NULL;
-    if (n <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(tanh_bwd_kernel, G1(n), y, dy, dx, (long)n);
-    return tav_last_error();
+    if (const int rc = plan::count_validate(y && dy && dx, n)) return rc;
+    TAV_LAUNCH(tanh_bwd_kernel, plan::grid1(n), stream, y, dy, dx, (long)n);
+    return 0;
 }
+static const plan::Launch ONE_BLOCK = {1, 1, 1, 256, 0}, ONE_THREAD = {1, 1, 1, 1, 0};
 extern "C" int tav_cross_entropy(const float* logits, const int64_t* target, const float* cw, float* loss, float* dlogits, int64_t B, int64_t C,
                                  float grad_scale, void* stream) {
-    if (!logits || !target || (!loss && !dlogits)) return TAV_ERR_NULL;
-    if (B <= 0 || C <= 0 || C > 64) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(cross_entropy_kernel, dim3(1), dim3(256), 0, ST, logits, target, cw, loss, dlogits, (int)B, (int)C, grad_scale);
-    return tav_last_error();
+    if (const int rc = plan::classes_validate(logits && target && (loss || dlogits), B, C, INT64_MAX)) return rc;
+    TAV_LAUNCH(cross_entropy_kernel, ONE_BLOCK, stream, logits, target, cw, loss, dlogits, (int)B, (int)C, grad_scale);
+    return 0;
 }
 extern "C" int tav_step_stats(const float* logits, const int64_t* preds, const int64_t* target, int64_t* cm, const float* loss,
                               const int32_t* status, tav_loop_acc* acc, int64_t B, int64_t C, void* stream) {
-    if (!target || (!logits) == (!preds) || (!cm && !acc)) return TAV_ERR_NULL;
-    if (B <= 0 || B > INT32_MAX || C <= 0 || C > 64) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(step_stats_kernel, dim3(1), dim3(256), 0, ST, logits, preds, target, cm, loss, status, acc, (int)B, (int)C);
-    return tav_last_error();
+    if (const int rc = plan::classes_validate(target && (!logits) != (!preds) && (cm || acc), B, C, INT32_MAX)) return rc;
+    TAV_LAUNCH(step_stats_kernel, ONE_BLOCK, stream, logits, preds, target, cm, loss, status, acc, (int)B, (int)C);
+    return 0;
 }
 extern "C" int tav_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream) {
-    if (!x || !y || !mask) return TAV_ERR_NULL;
-    if (n <= 0 || p < 0.f || p >= 1.f) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(dropout_fwd_kernel, G1(n), x, y, mask, (long)n, p, seed, offset);
-    return tav_last_error();
+    if (const int rc = plan::dropout_validate(x && y && mask, n, p)) return rc;
+    TAV_LAUNCH(dropout_fwd_kernel, plan::grid1(n), stream, x, y, mask, (long)n, p, seed, offset);
+    return 0;
 }
 extern "C" int tav_dropout_fwd_dev(const float* x, float* y, uint8_t* mask, int64_t n, float p, const uint64_t* seed_state, uint64_t offset,
                                    void* stream) {
-    if (!x || !y || !mask || !seed_state) return TAV_ERR_NULL;
-    if (n <= 0 || p < 0.f || p >= 1.f) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(dropout_fwd_dev_kernel, G1(n), x, y, mask, (long)n, p, seed_state, offset);
-    return tav_last_error();
+    if (const int rc = plan::dropout_validate(x && y && mask && seed_state, n, p)) return rc;
+    TAV_LAUNCH(dropout_fwd_dev_kernel, plan::grid1(n), stream, x, y, mask, (long)n, p, seed_state, offset);
+    return 0;
 }
 extern "C" int tav_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, int64_t n, float p, void* stream) {
-    if (!dy || !mask || !dx) return TAV_ERR_NULL;
-    if (n <= 0 || p < 0.f || p >= 1.f) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(dropout_bwd_kernel, G1(n), dy, mask, dx, (long)n, p);
-    return tav_last_error();
+    if (const int rc = plan::dropout_validate(dy && mask && dx, n, p)) return rc;
+    TAV_LAUNCH(dropout_bwd_kernel, plan::grid1(n), stream, dy, mask, dx, (long)n, p);
+    return 0;
 }
-extern "C" int tav_sumsq_partials(int32_t ntensors) { return ntensors * SUMSQ_BLOCKS; }
+extern "C" int tav_sumsq_partials(int32_t ntensors) { return plan::sumsq_partials(ntensors); }
 extern "C" int tav_sumsq_multi(const float* const* ptrs, const int64_t* sizes, int32_t ntensors, float* partials, float* out_sumsq, void* stream) {
-    if (!ptrs || !sizes || !partials || !out_sumsq) return TAV_ERR_NULL;
-    if (ntensors <= 0 || ntensors > 65535) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(sumsq_multi_kernel, dim3(SUMSQ_BLOCKS, ntensors), dim3(256), 0, ST, ptrs, sizes, partials);
-    hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, ST, partials, (long)ntensors * SUMSQ_BLOCKS, out_sumsq);
-    return tav_last_error();
+    if (const int rc = plan::multi_tensor_validate(ptrs && sizes && partials && out_sumsq, ntensors)) return rc;
+    TAV_LAUNCH(sumsq_multi_kernel, (plan::Launch{SUMSQ_BLOCKS, ntensors, 1, 256, 0}), stream, ptrs, sizes, partials);
+    TAV_LAUNCH(sum_final_kernel, ONE_BLOCK, stream, partials, (long)plan::sumsq_partials(ntensors), out_sumsq);
+    return 0;
 }
 extern "C" int tav_optim_chunk_elems(void) { return OPT_CHUNK; }
 extern "C" int tav_sumsq_chunked(const float* const* ptrs, const int64_t* sizes, const int32_t* chunk_prefix, int32_t ntensors, int32_t nchunks,
                                  float* partials, float* out_sumsq, void* stream) {
-    if (!ptrs || !sizes || !chunk_prefix || !partials || !out_sumsq) return TAV_ERR_NULL;
-    if (ntensors <= 0 || nchunks <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(sumsq_chunk_kernel, dim3(nchunks), dim3(256), 0, ST, ptrs, sizes, chunk_prefix, ntensors, partials);
-    hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, ST, partials, (long)nchunks, out_sumsq);
-    return tav_last_error();
+    if (const int rc = plan::chunked_validate(ptrs && sizes && chunk_prefix && partials && out_sumsq, ntensors, nchunks)) return rc;
+    TAV_LAUNCH(sumsq_chunk_kernel, (plan::Launch{nchunks, 1, 1, 256, 0}), stream, ptrs, sizes, chunk_prefix, ntensors, partials);
+    TAV_LAUNCH(sum_final_kernel, ONE_BLOCK, stream, partials, (long)nchunks, out_sumsq);
+    return 0;
 }
 // second stage of tav_sumsq_chunked on its own: a sharded optimizer computes the partials of the chunks it owns, the ranks exchange them, and every
 // rank adds the complete array here -- same kernel, same order, hence the same norm bit for bit as the replicated optimizer's
 extern "C" int tav_sum_partials(const float* partials, int64_t n, float* out, void* stream) {
-    if (!partials || !out) return TAV_ERR_NULL;
-    if (n <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, ST, partials, (long)n, out);
-    return tav_last_error();
+    if (const int rc = plan::count_validate(partials && out, n)) return rc;
+    TAV_LAUNCH(sum_final_kernel, ONE_BLOCK, stream, partials, (long)n, out);
+    return 0;
 }
 extern "C" int tav_adamw_chunked(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* sizes,
                                  const int32_t* chunk_prefix, int32_t ntensors, int32_t nchunks, const float* clip_coef, const float* lr, float beta1,
                                  float beta2, float eps, float weight_decay, int32_t* step, float* bias_corr, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !sizes || !chunk_prefix || !lr || !step || !bias_corr) return TAV_ERR_NULL;
-    if (ntensors <= 0 || nchunks <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, ST, step, beta1, beta2, bias_corr);
-    hipLaunchKernelGGL(adamw_chunk_kernel, dim3(nchunks), dim3(256), 0, ST, params, grads, exp_avg, exp_avg_sq, sizes, chunk_prefix, ntensors, clip_coef, lr,
-                       beta1, beta2, eps, weight_decay, (const float*)bias_corr);
-    return tav_last_error();
+    if (const int rc = plan::chunked_validate(params && grads && exp_avg && exp_avg_sq && sizes && chunk_prefix && lr && step && bias_corr, ntensors, nchunks)) return rc;
+    TAV_LAUNCH(adam_tick_kernel, ONE_THREAD, stream, step, beta1, beta2, bias_corr);
+    TAV_LAUNCH(adamw_chunk_kernel, (plan::Launch{nchunks, 1, 1, 256, 0}), stream, params, grads, exp_avg, exp_avg_sq, sizes, chunk_prefix, ntensors, clip_coef, lr,
+               beta1, beta2, eps, weight_decay, (const float*)bias_corr);
+    return 0;
 }
 extern "C" int tav_optim_max_groups(void) { return OPT_MAX_GROUPS; }
 extern "C" int tav_adamw_chunked_groups(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                                         const int64_t* sizes, const int32_t* chunk_prefix, int32_t ntensors, int32_t nchunks, const float* clip_coef,
                                         const int32_t* group_of, const float* hyper, int32_t ngroups, float beta1, float beta2, float eps, int32_t* step,
                                         float* bias_corr, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !sizes || !chunk_prefix || !group_of || !hyper || !step || !bias_corr) return TAV_ERR_NULL;
-    if (ntensors <= 0 || nchunks <= 0 || ngroups < 1 || ngroups > OPT_MAX_GROUPS) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, ST, step, beta1, beta2, bias_corr);
-    hipLaunchKernelGGL(adamw_chunk_groups_kernel, dim3(nchunks), dim3(256), 0, ST, params, grads, exp_avg, exp_avg_sq, sizes, chunk_prefix, ntensors, clip_coef,
-                       group_of, hyper, (int)ngroups, beta1, beta2, eps, (const float*)bias_corr);
-    return tav_last_error();
+    if (const int rc = plan::chunked_validate(params && grads && exp_avg && exp_avg_sq && sizes && chunk_prefix && group_of && hyper && step && bias_corr, ntensors,
+                                              nchunks, ngroups))
+        return rc;
+    TAV_LAUNCH(adam_tick_kernel, ONE_THREAD, stream, step, beta1, beta2, bias_corr);
+    TAV_LAUNCH(adamw_chunk_groups_kernel, (plan::Launch{nchunks, 1, 1, 256, 0}), stream, params, grads, exp_avg, exp_avg_sq, sizes, chunk_prefix, ntensors, clip_coef,
+               group_of, hyper, (int)ngroups, beta1, beta2, eps, (const float*)bias_corr);
+    return 0;
 }
 extern "C" int tav_clip_coef(const float* sumsq, float max_norm, float* coef_out, float* norm_out, void* stream) {
-    if (!sumsq || !coef_out) return TAV_ERR_NULL;
-    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, ST, sumsq, max_norm, coef_out, norm_out);
-    return tav_last_error();
+    if (const int rc = plan::ptrs_validate(sumsq && coef_out)) return rc;
+    TAV_LAUNCH(clip_coef_kernel, ONE_THREAD, stream, sumsq, max_norm, coef_out, norm_out);
+    return 0;
 }
 extern "C" int tav_adamw_multi(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* sizes,
                                int32_t ntensors, const float* clip_coef, const float* lr, float beta1, float beta2, float eps, float weight_decay,
                                int32_t* step, float* bias_corr, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !sizes || !lr || !step || !bias_corr) return TAV_ERR_NULL;
-    if (ntensors <= 0 || ntensors > 65535) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, ST, step, beta1, beta2, bias_corr);
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3(192, ntensors), dim3(256), 0, ST, params, grads, exp_avg, exp_avg_sq, sizes, clip_coef, lr, beta1, beta2, eps,
-                       weight_decay, (const float*)bias_corr);
-    return tav_last_error();
+    if (const int rc = plan::multi_tensor_validate(params && grads && exp_avg && exp_avg_sq && sizes && lr && step && bias_corr, ntensors)) return rc;
+    TAV_LAUNCH(adam_tick_kernel, ONE_THREAD, stream, step, beta1, beta2, bias_corr);
+    TAV_LAUNCH(adamw_multi_kernel, (plan::Launch{plan::ADAMW_MULTI_BLOCKS, ntensors, 1, 256, 0}), stream, params, grads, exp_avg, exp_avg_sq, sizes, clip_coef, lr, beta1,
+               beta2, eps, weight_decay, (const float*)bias_corr);
+    return 0;
 }

@@ -162,18 +162,6 @@ __global__ __launch_bounds__(256) void fp8_quantize_stream_kernel(const T* __res
         }
     }
 }
-template <typename T, bool DELAYED>
-static bool quantize_stream(const void* x, int64_t rows, int64_t cols, int64_t ld, float* scales, void* q, int64_t ld_q, hipStream_t st) {
-    // the streaming form needs 16-B aligned groups of 8 and 32-bit group indices
-    if (cols % 8 || ld % 8 || ld_q % 8 || rows * (cols / 8) >= (1ll << 31) || ((uintptr_t)x & 15) || ((uintptr_t)q & 7)) return false;
-    const long n8 = rows * (cols / 8);
-    long nb = (n8 + 256 * 4 - 1) / (256 * 4);
-    nb = nb < 1 ? 1 : (nb > 8192 ? 8192 : nb);
-    hipLaunchKernelGGL((fp8_quantize_stream_kernel<T, DELAYED>), dim3((unsigned)nb), dim3(256), 0, st, (const T*)x, scales, (uint8_t*)q, (unsigned)rows,
-                       (unsigned)(cols / 8), (long)ld, (long)ld_q);
-    return true;
-}
-
 // every state whose running maximum moved this step takes it over as its scale; the others (unused this step, or just calibrated) stay
 __global__ void fp8_roll_states_kernel(float* __restrict__ states, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -193,65 +181,58 @@ __global__ void fp8_splitk_reduce_kernel(const float* __restrict__ S, float* __r
     st4(out + i * 4, v);
 }
 
+// tav_fp8_quantize and its delayed-scaling form: the streaming kernel where there is no transposed copy and the operands allow it,
+// else the 64 x 64 tiles
+template <bool DELAYED>
+static int quantize(const void* x, int32_t dtype, int64_t rows, int64_t cols, int64_t ld, float* scales, void* q, int64_t ld_q, void* qt, int64_t ld_qt,
+                    int64_t rows_pad, void* stream) {
+    if (const int rc = plan::fp8_quantize_validate(x && scales && (q || qt), q, qt, dtype, rows, cols, ld, ld_q, ld_qt, rows_pad)) return rc;
+    const long rp = qt ? rows_pad : rows;
+    if (plan::fp8_can_stream(qt, (uintptr_t)x, (uintptr_t)q, rows, cols, ld, ld_q)) {
+        return floats::dispatch(dtype, [&](auto t) {
+            using T = decltype(t);
+            TAV_LAUNCH((fp8_quantize_stream_kernel<T, DELAYED>), plan::fp8_stream_launch(rows, cols), stream, (const T*)x, scales, (uint8_t*)q, (unsigned)rows,
+                       (unsigned)(cols / 8), (long)ld, (long)ld_q);
+            return 0;
+        });
+    }
+    return floats::dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((fp8_quantize_kernel<T, DELAYED>), plan::fp8_tile_launch(rp, cols), stream, (const T*)x, scales, (uint8_t*)q, (uint8_t*)qt, (int)rows, (int)cols,
+                   (long)ld, (long)ld_q, (long)ld_qt, (int)rp);
+        return 0;
+    });
+}
+
 }  // namespace tav
 using namespace tav;
-#define ST ((hipStream_t)stream)
 
-extern "C" int tav_fp8_amax_partials(int64_t rows, int64_t cols) {
-    const long n4 = rows * (cols / 4);
-    long nb = (n4 + 256 * 8 - 1) / (256 * 8);                 // >= 8 groups per thread
-    return (int)(nb < 1 ? 1 : (nb > 2048 ? 2048 : nb));
-}
+extern "C" int tav_fp8_amax_partials(int64_t rows, int64_t cols) { return plan::fp8_amax_partials(rows, cols); }
 extern "C" int tav_fp8_amax(const void* x, int32_t dtype, int64_t rows, int64_t cols, int64_t ld, float* partials, float* scales, void* stream) {
-    if (!x || !partials || !scales) return TAV_ERR_NULL;
-    if (rows <= 0 || cols <= 0 || cols % 4) return TAV_ERR_SHAPE;
-    if (ld % 4) return TAV_ERR_ALIGN;
-    const int nb = tav_fp8_amax_partials(rows, cols);
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((fp8_amax_partial_kernel<bf16>), dim3(nb), dim3(256), 0, ST, (const bf16*)x, partials, (long)rows, (int)(cols / 4), (long)ld);
-    else if (dtype == TAV_F32) hipLaunchKernelGGL((fp8_amax_partial_kernel<float>), dim3(nb), dim3(256), 0, ST, (const float*)x, partials, (long)rows, (int)(cols / 4), (long)ld);
-    else return TAV_ERR_DTYPE;
-    hipLaunchKernelGGL(fp8_amax_final_kernel, dim3(1), dim3(256), 0, ST, (const float*)partials, nb, scales);
-    return tav_last_error();
+    if (const int rc = plan::fp8_amax_validate(x && partials && scales, dtype, rows, cols, ld)) return rc;
+    const int nb = plan::fp8_amax_partials(rows, cols);
+    return floats::dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((fp8_amax_partial_kernel<T>), (plan::Launch{nb, 1, 1, 256, 0}), stream, (const T*)x, partials, (long)rows, (int)(cols / 4), (long)ld);
+        TAV_LAUNCH(fp8_amax_final_kernel, (plan::Launch{1, 1, 1, 256, 0}), stream, (const float*)partials, nb, scales);
+        return 0;
+    });
 }
 extern "C" int tav_fp8_quantize(const void* x, int32_t dtype, int64_t rows, int64_t cols, int64_t ld, const float* scales, void* q, int64_t ld_q,
                                 void* qt, int64_t ld_qt, int64_t rows_pad, void* stream) {
-    if (!x || !scales || (!q && !qt)) return TAV_ERR_NULL;
-    if (rows <= 0 || cols <= 0 || cols % 4) return TAV_ERR_SHAPE;
-    if (ld % 4 || (q && ld_q % 4) || (qt && (ld_qt % 4 || rows_pad % 4 || rows_pad < rows || ld_qt < rows_pad))) return TAV_ERR_ALIGN;
-    const long rp = qt ? rows_pad : rows;
-    dim3 grid(tav_cdiv(cols, 64), tav_cdiv(rp, 64));
-    float* sc = const_cast<float*>(scales);
-    if (!qt && dtype == TAV_BF16 && quantize_stream<bf16, false>(x, rows, cols, ld, sc, q, ld_q, ST)) return tav_last_error();
-    if (!qt && dtype == TAV_F32 && quantize_stream<float, false>(x, rows, cols, ld, sc, q, ld_q, ST)) return tav_last_error();
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((fp8_quantize_kernel<bf16, false>), grid, dim3(256), 0, ST, (const bf16*)x, sc, (uint8_t*)q, (uint8_t*)qt, (int)rows, (int)cols, (long)ld, (long)ld_q, (long)ld_qt, (int)rp);
-    else if (dtype == TAV_F32) hipLaunchKernelGGL((fp8_quantize_kernel<float, false>), grid, dim3(256), 0, ST, (const float*)x, sc, (uint8_t*)q, (uint8_t*)qt, (int)rows, (int)cols, (long)ld, (long)ld_q, (long)ld_qt, (int)rp);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    return quantize<false>(x, dtype, rows, cols, ld, const_cast<float*>(scales), q, ld_q, qt, ld_qt, rows_pad, stream);
 }
 extern "C" int tav_fp8_quantize_delayed(const void* x, int32_t dtype, int64_t rows, int64_t cols, int64_t ld, float* state, void* q, int64_t ld_q,
                                         void* qt, int64_t ld_qt, int64_t rows_pad, void* stream) {
-    if (!x || !state || (!q && !qt)) return TAV_ERR_NULL;
-    if (rows <= 0 || cols <= 0 || cols % 4) return TAV_ERR_SHAPE;
-    if (ld % 4 || (q && ld_q % 4) || (qt && (ld_qt % 4 || rows_pad % 4 || rows_pad < rows || ld_qt < rows_pad))) return TAV_ERR_ALIGN;
-    const long rp = qt ? rows_pad : rows;
-    dim3 grid(tav_cdiv(cols, 64), tav_cdiv(rp, 64));
-    if (!qt && dtype == TAV_BF16 && quantize_stream<bf16, true>(x, rows, cols, ld, state, q, ld_q, ST)) return tav_last_error();
-    if (!qt && dtype == TAV_F32 && quantize_stream<float, true>(x, rows, cols, ld, state, q, ld_q, ST)) return tav_last_error();
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((fp8_quantize_kernel<bf16, true>), grid, dim3(256), 0, ST, (const bf16*)x, state, (uint8_t*)q, (uint8_t*)qt, (int)rows, (int)cols, (long)ld, (long)ld_q, (long)ld_qt, (int)rp);
-    else if (dtype == TAV_F32) hipLaunchKernelGGL((fp8_quantize_kernel<float, true>), grid, dim3(256), 0, ST, (const float*)x, state, (uint8_t*)q, (uint8_t*)qt, (int)rows, (int)cols, (long)ld, (long)ld_q, (long)ld_qt, (int)rp);
-    else return TAV_ERR_DTYPE;
-    return tav_last_error();
+    return quantize<true>(x, dtype, rows, cols, ld, state, q, ld_q, qt, ld_qt, rows_pad, stream);
 }
 extern "C" int tav_fp8_roll_states(float* states, int64_t n, void* stream) {
-    if (!states) return TAV_ERR_NULL;
-    if (n <= 0) return TAV_ERR_SHAPE;
-    hipLaunchKernelGGL(fp8_roll_states_kernel, dim3(tav_cdiv(n, 256)), dim3(256), 0, ST, states, (int)n);
-    return tav_last_error();
+    if (const int rc = plan::count_validate(states, n)) return rc;
+    TAV_LAUNCH(fp8_roll_states_kernel, plan::grid1(n), stream, states, (int)n);
+    return 0;
 }
 extern "C" int tav_splitk_reduce(const float* slabs, float* out, int32_t nsplit, int64_t n_elems, int32_t accumulate, void* stream) {
-    if (!slabs || !out) return TAV_ERR_NULL;
-    if (nsplit <= 0 || n_elems <= 0 || n_elems % 4) return TAV_ERR_SHAPE;
-    const long n4 = n_elems / 4;
-    hipLaunchKernelGGL(fp8_splitk_reduce_kernel, dim3(tav_cdiv(n4, 256)), dim3(256), 0, ST, slabs, out, nsplit, n4, accumulate);
-    return tav_last_error();
+    if (const int rc = plan::splitk_reduce_validate(slabs && out, nsplit, n_elems)) return rc;
+    TAV_LAUNCH(fp8_splitk_reduce_kernel, plan::grid1(n_elems / 4), stream, slabs, out, nsplit, (long)(n_elems / 4), accumulate);
+    return 0;
 }

@@ -6,8 +6,11 @@
 #include "tavhip_internal.h"
 
 namespace tav {
+// defined with the host decisions (entry_plan.h)
+using plan::GN_SPLIT, plan::GN_CB, plan::GN_AR;
 
 constexpr int LN_MAXV = 4;   // float4 vectors per lane: W <= 64*4*4 = 1024
+static_assert(64 * 4 * LN_MAXV == plan::LN_MAX_W, "entry_plan.h mirrors this");
 
 struct LnP {
     const void* x; const float* gamma; const float* beta; float* y_f32; void* y_lp; float* mean; float* rstd;
@@ -200,20 +203,9 @@ __global__ __launch_bounds__(256) void ln_param_reduce_multi_kernel(const LnRedu
     }
 }
 
-// cap on workgroups of the LN backward (= rows of the dgamma/dbeta partial buffer).  Measured at 11712 x 768: 256 -> 35.5 us,
-// 512 -> 33.9 us, 1024 -> 38.0 us (more partial rows for ln_param_reduce); at 46848 x 768 (batch 32): 256 -> 157 us, 512 -> 106.5 us
-// (4.7 TB/s), 1024 -> 131 us, 2048 -> 136 us: one workgroup per CU keeps too few bytes in flight, four pay for their partial rows.
-constexpr int LN_MAX_BLOCKS = 512;
-static inline int ln_blocks(long rows) {
-    long b = (rows + 15) / 16;      // >= 4 rows per wave so the per-lane dgamma/dbeta partials amortise
-    return (int)(b < 1 ? 1 : (b > LN_MAX_BLOCKS ? LN_MAX_BLOCKS : b));
-}
-
 // ------------------------------------------------------------------------------------------------ group norm over time
 // x [B][T][C] channels-last.  forward: pivot pass (the mean of up to 32 sampled rows per (b, c)), statistics pass (partial sums over a T-slice
 // for GN_CB = 256 channels per workgroup, then a finalize), apply pass element-wise; backward: statistics, finalize, parameter gradients, apply.
-constexpr int GN_SPLIT = 32;
-constexpr int GN_CB = 256;       // channels per workgroup of the statistics pass
 constexpr int GN_PIVOT_ROWS = 32;   // rows the pivot of the forward statistics is averaged over
 
 // piv[b][c] = mean of n = min(T, GN_PIVOT_ROWS) rows of entry b spread evenly over it: rows ((2 i + 1) T) / (2 n), the middles of n equal
@@ -321,7 +313,6 @@ __global__ void gn_finalize_kernel(const float* __restrict__ part, float* out, c
 // Apply passes: thread = 4 channels (one 8-B / 16-B access per row) x GN_AR rows at a stride of 4, so the per-(batch, channel) statistics
 // and the affine parameters are loaded ONCE per thread as float4s and four rows' loads are in flight per thread.  (One element quad per
 // thread with 12-24 scalar parameter loads beside its one useful load ran at 3.8 TB/s on the 524 MB activation.)
-constexpr int GN_AR = 16;        // rows per thread of the apply passes (a workgroup covers 4 * GN_AR rows x 256 channels)
 template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, const float* __restrict__ stats, int Tn, int C) {
@@ -424,134 +415,105 @@ static LnP pack(const tav_ln_args* a) {
 }  // namespace tav
 using namespace tav;
 
-extern "C" int tav_ln_bwd_partials(int64_t rows) { return ln_blocks(rows); }
+extern "C" int tav_ln_bwd_partials(int64_t rows) { return plan::ln_blocks(rows); }
 
 extern "C" int tav_ln_fwd(const tav_ln_args* a, void* stream) {
-    if (!a || !a->x || !a->gamma || !a->beta || (!a->y_f32 && !a->y_lp)) return TAV_ERR_NULL;
-    if (a->rows <= 0 || a->W <= 0 || a->W > 1024 || a->W % 4) return TAV_ERR_SHAPE;
-    if (a->ld_x % 4 || a->ld_y % 4) return TAV_ERR_ALIGN;
+    if (const int rc = plan::ln_fwd_validate(a)) return rc;
     const LnP p = pack(a);
-    hipStream_t st = (hipStream_t)stream;
-    const long want = (a->rows + 3) / 4;
-    dim3 grid((unsigned)(want < 2048 ? want : 2048)), block(256);
-    const bool lp_bf16 = a->y_lp && a->lp_dtype == TAV_BF16;
-    if (a->x_dtype == TAV_F32) {
-        if (lp_bf16) hipLaunchKernelGGL((ln_fwd_kernel<float, bf16>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((ln_fwd_kernel<float, float>), grid, block, 0, st, p);
-    } else if (a->x_dtype == TAV_BF16) {
-        if (lp_bf16) hipLaunchKernelGGL((ln_fwd_kernel<bf16, bf16>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((ln_fwd_kernel<bf16, float>), grid, block, 0, st, p);
-    } else return TAV_ERR_DTYPE;
-    return (int)hipGetLastError();
+    const plan::Launch L = plan::ln_fwd_launch(a->rows);
+    using cases = dtypes<on<TAV_F32, TAV_BF16>, on<TAV_F32, TAV_F32>, on<TAV_BF16, TAV_BF16>, on<TAV_BF16, TAV_F32>>;
+    return cases::dispatch(a->x_dtype, plan::lp_code(a->y_lp, a->lp_dtype), [&](auto tx, auto tlp) {
+        TAV_LAUNCH((ln_fwd_kernel<decltype(tx), decltype(tlp)>), L, stream, p);
+        return 0;
+    });
 }
 
 extern "C" int tav_ln_bwd(const tav_ln_args* a, void* stream) {
-    if (!a || !a->x || !a->gamma || !a->dy || !a->mean || !a->rstd || (!a->dx_f32 && !a->dx_lp)) return TAV_ERR_NULL;
-    if (a->act == 1 && !a->beta) return TAV_ERR_NULL;
-    if ((a->dgamma || a->dbeta) && !a->partials) return TAV_ERR_NULL;
-    if (a->rows <= 0 || a->W <= 0 || a->W > 1024 || a->W % 4) return TAV_ERR_SHAPE;
-    if (a->ld_x % 4 || a->ld_dy % 4 || a->ld_dx % 4) return TAV_ERR_ALIGN;
+    if (const int rc = plan::ln_bwd_validate(a)) return rc;
     LnP p = pack(a);
     if (!a->dgamma && !a->dbeta && !a->defer_param_reduce) p.partials = nullptr;
-    if (a->defer_param_reduce && !a->partials) return TAV_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = ln_blocks(a->rows);
-    dim3 grid(nb), block(256);
-    const bool lp_bf16 = a->dx_lp && a->lp_dtype == TAV_BF16;
-#define TAV_LN_BWD(TX, TDY)                                                                              \
-    do {                                                                                                 \
-        if (lp_bf16) hipLaunchKernelGGL((ln_bwd_kernel<TX, TDY, bf16>), grid, block, 0, st, p);           \
-        else hipLaunchKernelGGL((ln_bwd_kernel<TX, TDY, float>), grid, block, 0, st, p);                  \
-    } while (0)
-    if (a->x_dtype == TAV_F32 && a->dy_dtype == TAV_F32) TAV_LN_BWD(float, float);
-    else if (a->x_dtype == TAV_F32 && a->dy_dtype == TAV_BF16) TAV_LN_BWD(float, bf16);
-    else if (a->x_dtype == TAV_BF16 && a->dy_dtype == TAV_F32) TAV_LN_BWD(bf16, float);
-    else if (a->x_dtype == TAV_BF16 && a->dy_dtype == TAV_BF16) TAV_LN_BWD(bf16, bf16);
-    else return TAV_ERR_DTYPE;
-#undef TAV_LN_BWD
-    int e = (int)hipGetLastError();
-    if (e) return e;
-    if (p.partials && !a->defer_param_reduce) {
-        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3(tav_cdiv(a->W, 16)), dim3(256), 0, st, a->partials, a->dgamma, a->dbeta, nb, (int)a->W,
-                           a->accumulate_params);
-        e = (int)hipGetLastError();
-    }
-    return e;
+    const plan::Launch L = plan::ln_bwd_launch(a->rows);
+    using cases = dtypes<on<TAV_F32, TAV_F32>, on<TAV_F32, TAV_BF16>, on<TAV_BF16, TAV_F32>, on<TAV_BF16, TAV_BF16>>;
+    const int rc = cases::dispatch(a->x_dtype, a->dy_dtype, [&](auto tx, auto tdy) {
+        return floats::dispatch(plan::lp_code(a->dx_lp, a->lp_dtype), [&](auto tlp) {
+            TAV_LAUNCH((ln_bwd_kernel<decltype(tx), decltype(tdy), decltype(tlp)>), L, stream, p);
+            return 0;
+        });
+    });
+    if (rc || !p.partials || a->defer_param_reduce) return rc;
+    TAV_LAUNCH(ln_param_reduce_kernel, plan::ln_reduce_launch(a->W), stream, a->partials, a->dgamma, a->dbeta, (int)L.gx, (int)a->W, a->accumulate_params);
+    return 0;
 }
 
 extern "C" int tav_ln_param_reduce_multi(const tav_ln_reduce_item* items, int32_t n, void* stream) {
-    if (!items) return TAV_ERR_NULL;
-    if (n <= 0 || n > TAV_LN_REDUCE_MAX) return TAV_ERR_SHAPE;
-    LnReduceBatch b;
     int wmax = 0;
-    for (int i = 0; i < n; ++i) {
-        const tav_ln_reduce_item& it = items[i];
-        if (!it.partials || (!it.dgamma && !it.dbeta)) return TAV_ERR_NULL;
-        if (it.W <= 0 || it.W > 1024 || it.W % 4 || it.nblocks <= 0 || it.nblocks > LN_MAX_BLOCKS) return TAV_ERR_SHAPE;
-        b.it[i] = it;
-        wmax = it.W > wmax ? it.W : wmax;
-    }
-    for (int i = n; i < TAV_LN_REDUCE_MAX; ++i) b.it[i] = tav_ln_reduce_item{nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    hipLaunchKernelGGL(ln_param_reduce_multi_kernel, dim3(tav_cdiv(wmax, 16), n), dim3(256), 0, (hipStream_t)stream, b);
-    return (int)hipGetLastError();
+    if (const int rc = plan::ln_reduce_validate(items, n, &wmax)) return rc;
+    LnReduceBatch b;
+    for (int i = 0; i < TAV_LN_REDUCE_MAX; ++i) b.it[i] = i < n ? items[i] : tav_ln_reduce_item{nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    TAV_LAUNCH(ln_param_reduce_multi_kernel, plan::ln_reduce_launch(wmax, n), stream, b);
+    return 0;
 }
 
-// [B][GN_SPLIT][C][2] partial sums, [B][C][2] sums of the backward, [B][C] pivots of the forward
-extern "C" int tav_gn_workspace_floats(int64_t B, int64_t C) { return (int)(B * GN_SPLIT * C * 2 + B * C * 2 + B * C); }
+extern "C" int tav_gn_workspace_floats(int64_t B, int64_t C) { return plan::gn_workspace_floats(B, C); }
 
 extern "C" int tav_gn_gelu_fwd(const void* x, void* y, int32_t dtype, const float* gamma, const float* beta, float* stats, float* workspace,
                                int64_t B, int64_t T, int64_t C, float eps, void* stream) {
-    if (!x || !y || !gamma || !beta || !stats || !workspace) return TAV_ERR_NULL;
-    if (B <= 0 || T <= 0 || C <= 0 || C % 64) return TAV_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)tav_cdiv(C, GN_CB), GN_SPLIT, (unsigned)B);
-    const dim3 agrid((unsigned)tav_cdiv(C, GN_CB), (unsigned)tav_cdiv(T, 4 * GN_AR), (unsigned)B);
-    if (dtype != TAV_BF16 && dtype != TAV_F32) return TAV_ERR_DTYPE;
-    float* piv = workspace + B * GN_SPLIT * C * 2 + B * C * 2;
-    const dim3 pgrid((unsigned)tav_cdiv(B * (C / 4), 8));
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_pivot_kernel<bf16>), pgrid, dim3(256), 0, st, (const bf16*)x, piv, (int)T, (int)C, (int)B);
-    else hipLaunchKernelGGL((gn_pivot_kernel<float>), pgrid, dim3(256), 0, st, (const float*)x, piv, (int)T, (int)C, (int)B);
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_stats_kernel<bf16, false>), grid, dim3(256), 0, st, (const bf16*)x, (const bf16*)nullptr, gamma, beta, stats, piv, workspace, (int)T, (int)C);
-    else hipLaunchKernelGGL((gn_stats_kernel<float, false>), grid, dim3(256), 0, st, (const float*)x, (const float*)nullptr, gamma, beta, stats, piv, workspace, (int)T, (int)C);
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, stats, piv, (int)T, (int)C, (int)B, eps, 1);
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_apply_fwd_kernel<bf16>), agrid, dim3(256), 0, st, (const bf16*)x, (bf16*)y, gamma, beta, stats, (int)T, (int)C);
-    else hipLaunchKernelGGL((gn_apply_fwd_kernel<float>), agrid, dim3(256), 0, st, (const float*)x, (float*)y, gamma, beta, stats, (int)T, (int)C);
-    return (int)hipGetLastError();
+    if (const int rc = plan::gn_validate(x && y && gamma && beta && stats && workspace, dtype, B, T, C)) return rc;
+    const plan::GnPlan P = plan::gn_plan(B, T, C);
+    float* piv = workspace + plan::gn_layout(B, C).piv;
+    // (one dispatch per typed launch: the kernels of both types then lie pairwise in the code object, where they have always lain)
+    int rc = floats::dispatch(dtype, [&](auto t) {
+        using E = decltype(t);
+        TAV_LAUNCH((gn_pivot_kernel<E>), P.pivot, stream, (const E*)x, piv, (int)T, (int)C, (int)B);
+        return 0;
+    });
+    if (!rc) rc = floats::dispatch(dtype, [&](auto t) {
+        using E = decltype(t);
+        TAV_LAUNCH((gn_stats_kernel<E, false>), P.stats, stream, (const E*)x, (const E*)nullptr, gamma, beta, stats, piv, workspace, (int)T, (int)C);
+        TAV_LAUNCH(gn_finalize_kernel, P.finalize, stream, workspace, stats, piv, (int)T, (int)C, (int)B, eps, 1);
+        return 0;
+    });
+    if (!rc) rc = floats::dispatch(dtype, [&](auto t) {
+        using E = decltype(t);
+        TAV_LAUNCH((gn_apply_fwd_kernel<E>), P.apply, stream, (const E*)x, (E*)y, gamma, beta, stats, (int)T, (int)C);
+        return 0;
+    });
+    return rc;
 }
 
 extern "C" int tav_gn_gelu_bwd(const void* x, const void* dy, void* dx, int32_t dtype, const float* gamma, const float* beta, const float* stats,
                                float* workspace, float* dgamma, float* dbeta, int64_t B, int64_t T, int64_t C, int32_t accumulate, void* stream) {
-    if (!x || !dy || !dx || !gamma || !beta || !stats || !workspace || !dgamma || !dbeta) return TAV_ERR_NULL;
-    if (B <= 0 || T <= 0 || C <= 0 || C % 64) return TAV_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)tav_cdiv(C, GN_CB), GN_SPLIT, (unsigned)B);
-    const dim3 agrid((unsigned)tav_cdiv(C, GN_CB), (unsigned)tav_cdiv(T, 4 * GN_AR), (unsigned)B);
-    float* sums = workspace + B * GN_SPLIT * C * 2;
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_stats_kernel<bf16, true>), grid, dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, gamma, beta, stats, (const float*)nullptr, workspace, (int)T, (int)C);
-    else if (dtype == TAV_F32) hipLaunchKernelGGL((gn_stats_kernel<float, true>), grid, dim3(256), 0, st, (const float*)x, (const float*)dy, gamma, beta, stats, (const float*)nullptr, workspace, (int)T, (int)C);
-    else return TAV_ERR_DTYPE;
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(tav_cdiv(B * C, 256)), dim3(256), 0, st, workspace, sums, (const float*)nullptr, (int)T, (int)C, (int)B, 0.f, 0);
-    hipLaunchKernelGGL(gn_param_grad_kernel, dim3(tav_cdiv(C, 256)), dim3(256), 0, st, sums, dgamma, dbeta, (int)B, (int)C, accumulate);
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gn_apply_bwd_kernel<bf16>), agrid, dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, (bf16*)dx, gamma, beta, stats, sums, (int)T, (int)C);
-    else hipLaunchKernelGGL((gn_apply_bwd_kernel<float>), agrid, dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, gamma, beta, stats, sums, (int)T, (int)C);
-    return (int)hipGetLastError();
+    if (const int rc = plan::gn_validate(x && dy && dx && gamma && beta && stats && workspace && dgamma && dbeta, dtype, B, T, C)) return rc;
+    const plan::GnPlan P = plan::gn_plan(B, T, C);
+    float* sums = workspace + plan::gn_layout(B, C).sums;
+    int rc = floats::dispatch(dtype, [&](auto t) {
+        using E = decltype(t);
+        TAV_LAUNCH((gn_stats_kernel<E, true>), P.stats, stream, (const E*)x, (const E*)dy, gamma, beta, stats, (const float*)nullptr, workspace, (int)T, (int)C);
+        TAV_LAUNCH(gn_finalize_kernel, P.finalize, stream, workspace, sums, (const float*)nullptr, (int)T, (int)C, (int)B, 0.f, 0);
+        TAV_LAUNCH(gn_param_grad_kernel, P.param, stream, sums, dgamma, dbeta, (int)B, (int)C, accumulate);
+        return 0;
+    });
+    if (!rc) rc = floats::dispatch(dtype, [&](auto t) {
+        using E = decltype(t);
+        TAV_LAUNCH((gn_apply_bwd_kernel<E>), P.apply, stream, (const E*)x, (const E*)dy, (E*)dx, gamma, beta, stats, sums, (int)T, (int)C);
+        return 0;
+    });
+    return rc;
 }
 
 extern "C" int tav_gelu_fwd(const void* x, void* y, int32_t dtype, int64_t n, void* stream) {
-    if (!x || !y) return TAV_ERR_NULL;
-    if (n <= 0 || n % 4) return TAV_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gelu_fwd_kernel<bf16>), dim3(tav_cdiv(n / 4, 256)), dim3(256), 0, st, (const bf16*)x, (bf16*)y, n / 4);
-    else if (dtype == TAV_F32) hipLaunchKernelGGL((gelu_fwd_kernel<float>), dim3(tav_cdiv(n / 4, 256)), dim3(256), 0, st, (const float*)x, (float*)y, n / 4);
-    else return TAV_ERR_DTYPE;
-    return (int)hipGetLastError();
+    if (const int rc = plan::gelu_validate(x && y, dtype, n)) return rc;
+    return floats::dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((gelu_fwd_kernel<T>), plan::grid1(n / 4), stream, (const T*)x, (T*)y, n / 4);
+        return 0;
+    });
 }
 extern "C" int tav_gelu_bwd(const void* x, const void* dy, void* dx, int32_t dtype, int64_t n, void* stream) {
-    if (!x || !dy || !dx) return TAV_ERR_NULL;
-    if (n <= 0 || n % 4) return TAV_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == TAV_BF16) hipLaunchKernelGGL((gelu_bwd_kernel<bf16>), dim3(tav_cdiv(n / 4, 256)), dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, (bf16*)dx, n / 4);
-    else if (dtype == TAV_F32) hipLaunchKernelGGL((gelu_bwd_kernel<float>), dim3(tav_cdiv(n / 4, 256)), dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, n / 4);
-    else return TAV_ERR_DTYPE;
-    return (int)hipGetLastError();
+    if (const int rc = plan::gelu_validate(x && dy && dx, dtype, n)) return rc;
+    return floats::dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        TAV_LAUNCH((gelu_bwd_kernel<T>), plan::grid1(n / 4), stream, (const T*)x, (const T*)dy, (T*)dx, n / 4);
+        return 0;
+    });
 }

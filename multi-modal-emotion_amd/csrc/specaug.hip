@@ -6,10 +6,8 @@
 #include "tavhip_internal.h"
 
 namespace tav {
-
-constexpr int SPEC_T = 256;              // threads of a draw workgroup
-constexpr int SPEC_MAX_SPANS = 128;      // chosen starts kept in LDS
-constexpr uint64_t SPEC_EPS_STRIDE = 1ull << 40;      // a tag owns the 2^40 indices behind it; its epsilon draw is the word after them
+// defined with the host decisions (entry_plan.h)
+using plan::SPEC_T, plan::SPEC_MAX_SPANS, plan::SPEC_EPS_STRIDE;
 
 struct SpecKey { uint64_t key; int s; };
 TAV_DEV bool spec_less(uint64_t ka, int sa, uint64_t kb, int sb) { return ka < kb || (ka == kb && sa < sb); }
@@ -106,8 +104,6 @@ __global__ void specaug_fwd_kernel(const float* __restrict__ x, const uint8_t* _
 
 // Workgroup (x, p): four channels per thread, the rows [p * rpb, (p + 1) * rpb) in order.  Writes dx and, with `partials`, the part's column
 // sums over the time-masked rows; the final kernel adds the parts in order -- no atomics, the same bits on every run.
-constexpr int SPEC_ROWS = 32;
-constexpr int SPEC_MAX_PARTS = 1024;
 __global__ __launch_bounds__(256) void specaug_bwd_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ tmask, const uint8_t* __restrict__ fmask,
                                                           float* __restrict__ dx, float* __restrict__ partials, long rows, int T, int H4, int rpb) {
     const int c4 = blockIdx.x * 256 + threadIdx.x;
@@ -142,73 +138,39 @@ __global__ void specaug_bwd_final_kernel(const float* __restrict__ partials, flo
 }  // namespace tav
 using namespace tav;
 
-#define ST ((hipStream_t)stream)
-
-static bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-static int specaug_draw_check(const uint8_t* mask, int64_t B, int64_t L, float prob, int64_t length, int64_t min_masks) {
-    if (!mask) return TAV_ERR_NULL;
-    if (B < 1 || L < 1 || length < 1 || min_masks < 0 || B > 0x7fffffff || L > 0x7fffffff || length > 0x7fffffff || min_masks > 0x7fffffff ||
-        !(prob >= 0.f) || !(prob <= 1.f) || B * L > (int64_t)SPEC_EPS_STRIDE)
-        return TAV_ERR_SHAPE;
-    // the most spans a row can take: the kernel's n0 at len = L with eps replaced by its supremum (each rounded operation is monotone)
-    const float top = floorf(((prob * (float)L) / (float)length) + 1.0f);
-    int64_t cap = (int64_t)top > min_masks ? (int64_t)top : min_masks;
-    if (L / length < cap) cap = L / length;
-    return cap > SPEC_MAX_SPANS ? TAV_ERR_SHAPE : 0;
-}
-
 extern "C" int tav_specaug_draw(const uint8_t* valid, uint8_t* mask, int32_t* nspans, int64_t B, int64_t L, float prob, int64_t length,
                                 int64_t min_masks, uint64_t seed, uint64_t tag, void* stream) {
-    const int bad = specaug_draw_check(mask, B, L, prob, length, min_masks);
-    if (bad) return bad;
-    hipLaunchKernelGGL(specaug_draw_kernel, dim3((unsigned)B), dim3(SPEC_T), 0, ST, valid, mask, nspans, (int)L, prob, (int)length, (int)min_masks, seed,
-                       (const uint64_t*)nullptr, tag);
-    return tav_last_error();
+    if (const int rc = plan::specaug_draw_validate(mask, B, L, prob, length, min_masks)) return rc;
+    TAV_LAUNCH(specaug_draw_kernel, (plan::Launch{B, 1, 1, SPEC_T, 0}), stream, valid, mask, nspans, (int)L, prob, (int)length, (int)min_masks, seed,
+               (const uint64_t*)nullptr, tag);
+    return 0;
 }
 extern "C" int tav_specaug_draw_dev(const uint8_t* valid, uint8_t* mask, int32_t* nspans, int64_t B, int64_t L, float prob, int64_t length,
                                     int64_t min_masks, const uint64_t* seed_state, uint64_t tag, void* stream) {
-    if (!seed_state) return TAV_ERR_NULL;
-    const int bad = specaug_draw_check(mask, B, L, prob, length, min_masks);
-    if (bad) return bad;
-    hipLaunchKernelGGL(specaug_draw_kernel, dim3((unsigned)B), dim3(SPEC_T), 0, ST, valid, mask, nspans, (int)L, prob, (int)length, (int)min_masks,
-                       (uint64_t)0, seed_state, tag);
-    return tav_last_error();
-}
-
-static int specaug_shape_check(int64_t B, int64_t T, int64_t H) {
-    return (B < 1 || T < 1 || H < 1 || H % 4 || H > 0x7fffffff || T > 0x7fffffff || B > 0x7fffffff || B * T > (int64_t)1 << 40) ? TAV_ERR_SHAPE : 0;
+    if (const int rc = plan::specaug_draw_validate(seed_state && mask, B, L, prob, length, min_masks)) return rc;
+    TAV_LAUNCH(specaug_draw_kernel, (plan::Launch{B, 1, 1, SPEC_T, 0}), stream, valid, mask, nspans, (int)L, prob, (int)length, (int)min_masks, (uint64_t)0,
+               seed_state, tag);
+    return 0;
 }
 
 extern "C" int tav_specaug_fwd(const float* x, const uint8_t* tmask, const uint8_t* fmask, const float* embed, float* y, int64_t B, int64_t T,
                                int64_t H, void* stream) {
-    if (!x || !y || (tmask && !embed)) return TAV_ERR_NULL;
-    if (specaug_shape_check(B, T, H)) return TAV_ERR_SHAPE;
-    if (!aligned(x, 16) || !aligned(y, 16) || !aligned(embed, 16) || !aligned(fmask, 4)) return TAV_ERR_ALIGN;
+    const bool al = plan::aligned(x, 16) && plan::aligned(y, 16) && plan::aligned(embed, 16) && plan::aligned(fmask, 4);
+    if (const int rc = plan::specaug_fwd_validate(x && y && (!tmask || embed), al, B, T, H)) return rc;
     const long n4 = B * T * (H / 4);
-    hipLaunchKernelGGL(specaug_fwd_kernel, dim3(tav_cdiv(n4, 256)), dim3(256), 0, ST, x, tmask, fmask, embed, y, n4, (int)T, (int)(H / 4));
-    return tav_last_error();
+    TAV_LAUNCH(specaug_fwd_kernel, plan::grid1(n4), stream, x, tmask, fmask, embed, y, n4, (int)T, (int)(H / 4));
+    return 0;
 }
 
-static int specaug_bwd_parts(int64_t rows) {
-    const int64_t p = (rows + SPEC_ROWS - 1) / SPEC_ROWS;
-    return (int)(p > SPEC_MAX_PARTS ? SPEC_MAX_PARTS : (p < 1 ? 1 : p));
-}
-extern "C" int64_t tav_specaug_bwd_ws_bytes(int64_t rows, int64_t H) {
-    if (rows < 1 || H < 1) return 0;
-    return (int64_t)specaug_bwd_parts(rows) * H * (int64_t)sizeof(float);
-}
+extern "C" int64_t tav_specaug_bwd_ws_bytes(int64_t rows, int64_t H) { return plan::specaug_bwd_ws_bytes(rows, H); }
 extern "C" int tav_specaug_bwd(const float* dy, const uint8_t* tmask, const uint8_t* fmask, float* dx, float* dembed, void* workspace,
                                int64_t workspace_bytes, int64_t B, int64_t T, int64_t H, void* stream) {
-    if (!dy || !dx || (dembed && !workspace)) return TAV_ERR_NULL;
-    if (specaug_shape_check(B, T, H)) return TAV_ERR_SHAPE;
+    const bool al = plan::aligned(dy, 16) && plan::aligned(dx, 16) && plan::aligned(dembed, 16) && plan::aligned(workspace, 16) && plan::aligned(fmask, 4);
+    if (const int rc = plan::specaug_bwd_validate(dy && dx && (!dembed || workspace), al, dembed, workspace_bytes, B, T, H)) return rc;
     const int64_t rows = B * T;
-    if (dembed && workspace_bytes < tav_specaug_bwd_ws_bytes(rows, H)) return TAV_ERR_SHAPE;
-    if (!aligned(dy, 16) || !aligned(dx, 16) || !aligned(dembed, 16) || !aligned(workspace, 16) || !aligned(fmask, 4)) return TAV_ERR_ALIGN;
-    const int nparts = specaug_bwd_parts(rows), H4 = (int)(H / 4);
-    const int rpb = (int)((rows + nparts - 1) / nparts);
+    const plan::PartsPlan P = plan::specaug_bwd_plan(rows, H);
     float* partials = dembed ? (float*)workspace : nullptr;
-    hipLaunchKernelGGL(specaug_bwd_kernel, dim3(tav_cdiv(H4, 256), nparts), dim3(256), 0, ST, dy, tmask, fmask, dx, partials, (long)rows, (int)T, H4, rpb);
-    if (dembed) hipLaunchKernelGGL(specaug_bwd_final_kernel, dim3(tav_cdiv(H4, 64)), dim3(64), 0, ST, (const float*)partials, dembed, nparts, H4);
-    return tav_last_error();
+    TAV_LAUNCH(specaug_bwd_kernel, P.partial, stream, dy, tmask, fmask, dx, partials, (long)rows, (int)T, (int)(H / 4), P.rows_per_part);
+    if (dembed) TAV_LAUNCH(specaug_bwd_final_kernel, P.final_, stream, (const float*)partials, dembed, P.parts, (int)(H / 4));
+    return 0;
 }

@@ -10,9 +10,8 @@
 #include "tavhip_internal.h"
 
 namespace tav {
-
-constexpr int VX_TW = 32, VX_TH = 8;      // output tile of a workgroup: 32 columns (128-B store segments per channel plane) x 8 rows
-constexpr int VX_MAX = 16384;             // sizes up to here keep (2 o + 1) n_in inside int32
+// defined with the host decisions (entry_plan.h)
+using plan::VX_TW, plan::VX_TH;
 
 // the source taps of one output coordinate along one axis: n = 2 intermediate pixels (1 without a first resize), each with two source indices
 struct VxAxis {
@@ -102,31 +101,13 @@ __global__ __launch_bounds__(VX_TW * VX_TH) void video_clip_transform_kernel(con
 }  // namespace tav
 using namespace tav;
 
-static bool vx_size_ok(int32_t v) { return v >= 1 && v <= VX_MAX; }
-
 extern "C" int tav_video_clip_transform(const void* src, float* dst, const tav_clip_xform* x, void* stream) {
-    if (!src || !dst || !x) return TAV_ERR_NULL;
-    if (x->src_dtype != TAV_U8 && x->src_dtype != TAV_F32) return TAV_ERR_DTYPE;
-    if (x->T < 1 || !vx_size_ok(x->H) || !vx_size_ok(x->W) || !vx_size_ok(x->out_h) || !vx_size_ok(x->out_w)) return TAV_ERR_SHAPE;
-    if (x->sT < 0 || x->sH < 0 || x->sW < 0 || x->sC < 0) return TAV_ERR_SHAPE;
-    if (x->nf < 1 || x->nf > 32) return TAV_ERR_SHAPE;
-    for (int i = 0; i < x->nf; ++i)
-        if (x->frame[i] < 0 || x->frame[i] >= x->T) return TAV_ERR_SHAPE;
-    if (!vx_size_ok(x->crop_h) || !vx_size_ok(x->crop_w) || x->crop_top < 0 || x->crop_left < 0 || x->crop_top > x->H - x->crop_h ||
-        x->crop_left > x->W - x->crop_w)
-        return TAV_ERR_SHAPE;
-    if (x->mid_h != 0 || x->mid_w != 0)
-        if (!vx_size_ok(x->mid_h) || !vx_size_ok(x->mid_w)) return TAV_ERR_SHAPE;
-    const dim3 grid(tav_cdiv(x->out_w, VX_TW), tav_cdiv(x->out_h, VX_TH), (unsigned)x->nf);
-    const dim3 block(VX_TW * VX_TH);
-    const hipStream_t st = (hipStream_t)stream;
-    const bool two = x->mid_h != 0;
-    if (x->src_dtype == TAV_U8) {
-        if (two) hipLaunchKernelGGL((video_clip_transform_kernel<uint8_t, 2>), grid, block, 0, st, (const uint8_t*)src, dst, *x);
-        else hipLaunchKernelGGL((video_clip_transform_kernel<uint8_t, 1>), grid, block, 0, st, (const uint8_t*)src, dst, *x);
-    } else {
-        if (two) hipLaunchKernelGGL((video_clip_transform_kernel<float, 2>), grid, block, 0, st, (const float*)src, dst, *x);
-        else hipLaunchKernelGGL((video_clip_transform_kernel<float, 1>), grid, block, 0, st, (const float*)src, dst, *x);
-    }
-    return tav_last_error();
+    if (const int rc = plan::video_clip_validate(src && dst && x, x)) return rc;
+    const plan::Launch L = plan::video_clip_launch(x);
+    return dtypes<on<TAV_U8>, on<TAV_F32>>::dispatch(x->src_dtype, [&](auto t) {
+        using T = decltype(t);
+        if (x->mid_h != 0) TAV_LAUNCH((video_clip_transform_kernel<T, 2>), L, stream, (const T*)src, dst, *x);      // two resizes
+        else TAV_LAUNCH((video_clip_transform_kernel<T, 1>), L, stream, (const T*)src, dst, *x);
+        return 0;
+    });
 }

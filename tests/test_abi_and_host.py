@@ -5,6 +5,8 @@ import ctypes as C
 import math
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -751,3 +753,91 @@ def test_bucket_norm_is_used_only_when_the_gradients_live_in_the_buckets():
     opt.norm_buffers = [flat[:19]]                              # the bucket holds 3 elements that are nobody's gradient
     opt._norm_ok_key = None
     assert not opt._grads_in_norm_buffers(ps)
+
+
+# ---- include/tavhip.h against the ctypes binding: a wrong argtype or field order is memory corruption, not an error
+_STRUCTS = {"tav_gemm_nt_args": "GemmNTArgs", "tav_gemm_tn_args": "GemmTNArgs", "tav_gemm_tn_problem": "GemmTNProblem", "tav_attn_args": "AttnArgs",
+            "tav_ln_args": "LnArgs", "tav_ln_reduce_item": "LnReduceItem", "tav_text_embed_args": "TextEmbedArgs", "tav_clip_xform": "ClipXform",
+            "tav_resample_args": "ResampleArgs"}
+_SCALARS = {"int": "int32", "int32_t": "int32", "int64_t": "int64", "uint64_t": "uint64", "float": "float", "double": "double"}
+
+
+def _c_class(decl):
+    """Class of a C type as the header writes it: pointer, char*, int32, int64, uint64, float, double."""
+    t = " ".join(decl.replace("const", " ").split())
+    if "*" in t:
+        return "char*" if t.replace(" ", "") == "char*" else "pointer"
+    return _SCALARS[t]
+
+
+def _ctypes_class(t):
+    if t is C.c_char_p:
+        return "char*"
+    if t is C.c_void_p or hasattr(t, "contents") or isinstance(t, type(C.POINTER(C.c_int))):
+        return "pointer"
+    return {C.c_int32: "int32", C.c_int64: "int64", C.c_uint64: "uint64", C.c_float: "float", C.c_double: "double"}[t]
+
+
+def _parse_header():
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tavhip.h")).read(), flags=re.S)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            m = re.match(r"(.*?[\s\*])(\w+(?:\[\d+\])?(?:\s*,\s*\w+(?:\[\d+\])?)*)$", decl, flags=re.S)
+            assert m, decl
+            for item in m.group(2).split(","):
+                fname, _, dim = item.strip().partition("[")
+                fields.append((fname, _c_class(m.group(1)), int(dim[:-1]) if dim else 0))
+        structs[name] = fields
+    protos = {}
+    for res, name, args in re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(tav_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+        args = [a.strip() for a in args.split(",")]
+        if args == ["void"]:
+            args = []
+        kinds = []
+        for a in args:
+            m = re.match(r"(.*?[\s\*])(\w+)$", a, flags=re.S)             # type, then the parameter's name
+            kinds.append((_c_class(m.group(1)), next((s for s in structs if re.search(r"\b%s\b" % s, m.group(1))), None)))
+        protos[name] = (_c_class(res), kinds)
+    return structs, protos
+
+
+def test_binding_matches_the_header_type_by_type(tmp_path):
+    """Every prototype of include/tavhip.h against _lib._SIGS (arity, result and argument classes, which struct a struct pointer points to),
+    every struct against its ctypes Structure (field names, order, classes, array lengths), and sizeof / offsetof of every struct as a C
+    compiler lays it out."""
+    structs, protos = _parse_header()
+    assert set(protos) == set(_lib._SIGS) and len(protos) >= 90
+    for name, (res, args) in protos.items():
+        cres, cargs = _lib._SIGS[name]
+        assert _ctypes_class(cres) == res, f"{name}: result {cres} vs {res}"
+        assert len(cargs) == len(args), f"{name}: {len(cargs)} argtypes, {len(args)} parameters"
+        for k, (ct, (kind, struct)) in enumerate(zip(cargs, args)):
+            assert _ctypes_class(ct) == kind, f"{name}: argument {k} is {ct}, the header says {kind}"
+            if struct in _STRUCTS:
+                assert ct._type_ is getattr(_lib, _STRUCTS[struct]), f"{name}: argument {k} points to {ct._type_}, the header says {struct}"
+    assert set(_STRUCTS) <= set(structs)
+    for cname, pyname in _STRUCTS.items():
+        cls = getattr(_lib, pyname)
+        assert [f[0] for f in cls._fields_] == [f[0] for f in structs[cname]], cname
+        for (fname, ct), (_, kind, dim) in zip(cls._fields_, structs[cname]):
+            if dim:
+                assert ct._length_ == dim and _ctypes_class(ct._type_) == kind, f"{cname}.{fname}"
+            else:
+                assert _ctypes_class(ct) == kind, f"{cname}.{fname}"
+    cc = next((p for p in (shutil.which(c) for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang")) if p), None)
+    assert cc is not None, "no host C compiler: the library was built here, so one exists"
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "tavhip.h"', 'int main(void) {']
+    for cname in _STRUCTS:
+        lines.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'    printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _, _ in structs[cname]]
+    lines += ['    return 0;', '}']
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
+    laid = dict(ln.split() for ln in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
+    for cname, pyname in _STRUCTS.items():
+        cls = getattr(_lib, pyname)
+        assert C.sizeof(cls) == int(laid[cname]), f"sizeof({cname})"
+        for f, _ in cls._fields_:
+            assert getattr(cls, f).offset == int(laid[f"{cname}.{f}"]), f"offsetof({cname}, {f})"
