@@ -176,6 +176,29 @@ _SIGS = {
     "tav_adamw_chunked_groups": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp]),
 }
 
+# include/tavhip_align.h: the forced-alignment entry points.  A table of their own, bound by lib() like _SIGS but not part of
+# declared_symbols(): the symbol set of include/tavhip.h is pinned by a recorded table ("alignment ABI").
+ALIGN_ABI_VERSION = 1
+
+
+class AlignPlan(C.Structure):
+    _fields_ = [("block", i32), ("tokens_per_thread", i32), ("frames_per_stage", i32), ("bits_frames", i32), ("lds_bytes", i64), ("ws_bytes_per_row", i64)]
+
+
+class CtcAlignArgs(C.Structure):
+    _fields_ = [("emission", vp), ("tokens", vp), ("n_frames", vp), ("n_tokens", vp), ("trellis", vp), ("path_token", vp), ("path_prob", vp),
+                ("seg", vp), ("seg_score", vp), ("span", vp), ("workspace", vp), ("workspace_bytes", i64),
+                ("B", i64), ("Tmax", i64), ("Nmax", i64), ("V", i64), ("ld", i64), ("blank_id", i32), ("reserved", i32)]
+
+
+_ALIGN_SIGS = {
+    "tav_align_version": (C.c_int, []),
+    "tav_ctc_log_softmax": (C.c_int, [vp, vp, i64, i64, i64, i64, vp]),
+    "tav_ctc_align_plan": (C.c_int, [i64, i64, i64, C.POINTER(AlignPlan)]),
+    "tav_ctc_align_ws_bytes": (C.c_int64, [i64, i64, i64, i64]),
+    "tav_ctc_align": (C.c_int, [C.POINTER(CtcAlignArgs), vp]),
+}
+
 _lib = None
 
 
@@ -188,11 +211,14 @@ def lib():
                 f"{LIB_PATH} is missing: the TAV hot path has no fallback. Build it with "
                 "`make -C multi-modal-emotion_amd/csrc` (hipcc --offload-arch=gfx950).")
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(h, name)      # AttributeError here = header/library mismatch
-            fn.restype, fn.argtypes = res, args
+        for table in (_SIGS, _ALIGN_SIGS):
+            for name, (res, args) in table.items():
+                fn = getattr(h, name)      # AttributeError here = header/library mismatch
+                fn.restype, fn.argtypes = res, args
         if h.tav_version() != ABI_VERSION:
             raise RuntimeError(f"libtavhip ABI {h.tav_version()} != binding {ABI_VERSION}; rebuild")
+        if h.tav_align_version() != ALIGN_ABI_VERSION:
+            raise RuntimeError(f"libtavhip alignment ABI {h.tav_align_version()} != binding {ALIGN_ABI_VERSION}; rebuild")
         _lib = h
     return _lib
 

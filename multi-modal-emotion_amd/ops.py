@@ -3,6 +3,7 @@
 No arithmetic happens here; torch is used for device memory and streams only.  Scratch buffers are cached per
 (name, stream) so that concurrent branches on different HIP streams never share a workspace.
 """
+import collections
 import ctypes as C
 import math
 
@@ -1143,3 +1144,84 @@ def weight_norm_bwd(v, g, norms, dw_gemm):
     dg = torch.empty(K, dtype=torch.float32, device=v.device)
     check(lib().tav_weight_norm_bwd(ptr(v), ptr(g), ptr(norms), ptr(dw_gemm), ptr(wsb), ptr(dv), ptr(dg), H, Cg, K, 0, stream()), "weight_norm_bwd")
     return dv, dg
+
+
+# ---------------------------------------------------------------------------------------------- forced alignment (include/tavhip_align.h)
+CtcAlignment = collections.namedtuple("CtcAlignment", "path_token path_prob seg seg_score span trellis")
+
+
+def ctc_align_plan(T, N, V):
+    """tav_ctc_align_plan as a dict: block, tokens_per_thread, frames_per_stage, bits_frames, lds_bytes, ws_bytes_per_row."""
+    p = L.AlignPlan()
+    check(lib().tav_ctc_align_plan(int(T), int(N), int(V), C.byref(p)), "ctc_align_plan")
+    return {name: int(getattr(p, name)) for name, _ in L.AlignPlan._fields_}
+
+
+def _rows_2d(x, what):
+    """(rows, row stride) of a tensor whose last dimension is dense and whose leading dimensions lie at one pitch."""
+    if x.dim() < 2 or x.stride(-1) != 1 or x.dtype != torch.float32:
+        raise ValueError(f"{what}: a float32 tensor [..., W] with a dense last dimension is needed, got {tuple(x.shape)} {x.dtype} strides {x.stride()}")
+    ld, rows = x.stride(-2), 1
+    for d in range(x.dim() - 2, -1, -1):
+        if x.shape[d] != 1 and x.stride(d) != ld * rows:
+            raise ValueError(f"{what}: the rows of {tuple(x.shape)} (strides {x.stride()}) do not lie at one pitch")
+        rows *= x.shape[d]
+    return rows, ld
+
+
+def ctc_log_softmax(logits, V=None, out=None):
+    """tav_ctc_log_softmax: the row log-softmax over the first V columns of logits [..., W] (V = W by default).  Columns [V, W) are neither
+    read nor written (a new `out` keeps whatever its allocation held there)."""
+    W = logits.shape[-1]
+    V = W if V is None else int(V)
+    R, ld_in = _rows_2d(logits, "ctc_log_softmax")
+    if out is None:
+        out = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
+    if out.shape != logits.shape or out.device != logits.device:
+        raise ValueError(f"ctc_log_softmax: out {tuple(out.shape)} on {out.device} for logits {tuple(logits.shape)} on {logits.device}")
+    _, ld_out = _rows_2d(out, "ctc_log_softmax (out)")
+    if not logits.is_cuda:
+        raise ValueError("ctc_log_softmax runs on the GPU only (libtavhip has no host form)")
+    check(lib().tav_ctc_log_softmax(ptr(logits), ptr(out), R, V, ld_in, ld_out, stream()), "ctc_log_softmax")
+    return out
+
+
+def ctc_align(emission, tokens, n_frames, n_tokens, *, V=None, blank_id=0, want_trellis=False, out=None, _enqueue=None):
+    """tav_ctc_align, one launch for the batch: emission f32 [B, Tmax, W] log-probabilities (V valid columns, V = W by default), tokens int32
+    [B, Nmax], n_frames / n_tokens int32 [B] (all on the device) -> CtcAlignment(path_token [B, Tmax] i32, path_prob [B, Tmax] f32,
+    seg [B, Nmax, 2] i32, seg_score [B, Nmax] f32, span [B, 4] i32, trellis [B, Tmax + 1, Nmax + 1] f32 or None); include/tavhip_align.h
+    says what they hold.  `out`: a CtcAlignment of contiguous tensors to fill instead of new ones.  Nothing is read back: a row that
+    failed to align says so in span[:, 3] bit 0.  `_enqueue`: a list that receives the argument struct and everything it points to."""
+    if not emission.is_cuda:
+        raise ValueError("ctc_align runs on the GPU only (libtavhip has no host form)")
+    if emission.dim() != 3 or tokens.dim() != 2 or tokens.dtype != torch.int32 or n_frames.dtype != torch.int32 or n_tokens.dtype != torch.int32:
+        raise ValueError("ctc_align: emission [B, Tmax, W] float32, tokens [B, Nmax] int32, n_frames and n_tokens [B] int32")
+    B, Tmax, W = emission.shape
+    Nmax = tokens.shape[1]
+    V = W if V is None else int(V)
+    rows, ld = _rows_2d(emission, "ctc_align")
+    if tokens.shape[0] != B or n_frames.numel() != B or n_tokens.numel() != B or not (tokens.is_contiguous() and n_frames.is_contiguous() and n_tokens.is_contiguous()):
+        raise ValueError("ctc_align: tokens, n_frames and n_tokens must be contiguous and have one row per utterance")
+    dev = emission.device
+    if out is None:
+        out = CtcAlignment(torch.empty(B, Tmax, dtype=torch.int32, device=dev), torch.empty(B, Tmax, dtype=torch.float32, device=dev),
+                           torch.empty(B, Nmax, 2, dtype=torch.int32, device=dev), torch.empty(B, Nmax, dtype=torch.float32, device=dev),
+                           torch.empty(B, 4, dtype=torch.int32, device=dev),
+                           torch.empty(B, Tmax + 1, Nmax + 1, dtype=torch.float32, device=dev) if want_trellis else None)
+    shapes = ((B, Tmax), (B, Tmax), (B, Nmax, 2), (B, Nmax), (B, 4), (B, Tmax + 1, Nmax + 1))
+    for name, t, shape in zip(CtcAlignment._fields, out, shapes):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"ctc_align: out.{name} must be a contiguous {shape} tensor on {dev}, got {tuple(t.shape)} strides {t.stride()}")
+    nbytes = lib().tav_ctc_align_ws_bytes(B, Tmax, Nmax, V)
+    if nbytes < 0:
+        check(int(nbytes), "ctc_align")
+    ws = workspace("ctc_align", (nbytes + 3) // 4, dev) if nbytes else None
+    a = L.CtcAlignArgs()
+    a.emission, a.tokens, a.n_frames, a.n_tokens = ptr(emission), ptr(tokens), ptr(n_frames), ptr(n_tokens)
+    a.trellis, a.path_token, a.path_prob, a.seg, a.seg_score, a.span = ptr(out.trellis), ptr(out.path_token), ptr(out.path_prob), ptr(out.seg), ptr(out.seg_score), ptr(out.span)
+    a.workspace, a.workspace_bytes = ptr(ws), (ws.numel() * 4 if ws is not None else 0)
+    a.B, a.Tmax, a.Nmax, a.V, a.ld, a.blank_id = B, Tmax, Nmax, V, ld, int(blank_id)
+    if _enqueue is not None:                   # (tools/gpu_align_speed.py times the entry point without this wrapper's host work)
+        _enqueue.append((a, ws, emission, tokens, n_frames, n_tokens, out))
+    check(lib().tav_ctc_align(C.byref(a), stream()), "ctc_align")
+    return out

@@ -1,0 +1,107 @@
+// csrc/align_plan.h alone, as a host program (tests/test_ctc_align_host.py builds it with ASan + UBSan): sweeps (T, N, V) up to the limits
+// and checks what a launch relies on.  Prints "FAILED ..." per broken invariant and ends with "ok: 0 failed checks".
+#include <stdio.h>
+#include <vector>
+#include "../../multi-modal-emotion_amd/csrc/align_plan.h"
+
+using namespace tav::plan;
+static int failed = 0;
+#define CHECK(cond, ...)                                \
+    do {                                                \
+        if (!(cond)) {                                  \
+            ++failed;                                   \
+            printf("FAILED %s : ", #cond);              \
+            printf(__VA_ARGS__);                        \
+            printf("\n");                               \
+        }                                               \
+    } while (0)
+
+int main() {
+    const std::vector<int64_t> Ts = {1, 2, 3, 63, 64, 65, 128, 499, 714, 715, 1499, 3000, 4095, ALIGN_MAX_T};
+    const std::vector<int64_t> Ns = {1, 2, 62, 63, 64, 65, 127, 128, 129, 254, 255, 256, 300, 1022, 1023, 1024, 1025, 2046, 2047, ALIGN_MAX_N};
+    const std::vector<int64_t> Vs = {1, 2, 5, 29, 31, 32, 33, 64, 65, 127, ALIGN_MAX_V};
+    long plans = 0, in_ws = 0;
+    for (int64_t T : Ts)
+        for (int64_t N : Ns)
+            for (int64_t V : Vs) {
+                CHECK(align_shape_validate(T, N, V) == 0, "T %ld N %ld V %ld", (long)T, (long)N, (long)V);
+                const AlignPlan P = align_plan(T, N, V);
+                ++plans;
+                CHECK(P.lds_bytes <= 160 * 1024 && P.lds_bytes <= ALIGN_LDS_MAX, "lds %ld at T %ld N %ld V %ld", (long)P.lds_bytes, (long)T, (long)N, (long)V);
+                CHECK(P.block % 64 == 0 && P.block >= 64 && P.block <= ALIGN_MAX_BLOCK, "block %d", P.block);
+                CHECK(P.tpt >= 1 && P.tpt <= ALIGN_MAX_TPT, "tpt %d", P.tpt);
+                CHECK((int64_t)P.block * P.tpt >= N + 1, "block %d x %d does not cover N + 1 = %ld", P.block, P.tpt, (long)(N + 1));
+                CHECK((int64_t)(P.block - 64) * P.tpt < N + 1, "block %d x %d: a whole wave beyond N + 1 = %ld", P.block, P.tpt, (long)(N + 1));
+                CHECK(P.nwords == P.block / 64 * P.tpt && P.block / 64 <= 16, "nwords %d", P.nwords);
+                CHECK(P.stage_frames >= 4 && P.stage_frames % 4 == 0 && (int64_t)P.stage_frames * V <= ALIGN_STAGE_ELEMS, "stage %d at V %ld", P.stage_frames, (long)V);
+                // a stage fits the registers that carry it: ALIGN_PREFETCH per thread up to ALIGN_SMALL_BLOCK threads, ALIGN_PREFETCH_BIG beyond
+                const int regs = P.block <= ALIGN_SMALL_BLOCK ? ALIGN_PREFETCH : ALIGN_PREFETCH_BIG;
+                CHECK((int64_t)regs * P.block >= (int64_t)P.stage_frames * V, "stage of %ld elements, %d threads x %d registers", (long)(P.stage_frames * V), P.block, regs);
+                // the carve-up: increasing, 16-byte aligned, each area as large as its use, ending at lds_bytes
+                const int64_t off[] = {P.off_stage, P.off_seam, P.off_misc, P.off_path, P.off_prob, P.off_segs, P.off_bits, P.lds_bytes};
+                const int64_t need[] = {2 * P.stage_frames * V * 4, 2 * 16 * 4, 5 * 4, T * 2, T * 4, (N + 1) * 4, (int64_t)P.bits_frames * P.nwords * 8};
+                CHECK(off[0] == 0, "first offset %ld", (long)off[0]);
+                for (int i = 0; i < 7; ++i) {
+                    CHECK(off[i] % 16 == 0, "offset %d = %ld", i, (long)off[i]);
+                    CHECK(off[i + 1] - off[i] >= need[i], "area %d: %ld bytes for %ld", i, (long)(off[i + 1] - off[i]), (long)need[i]);
+                }
+                CHECK(P.bits_frames >= 1 && P.bits_frames <= T, "bits_frames %d at T %ld", P.bits_frames, (long)T);
+                if (P.ws_row_bytes == 0) {
+                    CHECK(P.bits_frames == T, "no workspace but %d of %ld frames in LDS", P.bits_frames, (long)T);
+                } else {
+                    ++in_ws;
+                    CHECK(P.ws_row_bytes == T * P.nwords * 8, "ws row %ld", (long)P.ws_row_bytes);
+                    CHECK(T * P.nwords * 8 > ALIGN_LDS_MAX - P.off_bits, "workspace although the words fit");
+                }
+                // workspace rows: increasing offsets that end at the advertised size
+                for (int64_t B : {(int64_t)1, (int64_t)5, (int64_t)32, ALIGN_MAX_B}) {
+                    const int64_t total = align_ws_bytes(B, T, N, V);
+                    CHECK(total == B * P.ws_row_bytes, "ws %ld for B %ld", (long)total, (long)B);
+                    int64_t end = 0;
+                    for (int64_t b = 0; b < (B < 40 ? B : 40); ++b) {
+                        CHECK(b * P.ws_row_bytes == end && end % 8 == 0, "row %ld starts at %ld", (long)b, (long)(b * P.ws_row_bytes));
+                        end = (b + 1) * P.ws_row_bytes;
+                    }
+                    CHECK((B - 1) * P.ws_row_bytes + P.ws_row_bytes == total, "last row ends at %ld of %ld", (long)(B * P.ws_row_bytes), (long)total);
+                }
+                tav_align_plan pub;
+                align_plan_public(P, &pub);
+                CHECK(pub.block == P.block && pub.tokens_per_thread == P.tpt && pub.frames_per_stage == P.stage_frames && pub.bits_frames == P.bits_frames &&
+                          pub.lds_bytes == P.lds_bytes && pub.ws_bytes_per_row == P.ws_row_bytes, "public plan");
+            }
+    CHECK(in_ws > 0 && in_ws < plans, "%ld of %ld plans use the workspace", in_ws, plans);
+    // the limits
+    CHECK(align_shape_validate(ALIGN_MAX_T + 1, 1, 32) == TAV_ERR_SHAPE && align_shape_validate(1, ALIGN_MAX_N + 1, 32) == TAV_ERR_SHAPE &&
+              align_shape_validate(1, 1, ALIGN_MAX_V + 1) == TAV_ERR_SHAPE && align_shape_validate(0, 1, 32) == TAV_ERR_SHAPE &&
+              align_shape_validate(1, 0, 32) == TAV_ERR_SHAPE && align_shape_validate(1, 1, 0) == TAV_ERR_SHAPE, "limits");
+    CHECK(ALIGN_MAX_T >= 3000 && ALIGN_MAX_N >= 2048, "limits below what the entry promises");
+    CHECK(align_ws_bytes(0, 10, 10, 32) == TAV_ERR_SHAPE && align_ws_bytes(ALIGN_MAX_B + 1, 10, 10, 32) == TAV_ERR_SHAPE &&
+              align_ws_bytes(1, ALIGN_MAX_T + 1, 10, 32) == TAV_ERR_SHAPE, "ws limits");
+    // the validator: pointers, then sizes, then strides
+    {
+        alignas(8) int dummy = 0;
+        tav_ctc_align_args a = {};
+        AlignPlan P;
+        CHECK(align_validate(nullptr, &P) == TAV_ERR_NULL && align_validate(&a, &P) == TAV_ERR_NULL, "null");
+        a.emission = (const float*)&dummy; a.tokens = a.n_frames = a.n_tokens = &dummy; a.path_token = a.seg = a.span = &dummy;
+        a.path_prob = a.seg_score = (float*)&dummy;
+        a.B = 2; a.Tmax = 100; a.Nmax = 20; a.V = 29; a.ld = 32;
+        CHECK(align_validate(&a, &P) == 0 && P.block == 64, "plain");
+        tav_ctc_align_args b = a; b.span = nullptr;  CHECK(align_validate(&b, &P) == TAV_ERR_NULL, "span");
+        b = a; b.B = 0;                              CHECK(align_validate(&b, &P) == TAV_ERR_SHAPE, "B");
+        b = a; b.ld = 28;                            CHECK(align_validate(&b, &P) == TAV_ERR_SHAPE, "V > ld");
+        b = a; b.ld = 30;                            CHECK(align_validate(&b, &P) == TAV_ERR_ALIGN, "ld not a multiple of 4");
+        b = a; b.ld = 30; b.Tmax = ALIGN_MAX_T + 1;  CHECK(align_validate(&b, &P) == TAV_ERR_SHAPE, "shape before alignment");
+        b = a; b.blank_id = 29;                      CHECK(align_validate(&b, &P) == TAV_ERR_SHAPE, "blank");
+        b = a; b.Tmax = 1200; b.Nmax = 1100;         CHECK(align_validate(&b, &P) == TAV_ERR_NULL, "workspace missing");
+        b.workspace = &dummy; b.workspace_bytes = 8; CHECK(align_validate(&b, &P) == TAV_ERR_SHAPE, "workspace small");
+        b.workspace_bytes = 2 * P.ws_row_bytes;      CHECK(align_validate(&b, &P) == 0, "workspace");
+    }
+    CHECK(log_softmax_validate(false, 1, 1, 1, 1) == TAV_ERR_NULL && log_softmax_validate(true, 0, 1, 1, 1) == TAV_ERR_SHAPE &&
+              log_softmax_validate(true, 4, 29, 28, 32) == TAV_ERR_SHAPE && log_softmax_validate(true, 4, 29, 32, 28) == TAV_ERR_SHAPE &&
+              log_softmax_validate(true, 4, LSM_MAX_V + 1, 1 << 20, 1 << 20) == TAV_ERR_SHAPE && log_softmax_validate(true, 5, 29, 29, 33) == 0, "log-softmax");
+    CHECK(log_softmax_blocks(1) == 1 && log_softmax_blocks(4) == 1 && log_softmax_blocks(5) == 2, "log-softmax grid");
+    printf("plans %ld in_ws %ld\n", plans, in_ws);
+    printf("ok: %d failed checks\n", failed);
+    return failed ? 1 : 0;
+}
