@@ -1,5 +1,6 @@
 """Drop-in for the reference's SingleModels/text_nn.py (text-only entrypoint, BASELINE.json configs[0]): same main() / runModel()
-shape and CLI flags.  The reference tokenises a dataset pickle (text_nn.py:28-57); offline, batches come from synthetic.make_batch
+shape and CLI flags; `--model LSTM --lstm_layers L --hidden_layers H` trains the reference's LSTMClassifier baseline (hyper_parameter_config/
+lstm.yaml), with `--synthetic` on a seeded random vector table of width H.  The reference tokenises a dataset pickle (text_nn.py:28-57); offline, batches come from synthetic.make_batch
 with the contract of its DataLoader: ({"input_ids": int64 [b,1,S], "attention_mask": float [b,S]}, labels)."""
 import numpy as np
 import torch
@@ -8,8 +9,15 @@ from torch.utils.data import DataLoader, Dataset
 from .. import config as C
 from .. import runtime, synthetic
 from ..utils.global_functions import CrossEntropyLoss, Metrics, NewCrossEntropyLoss, arg_parse
-from .models.text import BertClassifier
+from .models.text import BertClassifier, LSTMClassifier
 from .train_model.text_training import TextTrainStep, get_statistics
+
+
+class SyntheticVectors:
+    """Stands in for torchtext's GloVe offline: `.vectors` is a seeded normal table [vocab, width] at GloVe's scale (std 0.4)."""
+
+    def __init__(self, vocab, width, seed):
+        self.vectors = torch.randn(vocab, width, generator=torch.Generator().manual_seed(seed)) * 0.4
 
 
 class SyntheticTextBatches(Dataset):
@@ -35,7 +43,10 @@ def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
     else:
         criterion = NewCrossEntropyLoss(class_weights=param_dict["weights"].to(device), epoch_switch=param_dict["epoch_switch"])
     Metric = Metrics(num_classes=model_param["output_dim"], id2label=param_dict["id2label"], rank=device)
-    model = BertClassifier(model_param).to(device)
+    if model_param.get("model") == "LSTM":
+        model = LSTMClassifier(model_param["glove_vec"], model_param).to(device)
+    else:
+        model = BertClassifier(model_param).to(device)
     step = TextTrainStep(model, criterion, lr=param_dict["lr"], weight_decay=param_dict["weight_decay"], clip=param_dict["clip"])
     for epoch in range(param_dict["epoch"]):
         total = 0.0
@@ -63,7 +74,13 @@ def main(argv=None):
                   "weight_decay": args.weight_decay, "loss": args.loss, "epoch_switch": args.epoch_switch,
                   "weights": torch.linspace(0.6, 0.95, args.output_dim), "id2label": id2label}
     model_param = {"output_dim": args.output_dim, "dropout": args.dropout}
-    mk = lambda n, seed: SyntheticTextBatches(cfg, n, args.batch_size, seed)   # noqa: E731
+    s_text = 128
+    if args.model == "LSTM":
+        from .models.text import _first_hidden
+        model_param.update(model="LSTM", lstm_layers=args.lstm_layers, hidden_layers=args.hidden_layers,
+                           glove_vec=SyntheticVectors(cfg["text"]["vocab"], _first_hidden(args.hidden_layers), args.seed))
+        s_text = 70                                                            # the reference pads every utterance to 70 tokens for this model
+    mk = lambda n, seed: SyntheticTextBatches(cfg, n, args.batch_size, seed, s_text)   # noqa: E731
     return runModel("cuda", mk(args.synthetic, 1000), mk(max(args.batch_size, args.synthetic // 4), 2000), None, param_dict, model_param)
 
 

@@ -11,7 +11,12 @@ def get_statistics(input, label, model, criterion, Metric, check="train", epoch=
     label = label.to(dev)
     mask = input["attention_mask"].to(dev)
     input_id = input["input_ids"].squeeze(1).to(dev)                      # reference :20
-    output = model(input_id, mask, check)
+    if getattr(model, "LSTM_layers", None) is not None:                   # LSTMClassifier.forward(x): dropout follows model.training
+        if model.training != (check == "train"):
+            model.train(check == "train")
+        output = model(input_id)
+    else:
+        output = model(input_id, mask, check)
     if Metric is not None:
         Metric.update_metrics(torch.argmax(output, dim=1), label.long())
     if criterion is None:

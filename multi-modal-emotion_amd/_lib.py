@@ -199,6 +199,37 @@ _ALIGN_SIGS = {
     "tav_ctc_align": (C.c_int, [C.POINTER(CtcAlignArgs), vp]),
 }
 
+# include/tavhip_rnn.h: the recurrent entry points (LSTM recurrence, log-sigmoid).  A third table, bound like _ALIGN_SIGS and for the
+# same reason outside declared_symbols().
+RNN_ABI_VERSION = 1
+
+
+class LstmPlan(C.Structure):
+    _fields_ = [("block", i32), ("rows_per_wg", i32), ("Hp", i32), ("tiles_per_wave", i32), ("lds_bytes", i64), ("ws_gates_off", i64),
+                ("ws_cell_off", i64), ("ws_bytes", i64)]
+
+
+class LstmFwdArgs(C.Structure):
+    _fields_ = [("xproj", vp), ("w_hh", vp), ("b_hh", vp), ("h0", vp), ("c0", vp), ("y", vp), ("workspace", vp), ("workspace_bytes", i64),
+                ("B", i64), ("T", i64), ("H", i64), ("xp_stride_b", i64), ("xp_stride_t", i64), ("dtype", i32), ("reserved", i32)]
+
+
+class LstmBwdArgs(C.Structure):
+    _fields_ = [("dy", vp), ("dh_T", vp), ("dc_T", vp), ("w_hh_t", vp), ("workspace", vp), ("workspace_bytes", i64), ("dz", vp), ("dh0", vp),
+                ("dc0", vp), ("dc_trace", vp), ("B", i64), ("T", i64), ("H", i64), ("dy_stride_b", i64), ("dy_stride_t", i64),
+                ("dz_stride_b", i64), ("dz_stride_t", i64), ("dtype", i32), ("reserved", i32)]
+
+
+_RNN_SIGS = {
+    "tav_rnn_version": (C.c_int, []),
+    "tav_lstm_get_plan": (C.c_int, [i64, i64, i64, i32, C.POINTER(LstmPlan)]),
+    "tav_lstm_ws_bytes": (C.c_int64, [i64, i64, i64, i32]),
+    "tav_lstm_fwd": (C.c_int, [C.POINTER(LstmFwdArgs), vp]),
+    "tav_lstm_bwd": (C.c_int, [C.POINTER(LstmBwdArgs), vp]),
+    "tav_logsigmoid_fwd": (C.c_int, [vp, vp, i64, vp]),
+    "tav_logsigmoid_bwd": (C.c_int, [vp, vp, vp, i64, vp]),
+}
+
 _lib = None
 
 
@@ -211,7 +242,7 @@ def lib():
                 f"{LIB_PATH} is missing: the TAV hot path has no fallback. Build it with "
                 "`make -C multi-modal-emotion_amd/csrc` (hipcc --offload-arch=gfx950).")
         h = C.CDLL(LIB_PATH)
-        for table in (_SIGS, _ALIGN_SIGS):
+        for table in (_SIGS, _ALIGN_SIGS, _RNN_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(h, name)      # AttributeError here = header/library mismatch
                 fn.restype, fn.argtypes = res, args
@@ -219,6 +250,8 @@ def lib():
             raise RuntimeError(f"libtavhip ABI {h.tav_version()} != binding {ABI_VERSION}; rebuild")
         if h.tav_align_version() != ALIGN_ABI_VERSION:
             raise RuntimeError(f"libtavhip alignment ABI {h.tav_align_version()} != binding {ALIGN_ABI_VERSION}; rebuild")
+        if h.tav_rnn_version() != RNN_ABI_VERSION:
+            raise RuntimeError(f"libtavhip recurrent ABI {h.tav_rnn_version()} != binding {RNN_ABI_VERSION}; rebuild")
         _lib = h
     return _lib
 

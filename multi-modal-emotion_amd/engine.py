@@ -164,6 +164,40 @@ class WeightCache:
         self.d[key] = (ver, val, aux, self._refs(params))
         return val
 
+    def lstm(self, w_ih, w_hh, b_ih, b_hh):
+        """Padded operands of one LSTM layer (include/tavhip_rnn.h, padding rule): each gate block of W_ih [4H, E] and W_hh [4H, H] padded to
+        Hp = ceil(H / 64) 64 rows, the columns to Ep / Hp, pads zero -> (W_ih [4Hp, Ep], its transpose, W_hh [4Hp, Hp], its transpose, in the
+        operand dtype; b_ih, b_hh f32 [4Hp])."""
+        def build():
+            H, E_ = w_hh.shape[1], w_ih.shape[1]
+            Hp, Ep, dev, lp = (H + 63) // 64 * 64, (E_ + 63) // 64 * 64, w_hh.device, self.pol.lp
+            wi_n, wi_t = torch.zeros(4 * Hp, Ep, dtype=lp, device=dev), torch.zeros(Ep, 4 * Hp, dtype=lp, device=dev)
+            wh_n, wh_t = torch.zeros(4 * Hp, Hp, dtype=lp, device=dev), torch.zeros(Hp, 4 * Hp, dtype=lp, device=dev)
+            bi, bh = ops.zeros_f32((4 * Hp,), dev), ops.zeros_f32((4 * Hp,), dev)
+            for q in range(4):
+                rows, prow = slice(q * H, (q + 1) * H), slice(q * Hp, q * Hp + H)
+                ops.cast_weight(w_ih.detach()[rows], lp, out_n=wi_n[prow, :E_], out_t=wi_t[:E_, prow])
+                ops.cast_weight(w_hh.detach()[rows], lp, out_n=wh_n[prow, :H], out_t=wh_t[:H, prow])
+                for b, dst in ((b_ih, bi), (b_hh, bh)):
+                    if b is not None:
+                        ops.cast_weight(b.detach()[rows].view(1, H), torch.float32, want_t=False, out_n=dst[prow].view(1, H))
+            return wi_n, wi_t, wh_n, wh_t, bi, bh
+        return self._get(("lstm", id(w_hh)), (w_ih, w_hh, b_ih, b_hh), build)
+
+    def padded_f32(self, w, rows, cols, b=None):
+        """An f32 copy of w [R, C] (and of b [R]) zero-padded to [rows, cols] ([rows]): the frozen embedding table at the padded width, the
+        classifier head at four-row granularity."""
+        def build():
+            R, Cc = w.shape
+            wp = ops.zeros_f32((rows, cols), w.device)
+            ops.cast_weight(w.detach(), torch.float32, want_t=False, out_n=wp[:R, :Cc])
+            bp = None
+            if b is not None:
+                bp = ops.zeros_f32((rows,), w.device)
+                ops.cast_weight(b.detach().view(1, R), torch.float32, want_t=False, out_n=bp[:R].view(1, R))
+            return wp, bp
+        return self._get(("pad32", id(w), rows, cols), (w, b), build)
+
     def fp8_state(self, param, tag):
         """(Fp8States, key) of one quantisation site: the tensor `tag` produced next to `param` (a layer's wq identifies the layer)."""
         if self._fp8_states is None:
@@ -513,6 +547,110 @@ class LinearFn(torch.autograd.Function):
             dx = ops.gemm_nt(gy_lp, w_t, out_dtype=torch.float32 if ctx.in_f32 else pol.lp)
         d_res = gy if ctx.needs_input_grad[4] else None
         return (dx if ctx.in_f32 else None, None if ctx.in_f32 else dx, dW, dB, d_res, None, None)
+
+
+def _unpad_gates(wp, H, cols):
+    """[4Hp, >= cols] -> [4H, cols]: the gate blocks without their pad rows (a copy; no arithmetic)."""
+    Hp = wp.shape[0] // 4
+    if Hp == H and wp.shape[1] == cols:
+        return wp
+    return torch.cat([wp[q * Hp:q * Hp + H, :cols] for q in range(4)], 0)
+
+
+class LstmLayerFn(torch.autograd.Function):
+    """One nn.LSTM layer (one direction) on time-major rows: x [T B, Ep] (f32 or the operand dtype, columns padded to Ep = ceil(E / 64) 64
+    with zeros) -> (y [T B, Hp] in the operand dtype, h_T, c_T f32 [B, Hp]).  Forward: the projection x W_ih^T + b_ih as one GEMM, then
+    tav_lstm_fwd.  Backward: tav_lstm_bwd, then dW_hh and dW_ih as weight-gradient GEMMs over the T B rows (h_{t-1} is the view [0, T) of the
+    forward's y), the bias gradients as one column sum, dx as the projection's dgrad.  h0 / c0: optional f32 [B, Hp], pads zero."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, h0, c0, ectx, B, T):
+        pol = ectx.pol
+        if pol.fp8:
+            raise ValueError(f"the LSTM recurrence runs under the bf16 and fp32 policies; {pol.name!r} has no e4m3 form of it")
+        H = w_hh.shape[1]
+        x = _c(x)
+        x_lp = x if x.dtype == pol.lp else _to_lp(pol, x)
+        wi_n, _, wh_n, _, bi, bh = ectx.cache.lstm(w_ih, w_hh, b_ih, b_hh)
+        Hp = wh_n.shape[1]
+        if x_lp.shape != (T * B, wi_n.shape[1]):
+            raise ValueError(f"LstmLayerFn: x must be [T B, {wi_n.shape[1]}] = [{T * B}, {wi_n.shape[1]}], got {tuple(x_lp.shape)}")
+        xproj = ops.gemm_nt(x_lp, wi_n, bias=bi, out_dtype=pol.lp)
+        saved = ops.lstm_fwd(xproj.view(T, B, 4 * Hp), wh_n, bh, _c(h0), _c(c0), H=H, time_major=True)
+        ctx.ectx, ctx.saved, ctx.x_dtype, ctx.dims = ectx, saved, x.dtype, (B, T, H, Hp)
+        ctx.save_for_backward(x_lp, w_ih, w_hh, b_ih, b_hh)
+        ctx.set_materialize_grads(False)
+        h_T, c_T = ops.cast2d(saved.y[T], torch.float32), ops.cast2d(ops.lstm_cells(saved)[T], torch.float32)      # (copies: y and the workspace stay whole)
+        return saved.y[1:].view(T * B, Hp), h_T, c_T
+
+    @staticmethod
+    def backward(ctx, gy, gh_T, gc_T):
+        pol, saved = ctx.ectx.pol, ctx.saved
+        B, T, H, Hp = ctx.dims
+        x_lp, w_ih, w_hh, b_ih, b_hh = ctx.saved_tensors
+        _, wi_t, _, wh_t, _, _ = ctx.ectx.cache.lstm(w_ih, w_hh, b_ih, b_hh)
+        if gy is None:
+            gy = torch.zeros(T * B, Hp, dtype=pol.lp, device=x_lp.device)
+        gy = _c(gy)
+        gy_lp = gy if gy.dtype == pol.lp else _to_lp(pol, gy)
+        need_state = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]
+        dz, dh0, dc0, _ = ops.lstm_bwd(saved, gy_lp.view(T, B, Hp), wh_t, _c(gh_T), _c(gc_T), time_major=True, dz_time_major=True, want_state_grads=need_state)
+        dz = dz.view(T * B, 4 * Hp)
+        dW_ih = dW_hh = db = dx = None
+        if ctx.needs_input_grad[1]:
+            dW_ih = _unpad_gates(ops.gemm_tn(dz, x_lp), H, w_ih.shape[1])
+        if ctx.needs_input_grad[2]:
+            dW_hh = _unpad_gates(ops.gemm_tn(dz, saved.y[:T].view(T * B, Hp)), H, H)
+        if (b_ih is not None and ctx.needs_input_grad[3]) or (b_hh is not None and ctx.needs_input_grad[4]):
+            db = _unpad_gates(ops.colsum(dz).view(4 * Hp, 1), H, 1).view(4 * H)
+        if ctx.needs_input_grad[0]:
+            dx = ops.gemm_nt(dz, wi_t, out_dtype=ctx.x_dtype)
+        return (dx, dW_ih, dW_hh, db if b_ih is not None and ctx.needs_input_grad[3] else None, db if b_hh is not None and ctx.needs_input_grad[4] else None,
+                dh0 if ctx.needs_input_grad[5] else None, dc0 if ctx.needs_input_grad[6] else None, None, None, None)
+
+
+class LstmTailFn(torch.autograd.Function):
+    """The tail of the reference's LSTMClassifier on time-major rows y [T B, Hp]: fc2 -> dropout(p) -> mean over T -> LogSigmoid, from
+    tav_head_*, tav_dropout_*, tav_mean_pool_* and tav_logsigmoid_*.  The head runs at Op = ceil(O / 4) 4 zero-padded rows so that the pool's
+    width B Op is a multiple of 4; the pad columns are dropped from the result."""
+
+    @staticmethod
+    def forward(ctx, y, w, b, p_drop, seed, ectx, B, T):
+        pol = ectx.pol
+        O, H = w.shape
+        Op = (O + 3) // 4 * 4
+        y = _c(y)
+        y32 = y if y.dtype == torch.float32 else ops.cast2d(y, torch.float32)
+        wp, bp = ectx.cache.padded_f32(w, Op, y32.shape[1], b)
+        z = ops.head_fwd(y32, wp, bp)                                                   # [T B, Op]
+        mask = None
+        if p_drop > 0.0:
+            z, mask = ops.dropout_fwd(z, p_drop, seed, 0)
+        pooled = ops.mean_pool_fwd(z.view(T, B * Op), 1, T).view(B, Op)                 # one "batch entry" of T rows: the mean over time
+        out = ops.logsigmoid_fwd(pooled)
+        ctx.ectx, ctx.dims, ctx.p_drop, ctx.lp = ectx, (B, T, O, Op, H), p_drop, y.dtype
+        ctx.save_for_backward(y32, mask, w, b, pooled)
+        return out if Op == O else out[:, :O].contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        B, T, O, Op, H = ctx.dims
+        y32, mask, w, b, pooled = ctx.saved_tensors
+        wp, _ = ctx.ectx.cache.padded_f32(w, Op, y32.shape[1], b)
+        g = _c(g)
+        if Op != O:
+            gp = ops.zeros_f32((B, Op), g.device)
+            gp[:, :O].copy_(g)
+            g = gp
+        dpool = ops.logsigmoid_bwd(pooled, g)
+        dz, _ = ops.mean_pool_bwd(dpool.view(1, B * Op), 1, T)                          # [T, B Op]
+        dz = dz.view(T * B, Op)
+        if mask is not None:
+            dz = ops.dropout_bwd(dz, mask, ctx.p_drop)
+        dy, dW, db = ops.head_bwd(y32, wp, dz, need_dx=ctx.needs_input_grad[0])
+        if dy is not None and ctx.lp != torch.float32:
+            dy = ops.cast2d(dy, ctx.lp)
+        return dy, dW[:O, :H].contiguous(), db[:O].contiguous(), None, None, None, None, None
 
 
 class LayerNormF32Fn(torch.autograd.Function):

@@ -1225,3 +1225,104 @@ def ctc_align(emission, tokens, n_frames, n_tokens, *, V=None, blank_id=0, want_
         _enqueue.append((a, ws, emission, tokens, n_frames, n_tokens, out))
     check(lib().tav_ctc_align(C.byref(a), stream()), "ctc_align")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- LSTM recurrence, log-sigmoid (include/tavhip_rnn.h)
+LstmSaved = collections.namedtuple("LstmSaved", "y workspace B T H Hp dtype")
+
+
+def lstm_plan(B, T, H, dtype):
+    """tav_lstm_get_plan as a dict: block, rows_per_wg, Hp, tiles_per_wave, lds_bytes, ws_gates_off, ws_cell_off, ws_bytes."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"lstm: the recurrence runs in float32 or bfloat16 operands, got {dtype}")
+    p = L.LstmPlan()
+    check(lib().tav_lstm_get_plan(int(B), int(T), int(H), dt(dtype), C.byref(p)), "lstm_plan")
+    return {name: int(getattr(p, name)) for name, _ in L.LstmPlan._fields_}
+
+
+def _bt_strides(x, B, T, W, what, time_major):
+    """(stride_b, stride_t) in elements of a [B, T, W] (or, time-major, [T, B, W]) tensor with a dense last dimension."""
+    want = (T, B, W) if time_major else (B, T, W)
+    if x.dim() != 3 or tuple(x.shape) != want or x.stride(-1) != 1:
+        raise ValueError(f"{what}: a {want} tensor with a dense last dimension is needed, got {tuple(x.shape)} strides {x.stride()}")
+    return (x.stride(1), x.stride(0)) if time_major else (x.stride(0), x.stride(1))
+
+
+def _state(x, B, Hp, what):
+    if x is not None and (tuple(x.shape) != (B, Hp) or x.dtype != torch.float32 or not x.is_contiguous()):
+        raise ValueError(f"{what}: a contiguous float32 [{B}, {Hp}] tensor is needed, got {tuple(x.shape)} {x.dtype}")
+    return x
+
+
+def lstm_fwd(xproj, w_hh, b_hh=None, h0=None, c0=None, *, H=None, time_major=False):
+    """tav_lstm_fwd, one launch: xproj [B, T, 4 Hp] (time_major: [T, B, 4 Hp]) and w_hh [4 Hp, Hp] in one operand dtype (float32 / bfloat16),
+    gate blocks padded to Hp = ceil(H / 64) 64 with zero pads; b_hh f32 [4 Hp], h0 / c0 f32 [B, Hp], all optional.  -> LstmSaved: y
+    [T + 1, B, Hp] (slot 0 = h0, slot t + 1 = h_t) and the workspace (f32 words) the backward reads; lstm_cells() / lstm_gates() view it."""
+    if not xproj.is_cuda:
+        raise ValueError("lstm_fwd runs on the GPU only (libtavhip has no host form)")
+    Hp = w_hh.shape[1]
+    H = Hp if H is None else int(H)
+    B, T = (xproj.shape[1], xproj.shape[0]) if time_major else (xproj.shape[0], xproj.shape[1])
+    plan = lstm_plan(B, T, H, xproj.dtype)
+    if plan["Hp"] != Hp or tuple(w_hh.shape) != (4 * Hp, Hp) or w_hh.dtype != xproj.dtype or not w_hh.is_contiguous():
+        raise ValueError(f"lstm_fwd: w_hh must be a contiguous {xproj.dtype} [{4 * plan['Hp']}, {plan['Hp']}] tensor for H = {H}, got {tuple(w_hh.shape)} {w_hh.dtype}")
+    sb, st = _bt_strides(xproj, B, T, 4 * Hp, "lstm_fwd: xproj", time_major)
+    if b_hh is not None and (b_hh.dtype != torch.float32 or b_hh.numel() != 4 * Hp or not b_hh.is_contiguous()):
+        raise ValueError(f"lstm_fwd: b_hh must be a contiguous float32 [{4 * Hp}] tensor")
+    y = torch.empty(T + 1, B, Hp, dtype=xproj.dtype, device=xproj.device)
+    ws = torch.empty(plan["ws_bytes"] // 4, dtype=torch.float32, device=xproj.device)
+    a = L.LstmFwdArgs()
+    a.xproj, a.w_hh, a.b_hh, a.h0, a.c0 = ptr(xproj), ptr(w_hh), ptr(b_hh), ptr(_state(h0, B, Hp, "lstm_fwd: h0")), ptr(_state(c0, B, Hp, "lstm_fwd: c0"))
+    a.y, a.workspace, a.workspace_bytes = ptr(y), ptr(ws), ws.numel() * 4
+    a.B, a.T, a.H, a.xp_stride_b, a.xp_stride_t, a.dtype = B, T, H, sb, st, dt(xproj)
+    check(lib().tav_lstm_fwd(C.byref(a), stream()), "lstm_fwd")
+    return LstmSaved(y, ws, B, T, H, Hp, xproj.dtype)
+
+
+def lstm_gates(s):
+    """The saved gate activations of a forward, f32 [T, B, 4, Hp] (i, f, g, o): a view of the workspace."""
+    p = lstm_plan(s.B, s.T, s.H, s.dtype)
+    return s.workspace[p["ws_gates_off"] // 4:p["ws_gates_off"] // 4 + s.T * s.B * 4 * s.Hp].view(s.T, s.B, 4, s.Hp)
+
+
+def lstm_cells(s):
+    """The saved cell states of a forward, f32 [T + 1, B, Hp] (slot 0 = c0, slot T = c_T): a view of the workspace."""
+    p = lstm_plan(s.B, s.T, s.H, s.dtype)
+    return s.workspace[p["ws_cell_off"] // 4:p["ws_cell_off"] // 4 + (s.T + 1) * s.B * s.Hp].view(s.T + 1, s.B, s.Hp)
+
+
+def lstm_bwd(saved, dy, w_hh_t, dh_T=None, dc_T=None, *, time_major=False, dz_time_major=True, want_state_grads=True, want_trace=False):
+    """tav_lstm_bwd, one launch: dy [B, T, Hp] (time_major: [T, B, Hp]) in the forward's dtype, w_hh_t [Hp, 4 Hp] the transposed operand.
+    -> (dZ [T, B, 4 Hp] (or [B, T, 4 Hp]) in that dtype, dh0, dc0 f32 [B, Hp] or None, dc_trace f32 [T, B, Hp] or None)."""
+    B, T, H, Hp = saved.B, saved.T, saved.H, saved.Hp
+    if tuple(w_hh_t.shape) != (Hp, 4 * Hp) or w_hh_t.dtype != saved.dtype or not w_hh_t.is_contiguous() or dy.dtype != saved.dtype:
+        raise ValueError(f"lstm_bwd: w_hh_t must be a contiguous {saved.dtype} [{Hp}, {4 * Hp}] tensor and dy of that dtype, got {tuple(w_hh_t.shape)} {w_hh_t.dtype}, {dy.dtype}")
+    ysb, yst = _bt_strides(dy, B, T, Hp, "lstm_bwd: dy", time_major)
+    dev = dy.device
+    dz = torch.empty((T, B, 4 * Hp) if dz_time_major else (B, T, 4 * Hp), dtype=saved.dtype, device=dev)
+    zsb, zst = _bt_strides(dz, B, T, 4 * Hp, "lstm_bwd: dz", dz_time_major)
+    dh0 = torch.empty(B, Hp, dtype=torch.float32, device=dev) if want_state_grads else None
+    dc0 = torch.empty(B, Hp, dtype=torch.float32, device=dev) if want_state_grads else None
+    trace = torch.empty(T, B, Hp, dtype=torch.float32, device=dev) if want_trace else None
+    a = L.LstmBwdArgs()
+    a.dy, a.dh_T, a.dc_T, a.w_hh_t = ptr(dy), ptr(_state(dh_T, B, Hp, "lstm_bwd: dh_T")), ptr(_state(dc_T, B, Hp, "lstm_bwd: dc_T")), ptr(w_hh_t)
+    a.workspace, a.workspace_bytes, a.dz, a.dh0, a.dc0, a.dc_trace = ptr(saved.workspace), saved.workspace.numel() * 4, ptr(dz), ptr(dh0), ptr(dc0), ptr(trace)
+    a.B, a.T, a.H, a.dy_stride_b, a.dy_stride_t, a.dz_stride_b, a.dz_stride_t, a.dtype = B, T, H, ysb, yst, zsb, zst, dt(saved.dtype)
+    check(lib().tav_lstm_bwd(C.byref(a), stream()), "lstm_bwd")
+    return dz, dh0, dc0, trace
+
+
+def logsigmoid_fwd(x):
+    if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError(f"logsigmoid_fwd: a contiguous float32 tensor on the GPU is needed, got {x.dtype} on {x.device}")
+    y = torch.empty_like(x)
+    check(lib().tav_logsigmoid_fwd(ptr(x), ptr(y), x.numel(), stream()), "logsigmoid_fwd")
+    return y
+
+
+def logsigmoid_bwd(x, dy):
+    if x.dtype != torch.float32 or dy.dtype != torch.float32 or not x.is_contiguous() or not dy.is_contiguous() or dy.shape != x.shape or not x.is_cuda:
+        raise ValueError("logsigmoid_bwd: x and dy must be contiguous float32 tensors of one shape on the GPU")
+    dx = torch.empty_like(x)
+    check(lib().tav_logsigmoid_bwd(ptr(x), ptr(dy), ptr(dx), x.numel(), stream()), "logsigmoid_bwd")
+    return dx
