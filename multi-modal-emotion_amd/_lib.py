@@ -230,6 +230,55 @@ _RNN_SIGS = {
     "tav_logsigmoid_bwd": (C.c_int, [vp, vp, vp, i64, vp]),
 }
 
+# include/tavhip_conv.h: the dense 3-D convolution entry points (Conv3d forward / input gradient / weight gradient, flatten + Linear,
+# sigmoid).  A fourth table, bound like the two above and for the same reason outside declared_symbols().
+CONV_ABI_VERSION = 1
+
+
+class Conv3dPlan(C.Structure):
+    _fields_ = [("cin_p", i32), ("cout_p", i32), ("tw", i32), ("th", i32), ("block", i32), ("n_tiles", i32), ("n_passes", i32), ("k_steps", i32),
+                ("kp", i64), ("lds_bytes", i64), ("od", i64), ("oh", i64), ("ow", i64), ("patches", i64),
+                ("wg_block", i32), ("wg_ci_tiles", i32), ("wg_co_tiles", i32), ("wg_groups", i32), ("wg_nslabs", i32), ("reserved", i32),
+                ("wg_lds_bytes", i64), ("wg_slab_floats", i64)]
+
+
+class Conv3dFwdArgs(C.Structure):
+    _fields_ = [("x", vp), ("w", vp), ("bias", vp), ("y", vp), ("g", vp), ("B", i64), ("D", i64), ("H", i64), ("W", i64), ("Cin", i64), ("Cout", i64),
+                ("pad", i32), ("gelu", i32), ("dtype", i32), ("reserved", i32)]
+
+
+class Conv3dWgradArgs(C.Structure):
+    _fields_ = [("x", vp), ("dz", vp), ("workspace", vp), ("workspace_bytes", i64), ("dw", vp), ("db", vp),
+                ("B", i64), ("D", i64), ("H", i64), ("W", i64), ("Cin", i64), ("Cout", i64), ("nslabs", i32), ("dtype", i32)]
+
+
+class FlatLinearFwdArgs(C.Structure):
+    _fields_ = [("x", vp), ("w", vp), ("bias", vp), ("out", vp), ("workspace", vp), ("workspace_bytes", i64),
+                ("B", i64), ("S", i64), ("C", i64), ("O", i64), ("nparts", i32), ("dtype", i32)]
+
+
+class FlatLinearBwdArgs(C.Structure):
+    _fields_ = [("x", vp), ("w", vp), ("dy", vp), ("dx", vp), ("dw", vp), ("db", vp), ("B", i64), ("S", i64), ("C", i64), ("O", i64),
+                ("dtype", i32), ("reserved", i32)]
+
+
+_CONV_SIGS = {
+    "tav_conv_version": (C.c_int, []),
+    "tav_conv3d_get_plan": (C.c_int, [i64, i64, i64, i64, i64, i64, i32, i32, C.POINTER(Conv3dPlan)]),
+    "tav_conv3d_wgrad_ws_bytes": (C.c_int64, [i64, i64, i64, i64, i64, i64, i32, i32]),
+    "tav_conv3d_pack_input": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i32, vp]),
+    "tav_conv3d_pack_weight": (C.c_int, [vp, vp, i64, i64, i32, i32, vp]),
+    "tav_conv3d_fwd": (C.c_int, [C.POINTER(Conv3dFwdArgs), vp]),
+    "tav_conv3d_dz": (C.c_int, [vp, vp, vp, i64, i32, vp]),
+    "tav_conv3d_wgrad": (C.c_int, [C.POINTER(Conv3dWgradArgs), vp]),
+    "tav_flat_linear_parts": (C.c_int32, [i64]),
+    "tav_flat_linear_ws_bytes": (C.c_int64, [i64, i64, i64, i32]),
+    "tav_flat_linear_fwd": (C.c_int, [C.POINTER(FlatLinearFwdArgs), vp]),
+    "tav_flat_linear_bwd": (C.c_int, [C.POINTER(FlatLinearBwdArgs), vp]),
+    "tav_sigmoid_fwd": (C.c_int, [vp, vp, i64, vp]),
+    "tav_sigmoid_bwd": (C.c_int, [vp, vp, vp, i64, vp]),
+}
+
 _lib = None
 
 
@@ -242,7 +291,7 @@ def lib():
                 f"{LIB_PATH} is missing: the TAV hot path has no fallback. Build it with "
                 "`make -C multi-modal-emotion_amd/csrc` (hipcc --offload-arch=gfx950).")
         h = C.CDLL(LIB_PATH)
-        for table in (_SIGS, _ALIGN_SIGS, _RNN_SIGS):
+        for table in (_SIGS, _ALIGN_SIGS, _RNN_SIGS, _CONV_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(h, name)      # AttributeError here = header/library mismatch
                 fn.restype, fn.argtypes = res, args
@@ -252,6 +301,8 @@ def lib():
             raise RuntimeError(f"libtavhip alignment ABI {h.tav_align_version()} != binding {ALIGN_ABI_VERSION}; rebuild")
         if h.tav_rnn_version() != RNN_ABI_VERSION:
             raise RuntimeError(f"libtavhip recurrent ABI {h.tav_rnn_version()} != binding {RNN_ABI_VERSION}; rebuild")
+        if h.tav_conv_version() != CONV_ABI_VERSION:
+            raise RuntimeError(f"libtavhip convolution ABI {h.tav_conv_version()} != binding {CONV_ABI_VERSION}; rebuild")
         _lib = h
     return _lib
 

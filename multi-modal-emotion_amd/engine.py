@@ -184,6 +184,18 @@ class WeightCache:
             return wi_n, wi_t, wh_n, wh_t, bi, bh
         return self._get(("lstm", id(w_hh)), (w_ih, w_hh, b_ih, b_hh), build)
 
+    def conv3d(self, w, b):
+        """Operands of one nn.Conv3d(kernel_size=3) layer (include/tavhip_conv.h): (the forward's [cout_p, kp(Cin)], the input gradient's
+        flipped, transposed [cin_p, kp(Cout)], both in the operand dtype with zero pads; the bias f32 [cout_p], or None)."""
+        def build():
+            Cout = w.shape[0]
+            bp = None
+            if b is not None:
+                bp = ops.zeros_f32((ops.conv3d_cp(Cout),), w.device)
+                ops.cast_weight(b.detach().view(1, Cout), torch.float32, want_t=False, out_n=bp[:Cout].view(1, Cout))
+            return ops.conv3d_pack_weight(w.detach(), self.pol.lp), ops.conv3d_pack_weight(w.detach(), self.pol.lp, flip_transpose=True), bp
+        return self._get(("conv3d", id(w)), (w, b), build)
+
     def padded_f32(self, w, rows, cols, b=None):
         """An f32 copy of w [R, C] (and of b [R]) zero-padded to [rows, cols] ([rows]): the frozen embedding table at the padded width, the
         classifier head at four-row granularity."""
@@ -651,6 +663,59 @@ class LstmTailFn(torch.autograd.Function):
         if dy is not None and ctx.lp != torch.float32:
             dy = ops.cast2d(dy, ctx.lp)
         return dy, dW[:O, :H].contiguous(), db[:O].contiguous(), None, None, None, None, None
+
+
+def _no_fp8(pol, what):
+    if pol.fp8:
+        raise ValueError(f"{what} runs under the bf16 and fp32 policies; {pol.name!r} has no e4m3 form of it")
+
+
+class Conv3dGeluFn(torch.autograd.Function):
+    """nn.Conv3d(Cin, Cout, 3) -> GELU on channels-last activations: x [B, D, H, W, cin_p] in the operand dtype -> y [B, D-2, H-2, W-2, cout_p].
+    Forward: one tav_conv3d_fwd that stores y = gelu(z) and g = gelu'(z).  Backward: dZ = dY g rounded once (tav_conv3d_dz), the weight and
+    bias gradients from tav_conv3d_wgrad straight into the parameter's layout, and -- only where the input needs one, so never for the first
+    layer -- dX as the same forward kernel with a halo of 2 on the flipped, transposed operand copy."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, ectx):
+        _no_fp8(ectx.pol, "the 3-D convolution")
+        Cout, Cin = w.shape[:2]
+        w_op, _, bias = ectx.cache.conv3d(w, b)
+        y, g = ops.conv3d_fwd(x, w_op, bias, Cin, Cout, gelu=True, want_g=True)
+        ctx.ectx, ctx.dims = ectx, (Cin, Cout)
+        ctx.save_for_backward(x, g, w, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        Cin, Cout = ctx.dims
+        x, g, w, b = ctx.saved_tensors
+        dz = ops.conv3d_dz(_c(gy), g)
+        dw, db = ops.conv3d_wgrad(x, dz, Cin, Cout, want_bias=b is not None)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.conv3d_dgrad(dz, ctx.ectx.cache.conv3d(w, b)[1], Cin, Cout)
+        return dx, dw, db, None
+
+
+class FlatLinearSigmoidFn(torch.autograd.Function):
+    """x.view(B, -1) -> nn.Linear -> nn.Sigmoid on a channels-last activation x [B, D, H, W, cp]: w stays [O, C D H W] in torch's flatten
+    order (tav_flat_linear_* address it as c S + s and skip the pad channels).  -> f32 [B, O]."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, Cn, ectx):
+        _no_fp8(ectx.pol, "the flattened Linear")
+        y = ops.sigmoid_fwd(ops.flat_linear_fwd(x, w.detach(), None if b is None else b.detach(), Cn))
+        ctx.Cn = Cn
+        ctx.save_for_backward(x, w, b, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, b, y = ctx.saved_tensors
+        dlin = ops.sigmoid_bwd(y, _c(g))
+        dx, dw, db = ops.flat_linear_bwd(x, w.detach(), dlin, ctx.Cn, need_dx=ctx.needs_input_grad[0], need_db=b is not None)
+        return dx, dw, db, None, None
 
 
 class LayerNormF32Fn(torch.autograd.Function):

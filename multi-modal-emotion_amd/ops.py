@@ -1326,3 +1326,167 @@ def logsigmoid_bwd(x, dy):
     dx = torch.empty_like(x)
     check(lib().tav_logsigmoid_bwd(ptr(x), ptr(dy), ptr(dx), x.numel(), stream()), "logsigmoid_bwd")
     return dx
+
+
+# ---------------------------------------------------------------------------------------------- dense 3-D convolution, flatten + Linear, sigmoid (include/tavhip_conv.h)
+def _conv_dtype(dtype, what):
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{what}: the convolution runs in float32 or bfloat16 operands, got {dtype}")
+    return dt(dtype)
+
+
+def conv3d_plan(B, D, H, W, Cin, Cout, dtype, pad=0):
+    """tav_conv3d_get_plan as a dict (every field of tav_conv3d_plan): the padded widths, the patch tw x th, block, LDS bytes, grid (= patches),
+    and for pad = 0 the weight gradient's channel block, slab count and slab size."""
+    p = L.Conv3dPlan()
+    check(lib().tav_conv3d_get_plan(int(B), int(D), int(H), int(W), int(Cin), int(Cout), int(pad), _conv_dtype(dtype, "conv3d_plan"), C.byref(p)), "conv3d_plan")
+    return {name: int(getattr(p, name)) for name, _ in L.Conv3dPlan._fields_ if name != "reserved"}
+
+
+def conv3d_cp(Cn):
+    """The padded channel count of the channels-last activations: ceil(C / 16) 16."""
+    return (int(Cn) + 15) // 16 * 16
+
+
+def _cl(x, what, C=None):
+    """(B, D, H, W, Cp) of a contiguous channels-last activation on the GPU."""
+    if not x.is_cuda or x.dim() != 5 or not x.is_contiguous() or x.shape[4] % 16 or (C is not None and x.shape[4] != conv3d_cp(C)):
+        raise ValueError(f"{what}: a contiguous channels-last [B, D, H, W, Cp] GPU tensor with Cp = ceil(C / 16) 16 is needed, got {tuple(x.shape)} on {x.device}")
+    return tuple(x.shape)
+
+
+def conv3d_pack_input(x, dtype):
+    """NCDHW float32 [B, C, D, H, W] -> channels-last [B, D, H, W, Cp] in `dtype`, pad channels zero."""
+    if not x.is_cuda or x.dim() != 5 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"conv3d_pack_input: a contiguous float32 [B, C, D, H, W] GPU tensor is needed, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    B, Cn, D, H, W = x.shape
+    out = torch.empty(B, D, H, W, conv3d_cp(Cn), dtype=dtype, device=x.device)
+    check(lib().tav_conv3d_pack_input(ptr(x), ptr(out), B, Cn, D, H, W, _conv_dtype(dtype, "conv3d_pack_input"), stream()), "conv3d_pack_input")
+    return out
+
+
+def conv3d_pack_weight(w, dtype, flip_transpose=False):
+    """torch's Conv3d weight f32 [Cout, Cin, 3, 3, 3] -> the forward's operand [cout_p, kp(Cin)] or (flip_transpose) the input gradient's
+    [cin_p, kp(Cout)], in `dtype`, pads zero."""
+    if not w.is_cuda or w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3) or w.dtype != torch.float32 or not w.is_contiguous():
+        raise ValueError(f"conv3d_pack_weight: a contiguous float32 [Cout, Cin, 3, 3, 3] GPU tensor is needed, got {tuple(w.shape)} {w.dtype}")
+    Cout, Cin = w.shape[:2]
+    rows, inner = (Cin, Cout) if flip_transpose else (Cout, Cin)
+    kstep = 32 if dtype == torch.bfloat16 else 16
+    kp = (27 * conv3d_cp(inner) + kstep - 1) // kstep * kstep
+    out = torch.empty(conv3d_cp(rows), kp, dtype=dtype, device=w.device)
+    check(lib().tav_conv3d_pack_weight(ptr(w), ptr(out), Cout, Cin, int(bool(flip_transpose)), _conv_dtype(dtype, "conv3d_pack_weight"), stream()), "conv3d_pack_weight")
+    return out
+
+
+def _conv3d_launch(x, w_op, bias, Cin, Cout, pad, gelu, want_g, what):
+    B, D, H, W, cin_p = _cl(x, what, Cin)
+    plan = conv3d_plan(B, D, H, W, Cin, Cout, x.dtype, pad)
+    if tuple(w_op.shape) != (plan["cout_p"], plan["kp"]) or w_op.dtype != x.dtype or not w_op.is_contiguous():
+        raise ValueError(f"{what}: the weight operand must be a contiguous {x.dtype} [{plan['cout_p']}, {plan['kp']}] tensor, got {tuple(w_op.shape)} {w_op.dtype}")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != plan["cout_p"] or not bias.is_contiguous()):
+        raise ValueError(f"{what}: bias must be a contiguous float32 [{plan['cout_p']}] tensor (pads zero)")
+    y = torch.empty(B, plan["od"], plan["oh"], plan["ow"], plan["cout_p"], dtype=x.dtype, device=x.device)
+    g = torch.empty_like(y) if (gelu and want_g) else None
+    a = L.Conv3dFwdArgs()
+    a.x, a.w, a.bias, a.y, a.g = ptr(x), ptr(w_op), ptr(bias), ptr(y), ptr(g)
+    a.B, a.D, a.H, a.W, a.Cin, a.Cout, a.pad, a.gelu, a.dtype = B, D, H, W, Cin, Cout, pad, int(bool(gelu)), dt(x)
+    check(lib().tav_conv3d_fwd(C.byref(a), stream()), what)
+    return y, g
+
+
+def conv3d_fwd(x, w_op, bias, Cin, Cout, *, gelu=True, want_g=True):
+    """tav_conv3d_fwd with pad 0: x channels-last [B, D, H, W, cin_p], w_op from conv3d_pack_weight, bias f32 [cout_p] or None ->
+    (y [B, D-2, H-2, W-2, cout_p] = gelu(z) (or z), g = gelu'(z) or None), in x's dtype."""
+    return _conv3d_launch(x, w_op, bias, Cin, Cout, 0, gelu, want_g, "conv3d_fwd")
+
+
+def conv3d_dgrad(dz, w_flip, Cin, Cout):
+    """The input gradient of a Cin -> Cout layer: tav_conv3d_fwd with pad 2 on dz [B, D', H', W', cout_p] and the flip_transpose operand
+    [cin_p, kp(Cout)] -> dx [B, D'+2, H'+2, W'+2, cin_p]."""
+    return _conv3d_launch(dz, w_flip, None, Cout, Cin, 2, False, False, "conv3d_dgrad")[0]
+
+
+def conv3d_dz(dy, g=None):
+    """dz = dy * g (a copy without g), rounded once to the operand dtype: what both conv3d_dgrad and conv3d_wgrad read."""
+    if not dy.is_cuda or not dy.is_contiguous() or dy.numel() % 4 or (g is not None and (g.shape != dy.shape or g.dtype != dy.dtype or not g.is_contiguous())):
+        raise ValueError("conv3d_dz: dy and g must be contiguous GPU tensors of one shape and dtype")
+    dz = torch.empty_like(dy)
+    check(lib().tav_conv3d_dz(ptr(dy), ptr(g), ptr(dz), dy.numel(), _conv_dtype(dy.dtype, "conv3d_dz"), stream()), "conv3d_dz")
+    return dz
+
+
+def conv3d_wgrad(x, dz, Cin, Cout, *, nslabs=0, want_bias=True):
+    """tav_conv3d_wgrad: x [B, D, H, W, cin_p], dz [B, D-2, H-2, W-2, cout_p] -> (dw f32 [Cout, Cin, 3, 3, 3], db f32 [Cout] or None).
+    nslabs = 0: the plan's slab count."""
+    B, D, H, W, _ = _cl(x, "conv3d_wgrad: x", Cin)
+    if _cl(dz, "conv3d_wgrad: dz", Cout) != (B, D - 2, H - 2, W - 2, conv3d_cp(Cout)) or dz.dtype != x.dtype:
+        raise ValueError(f"conv3d_wgrad: dz must be [{B}, {D - 2}, {H - 2}, {W - 2}, {conv3d_cp(Cout)}] in {x.dtype}, got {tuple(dz.shape)} {dz.dtype}")
+    code = _conv_dtype(x.dtype, "conv3d_wgrad")
+    nbytes = lib().tav_conv3d_wgrad_ws_bytes(B, D, H, W, Cin, Cout, code, int(nslabs))
+    if nbytes < 0:
+        check(int(nbytes), "conv3d_wgrad_ws_bytes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    dw = torch.empty(Cout, Cin, 3, 3, 3, dtype=torch.float32, device=x.device)
+    db = torch.empty(Cout, dtype=torch.float32, device=x.device) if want_bias else None
+    a = L.Conv3dWgradArgs()
+    a.x, a.dz, a.workspace, a.workspace_bytes, a.dw, a.db = ptr(x), ptr(dz), ptr(ws), nbytes, ptr(dw), ptr(db)
+    a.B, a.D, a.H, a.W, a.Cin, a.Cout, a.nslabs, a.dtype = B, D, H, W, Cin, Cout, int(nslabs), code
+    check(lib().tav_conv3d_wgrad(C.byref(a), stream()), "conv3d_wgrad")
+    return dw, db
+
+
+def _flat_args(x, w, Cn, what):
+    B, D, H, W, cp = _cl(x, what, Cn)
+    S = D * H * W
+    if not w.is_cuda or w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != Cn * S or not w.is_contiguous():
+        raise ValueError(f"{what}: the weight must be a contiguous float32 [O, {Cn * S}] GPU tensor (torch's flatten order c S + s), got {tuple(w.shape)} {w.dtype}")
+    return B, S, w.shape[0]
+
+
+def flat_linear_fwd(x, w, bias, Cn, *, nparts=0):
+    """out[b, o] = bias[o] + sum_f x[b, f] w[o, f] with x channels-last [B, D, H, W, cp] and w f32 [O, C D H W] in torch's flatten order -> f32 [B, O]."""
+    B, S, O = _flat_args(x, w, Cn, "flat_linear_fwd")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != O or not bias.is_contiguous()):
+        raise ValueError(f"flat_linear_fwd: bias must be a contiguous float32 [{O}] tensor")
+    nbytes = lib().tav_flat_linear_ws_bytes(B, S, O, int(nparts))
+    if nbytes < 0:
+        check(int(nbytes), "flat_linear_ws_bytes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    out = torch.empty(B, O, dtype=torch.float32, device=x.device)
+    a = L.FlatLinearFwdArgs()
+    a.x, a.w, a.bias, a.out, a.workspace, a.workspace_bytes = ptr(x), ptr(w), ptr(bias), ptr(out), ptr(ws), nbytes
+    a.B, a.S, a.C, a.O, a.nparts, a.dtype = B, S, Cn, O, int(nparts), _conv_dtype(x.dtype, "flat_linear_fwd")
+    check(lib().tav_flat_linear_fwd(C.byref(a), stream()), "flat_linear_fwd")
+    return out
+
+
+def flat_linear_bwd(x, w, dy, Cn, *, need_dx=True, need_db=True):
+    """-> (dx like x or None, dw f32 like w, db f32 [O] or None) from dy f32 [B, O], in one pass over x and w."""
+    B, S, O = _flat_args(x, w, Cn, "flat_linear_bwd")
+    if dy.dtype != torch.float32 or tuple(dy.shape) != (B, O) or not dy.is_contiguous():
+        raise ValueError(f"flat_linear_bwd: dy must be a contiguous float32 [{B}, {O}] tensor, got {tuple(dy.shape)} {dy.dtype}")
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(w)
+    db = torch.empty(O, dtype=torch.float32, device=x.device) if need_db else None
+    a = L.FlatLinearBwdArgs()
+    a.x, a.w, a.dy, a.dx, a.dw, a.db = ptr(x), ptr(w), ptr(dy), ptr(dx), ptr(dw), ptr(db)
+    a.B, a.S, a.C, a.O, a.dtype = B, S, Cn, O, _conv_dtype(x.dtype, "flat_linear_bwd")
+    check(lib().tav_flat_linear_bwd(C.byref(a), stream()), "flat_linear_bwd")
+    return dx, dw, db
+
+
+def sigmoid_fwd(x):
+    if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError(f"sigmoid_fwd: a contiguous float32 tensor on the GPU is needed, got {x.dtype} on {x.device}")
+    y = torch.empty_like(x)
+    check(lib().tav_sigmoid_fwd(ptr(x), ptr(y), x.numel(), stream()), "sigmoid_fwd")
+    return y
+
+
+def sigmoid_bwd(y, dy):
+    if y.dtype != torch.float32 or dy.dtype != torch.float32 or not y.is_contiguous() or not dy.is_contiguous() or dy.shape != y.shape or not y.is_cuda:
+        raise ValueError("sigmoid_bwd: y and dy must be contiguous float32 tensors of one shape on the GPU")
+    dx = torch.empty_like(y)
+    check(lib().tav_sigmoid_bwd(ptr(y), ptr(dy), ptr(dx), y.numel(), stream()), "sigmoid_bwd")
+    return dx
