@@ -131,14 +131,21 @@ int tav_gemm_tn_grouped_ws(const tav_gemm_tn_problem* problems, int32_t nproblem
 int tav_fp8_amax_partials(int64_t rows, int64_t cols);
 int tav_fp8_amax(const void* x, int32_t dtype, int64_t rows, int64_t cols, int64_t ld, float* partials, float* scales, void* stream);
 /* q[r][c] = e4m3(x[r][c] * scales[0]) (row stride ld_q bytes) and/or the transposed copy qt[c][r] (row stride ld_qt >= rows_pad), whose
- * token axis is padded with zeros up to rows_pad -- the K axis of the weight-gradient GEMM.  x is f32 or bf16, cols % 4 == 0. */
+ * token axis is padded with zeros up to rows_pad -- the K axis of the weight-gradient GEMM.  x is f32 or bf16, cols % 4 == 0.
+ * Non-finite values: a NaN or +-Inf x[r][c] becomes the e4m3 NaN byte (0x7f / 0xff) in q[r][c] and qt[c][r], so the GEMM that reads it gives a
+ * non-finite row or column; every other byte is what it would be without it.  A FINITE x saturates to +-448 however large x * scales[0] is
+ * (even when the product overflows f32): the class of the input decides, not the scaled value.  tav_fp8_amax takes the maximum over the
+ * finite elements (a NaN is not counted), falls back to the scales {1, 1, 0} when the tensor holds an Inf or is all zero, and never
+ * writes a non-finite word. */
 int tav_fp8_quantize(const void* x, int32_t dtype, int64_t rows, int64_t cols, int64_t ld, const float* scales, void* q, int64_t ld_q, void* qt,
                      int64_t ld_qt, int64_t rows_pad, void* stream);
 /* v5, DELAYED scaling: `state` = 4 device floats {448/amax, amax/448, amax, running amax}.  tav_fp8_quantize_delayed quantises with state[0]
  * -- the scale the previous step (or a calibration pass: tav_fp8_amax writes the first three) left there -- and gathers the tensor's own
  * absolute maximum into state[3] on the way: one pass and one launch per tensor instead of three.  tav_fp8_roll_states, once per step after
  * the last quantisation, turns every state[3] > 0 of the `n` consecutive states into the next step's scale and clears it.  state + 1 is the
- * dequantisation factor tav_gemm_nt takes (a_dequant / b_dequant); it does not change within a step. */
+ * dequantisation factor tav_gemm_nt takes (a_dequant / b_dequant); it does not change within a step.
+ * Non-finite values: as tav_fp8_quantize -- NaN / +-Inf inputs become NaN bytes, finite inputs saturate -- and state[3] gathers the maximum
+ * over the FINITE elements only, so a poisoned tensor never leaves a non-finite word in a state. */
 int tav_fp8_quantize_delayed(const void* x, int32_t dtype, int64_t rows, int64_t cols, int64_t ld, float* state, void* q, int64_t ld_q, void* qt,
                              int64_t ld_qt, int64_t rows_pad, void* stream);
 int tav_fp8_roll_states(float* states, int64_t n, void* stream);
@@ -433,7 +440,8 @@ typedef struct tav_loop_acc {
 int tav_step_stats(const float* logits, const int64_t* preds, const int64_t* target, int64_t* cm, const float* loss, const int32_t* status,
                    tav_loop_acc* acc, int64_t B, int64_t C, void* stream);
 
-/* dropout with a counter-based RNG (models/tav.py:497-498): y = x * keep / (1-p); mask bytes saved for backward */
+/* dropout with a counter-based RNG (models/tav.py:497-498): y = keep ? x / (1-p) : 0; mask bytes saved for backward (dx = mask ? dy / (1-p) : 0).
+ * Both are selects, not products: a dropped NaN or Inf is exactly 0, a kept one stays non-finite. */
 int tav_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t n, float p, uint64_t seed, uint64_t offset, void* stream);
 /* v7: tav_dropout_fwd with the seed read from DEVICE memory (*seed_state, one uint64 word) when the kernel runs -- bit-identical to
  * tav_dropout_fwd(seed = *seed_state).  A hipGraph that captured this launch draws whatever seed the host wrote into the word before the

@@ -15,6 +15,7 @@ import attn_ref as AR
 import front_ref as FR
 import gemm_ref as GR
 import guarded
+import nonfinite_ref as NF
 import norm_ref as NR
 import step_end_ref as SR
 import tav_amd.ops as ops
@@ -3046,6 +3047,665 @@ def front_fp64_checks():
     return out
 
 
+# ------------------------------------------------------------------------------------------------ non-finite values ("Non-finite values")
+# Every case launches its kernel clean once and once per placement with ONE operand element replaced by a poison pattern (tests/nonfinite_ref.py),
+# and NF.verdict() holds the two launches against the three sets the fp64 reference of the same two problems gives: non-finite exactly where the
+# reference is, bit-equal to the clean launch where the reference did not move, inside the family's existing bound where it moved.
+@contextlib.contextmanager
+def _poisoned(t, index, pat):
+    """Inside: element `index` of the device tensor holds pattern `pat`, written through an integer view; afterwards its own bits are back (the
+    guard's snapshot of an operand must still match)."""
+    dn = "f32" if t.dtype == torch.float32 else "bf16"
+    v = t.view(torch.int32 if dn == "f32" else torch.int16)
+    old = v[index].clone()
+    v[index] = NF.signed_bits(pat, dn)
+    try:
+        yield
+    finally:
+        v[index] = old
+
+
+def _np(t):
+    return t.detach().double().cpu().numpy()
+
+
+def _fp8_bytes(t):
+    return NF.e4m3_decode(t.view(torch.uint8).cpu().numpy())
+
+
+def _quantize_form(x, state, want_t, delayed):
+    rows, cols = x.shape
+    rows_pad = (rows + ops.FP8_KPAD - 1) // ops.FP8_KPAD * ops.FP8_KPAD
+    q = _blank((rows, cols), torch.uint8)
+    qt = _blank((cols, rows_pad), torch.uint8) if want_t else None
+    fn = ops.lib().tav_fp8_quantize_delayed if delayed else ops.lib().tav_fp8_quantize
+    ops.check(fn(ops.ptr(x), ops.dt(x), rows, cols, x.stride(0), ops.ptr(state), ops.ptr(q), cols, ops.ptr(qt), rows_pad, rows_pad, ops.stream()), "fp8_quantize")
+    return q, qt
+
+
+def check_nonfinite_fp8_quantize(dtype, delayed):
+    """tav_fp8_quantize / tav_fp8_quantize_delayed, streaming kernel (q only, cols % 8 == 0) and tiled kernel (q + qt; q only with cols % 8 != 0),
+    at a scale that saturates half the range: a NaN or +-Inf input element becomes an e4m3 NaN byte in q and in the matching byte of qt, every
+    other byte is the clean launch's, the padding of qt stays zero; state[0..2] are untouched, state[3] is the maximum over the FINITE elements
+    bit for bit (the plain entry leaves state[3] alone)."""
+    dn = _GDT[dtype]
+    rs, launch = [], 0
+    for rows, cols0 in NF.FP8_SHAPES:
+        for form, cols, want_t in (("stream", cols0, False), ("tiled q+qt", cols0, True), ("tiled cols%8", cols0 - 4, False)):
+            x64 = NF.fp8_inputs(rows, cols, dn)
+            x = _up(x64, dtype)
+            a0 = float(NF.finite_amax(x64)) * 0.5
+            state = _fp8_state(a0)
+            scale = float(state[0].item())
+            qc, qtc = _quantize_form(x, state, want_t, delayed)
+            for site in NF.fp8_sites(rows, cols):
+                pat = launch % NF.NPAT
+                launch += 1
+                xp, _, rp, sets, _ = NF.fp8_quantize_case(rows, cols, dn, site, pat, scale)
+                state = _fp8_state(a0)
+                s0 = state.clone()
+                with _poisoned(x, site, pat):
+                    q, qt = _quantize_form(x, state, want_t, delayed)
+                tag = f"nonfinite.fp8.{'delayed' if delayed else 'plain'}[{dn},{rows}x{cols},{form},{NF.NAMES[pat]}@{site}]"
+                rs += NF.verdict(tag + ".q", _fp8_bytes(qc), _fp8_bytes(q), rp, None, sets)
+                if want_t:
+                    tsets = {k: v.T for k, v in sets.items()}
+                    rs += NF.verdict(tag + ".qt", _fp8_bytes(qtc[:, :rows]), _fp8_bytes(qt[:, :rows]), rp.T, None, tsets)
+                    pad = int(qt[:, rows:].ne(0).sum().item())
+                    rs.append((tag + ".qt_pad bytes zero", float(pad), 0.0, pad == 0))
+                rs.append(_exact(tag + ".state[0:3] unchanged", _bits(state[:3]), _bits(s0[:3])))
+                want3 = torch.tensor([float(NF.finite_amax(xp))], device=DEV) if delayed else s0[3:4]
+                rs.append(_exact(tag + ".state[3] over the finite elements", _bits(state[3:4]), _bits(want3)))
+                rs.append(_all_ff(tag + ".gap", state[4:]))
+    return rs
+
+
+def check_nonfinite_fp8_saturation():
+    """A hand-made state with amax 1e-30: state[0] = 4.48e32 is finite and x state[0] overflows f32 for the finite x = +-1e10, which must still
+    saturate to +-448 (0x7e / 0xfe) next to a NaN and an Inf that become NaN bytes: the class of the INPUT decides.  Both kernels, both entries,
+    both dtypes."""
+    vals = [1e10, -1e10, 1e-32, 0.0, 1e30, -1e-30, 1.0, -1.0] * 4
+    rs = []
+    for dtype in (torch.float32, torch.bfloat16):
+        dn = _GDT[dtype]
+        x64 = GR.round_to(np.array(vals).reshape(4, 8), dn)[0]
+        for delayed in (False, True):
+            for want_t in (False, True):
+                x = _up(x64, dtype)
+                xp = x64
+                sites = [((1, 0), 0), ((2, 1), 3), ((3, 6), 4), ((3, 7), 1)]
+                state = _fp8_state(1e-30)
+                scale = float(state[0].item())
+                with np.errstate(over="ignore"):
+                    assert np.isfinite(scale) and np.isinf(np.float32(1e10) * np.float32(scale))
+                with contextlib.ExitStack() as es:
+                    for site, pat in sites:
+                        es.enter_context(_poisoned(x, site, pat))
+                        xp = NF.plant(xp, site, pat, dn)
+                    q, qt = _quantize_form(x, state, want_t, delayed)
+                ref = NF.e4m3_quantize(xp, scale)
+                got = _fp8_bytes(q)
+                tag = f"nonfinite.fp8.saturation[{dn},{'delayed' if delayed else 'plain'},{'q+qt' if want_t else 'q'}]"
+                same = np.isnan(ref) == np.isnan(got)
+                bad = int((~same).sum()) + int((np.nan_to_num(ref, nan=0.0) != np.nan_to_num(got, nan=0.0)).sum())
+                rs.append((tag + ".q bytes (finite inputs saturate, non-finite inputs are NaN bytes)", float(bad), 0.0, bad == 0))
+                sat, want_sat = (int((np.abs(np.nan_to_num(t_, nan=0.0)) == 448.0).sum()) for t_ in (got, ref))
+                assert want_sat >= 8                                  # (+-1e10 in every row: the reference itself saturates)
+                rs.append((tag + f".saturated elements {sat} (reference {want_sat})", float(abs(sat - want_sat)), 0.0, sat == want_sat))
+                if want_t:
+                    gt = _fp8_bytes(qt[:, :4]).T
+                    bad = int((np.isnan(gt) != np.isnan(got)).sum()) + int((np.nan_to_num(gt, nan=0.0) != np.nan_to_num(got, nan=0.0)).sum())
+                    rs.append((tag + ".qt == q^T", float(bad), 0.0, bad == 0))
+                if delayed:
+                    rs.append(_exact(tag + ".state[3]", _bits(state[3:4]), _bits(torch.tensor([float(NF.finite_amax(xp))], device=DEV))))
+    return rs
+
+
+def check_nonfinite_fp8_amax():
+    """tav_fp8_amax: a NaN is not counted (the scales are those of the finite elements, bit for bit), an Inf falls back to scale 1; no word of
+    the scales is ever non-finite."""
+    rs = []
+    for dtype in (torch.float32, torch.bfloat16):
+        dn = _GDT[dtype]
+        for rows, cols in NF.FP8_SHAPES:
+            x64 = NF.fp8_inputs(rows, cols, dn)
+            x = _up(x64, dtype)
+            top = tuple(int(i) for i in np.unravel_index(np.abs(x64).argmax(), x64.shape))
+            for k, site in enumerate(NF.fp8_sites(rows, cols) + [top]):            # (the largest element itself poisoned as well)
+                for pat in ((k % NF.NPAT, (k + 3) % NF.NPAT) if site != top else range(NF.NPAT)):
+                    scales = _blank((5,), torch.float32)
+                    part = ops.workspace("fp8_amax", ops.lib().tav_fp8_amax_partials(rows, cols), x.device)
+                    with _poisoned(x, site, pat):
+                        ops.check(ops.lib().tav_fp8_amax(ops.ptr(x), ops.dt(x), rows, cols, x.stride(0), ops.ptr(part), ops.ptr(scales), ops.stream()), "fp8_amax")
+                    want = torch.from_numpy(NF.amax_scales(NF.plant(x64, site, pat, dn))).to(DEV)
+                    tag = f"nonfinite.fp8.amax[{dn},{rows}x{cols},{NF.NAMES[pat]}@{site}]"
+                    rs.append(_exact(tag, _bits(scales[:3]), _bits(want)))
+                    rs.append(_all_ff(tag + ".tail", scales[3:]))
+    return rs
+
+
+@functools.lru_cache(maxsize=None)
+def _nf_fp8_nt(M, N, K):
+    x = GR.nt_inputs(M, N, K, "fp8", seed=9100 + M + N + K)
+    return x, GR.nt_ref(x, bias=True, out_dtype="f32")
+
+
+def _fp8_dev(a):
+    return _in(torch.from_numpy(np.ascontiguousarray(a)).float().to(DEV).to(ops.FP8))
+
+
+@contextlib.contextmanager
+def _nan_byte(t, index, pat):
+    v = t.view(torch.uint8)
+    old = v[index].clone()
+    v[index] = NF.E4M3_NAN[pat % 2]
+    try:
+        yield
+    finally:
+        v[index] = old
+
+
+def check_nonfinite_fp8_gemm(M, N, K, hint):
+    """The fp8 tav_gemm_nt with an e4m3 NaN byte (0x7f / 0xff) planted in a q operand: an A byte poisons its output row, a B byte its column,
+    everything else is the clean launch bit for bit."""
+    x, rc = _nf_fp8_nt(M, N, K)
+    a8, b8 = _fp8_dev(x["a"]), _fp8_dev(x["b"])
+    sa, sb = _in(torch.tensor([x["sa"]], dtype=torch.float32, device=DEV)), _in(torch.tensor([x["sb"]], dtype=torch.float32, device=DEV))
+    bias = _up(x["bias"], torch.float32)
+
+    def run():
+        return ops.gemm_nt(a8, b8, a_dequant=sa, b_dequant=sb, bias=bias, out_dtype=torch.float32, tile_m=hint)
+    clean = _np(run())
+    bad = int((~np.isfinite(clean)).sum())
+    rs = [(f"nonfinite.fp8.gemm_nt[M{M},N{N},K{K},tm{hint}].clean launch finite", float(bad), 0.0, bad == 0)]
+    for launch, (tensor, index, kind) in enumerate(NF.fp8_nt_sites(M, N, K, hint)):
+        rp, sets = NF.fp8_nt_case(x, rc, tensor, index)
+        with _nan_byte(a8 if tensor == "a" else b8, index, launch):
+            got = _np(run())
+        tag = f"nonfinite.fp8.gemm_nt[M{M},N{N},K{K},tm{hint},{tensor}{index} byte {NF.E4M3_NAN[launch % 2]:#x}]"
+        rs += NF.verdict(tag, clean, got, rp["out"], rp["out_bound"], sets)
+    return rs
+
+
+def check_nonfinite_fp8_wgrad(T=333, N1=132, N2=256):
+    """ops.wgrad_fp8 (the NT GEMM of the transposed copies in eight K-slices + tav_splitk_reduce): a NaN byte in dY^T poisons a dW row, one in
+    X^T a dW column, at the first token, the last one and one of a middle slice."""
+    ops.clear_workspaces()
+    p = NF.fp8_wgrad_problem(T, N1, N2)
+    rows_pad = p["at"].shape[1]
+    at, bt = _fp8_dev(p["at"]), _fp8_dev(p["bt"])
+    sa, sb = _in(torch.tensor([1.0, p["sa"], 1.0], dtype=torch.float32, device=DEV)), _in(torch.tensor([1.0, p["sb"], 1.0], dtype=torch.float32, device=DEV))
+    dy8, x8 = ops.Fp8(None, at, sa, T, N1), ops.Fp8(None, bt, sb, T, N2)
+    clean = _np(ops.wgrad_fp8(dy8, x8))
+    rc = NF.fp8_wgrad_ref(p)
+    bad = int((~np.isfinite(clean)).sum())
+    rs = [(f"nonfinite.fp8.wgrad[T{T},N1{N1},N2{N2},Kp{rows_pad}].clean launch finite", float(bad), 0.0, bad == 0)]
+    for launch, (tensor, index) in enumerate(NF.fp8_wgrad_sites(T, N1, N2)):
+        rp, sets = NF.fp8_wgrad_case(p, rc, tensor, index)
+        with _nan_byte(at if tensor == "at" else bt, index, launch):
+            got = _np(ops.wgrad_fp8(dy8, x8))
+        rs += NF.verdict(f"nonfinite.fp8.wgrad[T{T},{tensor}{index} byte {NF.E4M3_NAN[launch % 2]:#x}]", clean, got, rp["out"], rp["out_bound"], sets)
+    return rs
+
+
+@functools.lru_cache(maxsize=4)                                       # (a few 333 x 384 fp64 arrays each: only a site two hints share is worth keeping)
+def _nf_nt_case(dname, flavour, tensor, index, pat):
+    M, N, K = NF.NT_SHAPE
+    return NF.nt_case(_nt_problem(dname, M, N, K), _nt_reference(dname, M, N, K, flavour), flavour, tensor, index, pat)
+
+
+def check_nonfinite_gemm_nt(dtype, hint):
+    """tav_gemm_nt at M 333, N 384, K 256, the flavours NF.nt_flavours(): poison in A (an output row, and C_pre's), B (a column), the bias (a
+    column), the f32 residual, gelu_in and the accumulate-prev tensor (one element each), at the first row / column, the last one (the ragged
+    tail tile) and one on a tile boundary, with k = 0, K - 1 and a k of a middle K-tile; the pattern rotates with every launch."""
+    dname = _GDT[dtype]
+    M, N, K = NF.NT_SHAPE
+    x = _nt_problem(dname, M, N, K)
+    dev = {"a": _up(x["a"], dtype), "b": _up(x["b"], dtype)}
+    rs, launch = [], 0
+    for name in NF.nt_flavours(dname):
+        kw = GR.FLAVOURS[name]
+        odt = torch.float32 if (dtype == torch.float32 or kw.get("out_dtype") == "f32") else torch.bfloat16
+        prev = "cprev_" + ("f32" if odt == torch.float32 else "bf16")
+        for key, tensor, dt_ in (("bias", "bias", torch.float32), ("resid", "resid", torch.float32), ("gelu_in", kw.get("gelu_in"), dtype), ("accumulate", prev, odt)):
+            if kw.get(key) and tensor not in dev:
+                dev[tensor] = _up(x[tensor], dt_)
+
+        def run():
+            args = dict(tile_m=hint, out_dtype=odt, act=kw.get("act", 0), want_pre=kw.get("want_pre", False), alpha=kw.get("alpha", 1.0))
+            for key, tensor in (("bias", "bias"), ("resid", "resid"), ("gelu_in", kw.get("gelu_in"))):
+                if kw.get(key):
+                    args[key] = dev[tensor]
+            if kw.get("accumulate"):
+                out = _blank((M, N), odt)
+                out.copy_(dev[prev])
+                args.update(out=out, accumulate=True)
+            res = ops.gemm_nt(dev["a"], dev["b"], **args)
+            out, pre = res if isinstance(res, tuple) else (res, None)
+            return _np(out), (None if pre is None else _np(pre))
+        clean, clean_pre = run()
+        for tensor, index, kind in NF.nt_sites(dname, hint, name):
+            pat = launch % NF.NPAT
+            launch += 1
+            rp, sets, pre_sets = _nf_nt_case(dname, name, tensor, index, pat)
+            with _poisoned(dev[tensor], index, pat):
+                got, got_pre = run()
+            tag = f"nonfinite.gemm_nt[{dname},tm{hint},{name},{NF.NAMES[pat]}@{tensor}{index}]"
+            rs += NF.verdict(tag, clean, got, rp["out"], rp["out_bound"], sets)
+            if pre_sets is not None:
+                rs += NF.verdict(tag + ".pre", clean_pre, got_pre, rp["pre"], rp["pre_bound"], pre_sets)
+    return rs
+
+
+_NF_TN_VARIANTS = [("plain", dict(), 0), ("chunk64,scale", dict(scale=0.37), 64), ("conv perm", dict(perm=(88, 3)), 0)]
+
+
+def check_nonfinite_gemm_tn(dtype, rows, nbatch):
+    """tav_gemm_tn at check_gemm_tn_bounded's widths and a token count that is no multiple of the 64-row K-tile: an A element poisons one dW
+    row and that element of dbias (dbias is A's column sum: tavhip.h), a B element one dW column and nothing of dbias."""
+    dname = _GDT[dtype]
+    N1, N2 = NF.TN_WIDTHS
+    x = _tn_problem(dname, rows * nbatch, N1, N2)
+    dev = dict(a=_up(x["a"], dtype), b=_up(x["b"], dtype))
+    rs, launch = [], 0
+    for name, kw, chunk in _NF_TN_VARIANTS:
+        ops.clear_workspaces()
+        out, dbias, ns = _tn_call(dev["a"], dev["b"], N1, N2, rows, nbatch, chunk_rows=chunk, **kw)
+        clean, clean_b = _np(out), _np(dbias)
+        rc = GR.tn_ref(x, nsplit=ns, **kw)
+        for tensor, index in NF.tn_sites(rows * nbatch, N1, N2):
+            pat = launch % NF.NPAT
+            launch += 1
+            rp, sets, bsets = NF.tn_case(x, rc, tensor, index, pat, nsplit=ns, **kw)
+            with _poisoned(dev[tensor], index, pat):
+                out, dbias, _ = _tn_call(dev["a"], dev["b"], N1, N2, rows, nbatch, chunk_rows=chunk, **kw)
+            tag = f"nonfinite.gemm_tn[{dname},rows{rows},nb{nbatch},{name},{NF.NAMES[pat]}@{tensor}{index}]"
+            rs += NF.verdict(tag, clean, _np(out), rp["out"], rp["out_bound"], sets)
+            rs += NF.verdict(tag + ".dbias", clean_b, _np(dbias), rp["dbias"], rp["dbias_bound"], bsets)
+    return rs
+
+
+def check_nonfinite_gemm_tn_grouped(dtype, rows=130):
+    """tav_gemm_tn_grouped (what a too small workspace falls back to) and every tav_gemm_tn_grouped_ws form: the poison sits in problem 1 of
+    four; its dW / db follow tav_gemm_tn's rule, the other three problems are the clean launch bit for bit."""
+    dname = _GDT[dtype]
+    xs = [_tn_problem(dname, rows, n1, n2, seed=50 + k) for k, (n1, n2) in enumerate(_GROUP_SHAPES)]
+    pairs = [(_up(x["a"], dtype), _up(x["b"], dtype)) for x in xs]
+    N1, N2 = _GROUP_SHAPES[1]
+    rs, launch = [], 0
+    for name, flags, nsplit in _grouped_forms(dtype, rows):
+        clean = [(_np(dW), _np(db)) for dW, db in _grouped_run(pairs, flags)]
+        rc = GR.tn_ref(xs[1], nsplit=nsplit)
+        for tensor, index in NF.tn_sites(rows, N1, N2):
+            pat = launch % NF.NPAT
+            launch += 1
+            rp, sets, bsets = NF.tn_case(xs[1], rc, tensor, index, pat, nsplit=nsplit)
+            with _poisoned(pairs[1][0 if tensor == "a" else 1], index, pat):
+                got = [(_np(dW), _np(db)) for dW, db in _grouped_run(pairs, flags)]
+            tag = f"nonfinite.gemm_tn_grouped[{dname},rows{rows},{name},{NF.NAMES[pat]}@{tensor}1{index}]"
+            rs += NF.verdict(tag + ".dW1", clean[1][0], got[1][0], rp["out"], rp["out_bound"], sets)
+            rs += NF.verdict(tag + ".db1", clean[1][1], got[1][1], rp["dbias"], rp["dbias_bound"], bsets)
+            for k in (0, 2, 3):                                     # the other problems: all of it U
+                for j, what in enumerate(("dW", "db")):
+                    every = np.ones(clean[k][j].shape, dtype=bool)
+                    rs += NF.verdict(f"{tag}.{what}{k}", clean[k][j], got[k][j], clean[k][j], None, dict(N=~every, U=every, C=~every))[:2]
+    return rs
+
+
+def _nf_arena(sizes, flat, mis=False):
+    A = _Arena(sizes, mis)
+    A.put(flat)
+    return A
+
+
+@contextlib.contextmanager
+def _poisoned_flat(arena, site, pat):
+    """Element `site` of the concatenated tensors of an _Arena holds pattern `pat`."""
+    with _poisoned(arena.buf, int(arena.idx[site].item()), pat):
+        yield
+
+
+def check_nonfinite_sumsq():
+    """tav_sumsq_multi, tav_sumsq_chunked and tav_sum_partials: one NaN among the gradients gives a NaN sum, one +-Inf gives +Inf -- the class
+    and the kind the fp64 sum of squares has."""
+    L = ops.lib()
+    sizes = SR.SIZE_LISTS[NF.STEP_SIZES]
+    nt = len(sizes)
+    _, g0 = SR.make_inputs(sum(sizes), seed=77 + nt)
+    rs, launch = [], 0
+    for mis in (False, True):
+        G = _nf_arena(sizes, g0, mis)
+        t_g, t_s = G.table(), _i64(sizes)
+        pre, nchunks = SR.chunk_prefix(sizes, int(L.tav_optim_chunk_elems()))
+        t_c = _i32(pre)
+        n_part = int(L.tav_sumsq_partials(nt))
+        for site in NF.step_sites(sizes):
+            for k in range(2 if launch else NF.NPAT):                # all five patterns at the first site, two (rotating) at the others
+                pat = (launch + k) % NF.NPAT
+                want = NF.sumsq_ref(NF.plant(g0, site, pat))
+                outs, part_c, part_m = _blank((4,), torch.float32), _blank((nchunks,), torch.float32), _blank((n_part,), torch.float32)
+                with _poisoned_flat(G, site, pat):
+                    ops.check(L.tav_sumsq_chunked(ops.ptr(t_g), ops.ptr(t_s), ops.ptr(t_c), nt, nchunks, ops.ptr(part_c), ops.ptr(outs[0:1]), ops.stream()), "sumsq_chunked")
+                    ops.check(L.tav_sumsq_multi(ops.ptr(t_g), ops.ptr(t_s), nt, ops.ptr(part_m), ops.ptr(outs[1:2]), ops.stream()), "sumsq_multi")
+                    ops.check(L.tav_sum_partials(ops.ptr(part_c), nchunks, ops.ptr(outs[2:3]), ops.stream()), "sum_partials")
+                got = outs[:3].cpu().numpy().astype(np.float64)
+                for form, v in zip(("chunked", "multi", "sum_partials"), got):
+                    ok = bool(np.isnan(v)) if np.isnan(want) else bool(v == want)
+                    rs.append((f"nonfinite.sumsq[{'+4B' if mis else 'aligned'},{NF.NAMES[pat]}@{site}].{form} = {v} (fp64: {want})", 0.0 if ok else 1.0, 0.0, ok))
+                rs.append(_all_ff("nonfinite.sumsq.gap", G.gaps(), outs[3:4]))
+            launch += 2
+    return rs
+
+
+def _adamw_launch(form, A, G, sizes, scal, step, wd):
+    L = ops.lib()
+    nt = len(sizes)
+    tp, tm, tv = (A[k].table() for k in "pmv")
+    t_g, t_s = G.table(), _i64(sizes)
+    pre, nchunks = SR.chunk_prefix(sizes, int(L.tav_optim_chunk_elems()))
+    b1, b2 = SR.BETAS
+    coef, lr, bc = ops.ptr(scal[1:2]), ops.ptr(scal[4:5]), ops.ptr(scal[5:7])
+    if form == "multi":
+        ops.check(L.tav_adamw_multi(ops.ptr(tp), ops.ptr(t_g), ops.ptr(tm), ops.ptr(tv), ops.ptr(t_s), nt, coef, lr, b1, b2, SR.EPS, wd, ops.ptr(step), bc,
+                                    ops.stream()), "adamw_multi")
+    elif form == "chunked":
+        ops.check(L.tav_adamw_chunked(ops.ptr(tp), ops.ptr(t_g), ops.ptr(tm), ops.ptr(tv), ops.ptr(t_s), ops.ptr(_i32(pre)), nt, nchunks, coef, lr, b1, b2,
+                                      SR.EPS, wd, ops.ptr(step), bc, ops.stream()), "adamw_chunked")
+    else:
+        hyper = _in(torch.tensor([[float(scal[4].item()), wd]], dtype=torch.float32, device=DEV))
+        ops.check(L.tav_adamw_chunked_groups(ops.ptr(tp), ops.ptr(t_g), ops.ptr(tm), ops.ptr(tv), ops.ptr(t_s), ops.ptr(_i32(pre)), nt, nchunks, coef,
+                                             ops.ptr(_i32([0] * nt)), ops.ptr(hyper), 1, b1, b2, SR.EPS, ops.ptr(step), bc, ops.stream()), "adamw_chunked_groups")
+    return {k: A[k].get() for k in "pmv"}
+
+
+def check_nonfinite_adamw(form):
+    """tav_adamw_multi / _chunked / _chunked_groups, step 2 from non-zero moments with a clip coefficient of 0.37: a NaN or +-Inf gradient
+    element makes exactly that element of p, exp_avg and exp_avg_sq non-finite (an Inf second moment gives inf / inf in the update) and leaves
+    every other element the clean launch's bits; a NaN clip coefficient makes EVERY element of all three non-finite."""
+    sizes = SR.SIZE_LISTS[NF.STEP_SIZES]
+    p0, g0, m0, v0 = NF.adamw_state(SR)
+    G = _nf_arena(sizes, g0, True)
+
+    def run(site, pat):
+        A = dict(p=_nf_arena(sizes, p0), m=_nf_arena(sizes, m0), v=_nf_arena(sizes, v0))
+        scal, step = _blank((8,), torch.float32), _blank((1,), torch.int32)
+        step.fill_(1)
+        scal[4] = SR.LR
+        scal[1] = SR.CLIP_STEP2
+        with contextlib.ExitStack() as es:
+            if site is not None:
+                es.enter_context(_poisoned_flat(G, site, pat))
+            elif pat is not None:
+                es.enter_context(_poisoned(scal, 1, pat))
+            got = _adamw_launch(form, A, G, sizes, scal, step, SR.WD)
+        gaps = _all_ff(f"nonfinite.adamw[{form}].gap", *[A[k].gaps() for k in "pmv"], scal[0:1], scal[2:4], scal[7:8])
+        return got, gaps
+    clean, gap = run(None, None)
+    rs = [gap]
+    cases = [(site, (i + j) % NF.NPAT) for i, site in enumerate(NF.step_sites(sizes)) for j in ((0, 3, 4) if i == 0 else (1 + i, 3 + i))] + [(None, 0), (None, 1)]
+    for site, pat in cases:
+        rc, rp, sets = NF.adamw_case(p0, g0, m0, v0, 2, SR.f32(SR.LR), SR.WD, SR.CLIP_STEP2, site, pat, SR.ref_step)
+        got, gap = run(site, pat)
+        rs.append(gap)
+        for k, nm in zip("pmv", ("p", "exp_avg", "exp_avg_sq")):
+            tag = f"nonfinite.adamw[{form},{NF.NAMES[pat]}@{'clip coefficient' if site is None else site}].{nm}"
+            rs += NF.verdict(tag, clean[k], got[k], rp[k], rp[k + "_bound"], sets[k])
+    return rs
+
+
+def check_nonfinite_cross_entropy():
+    """tav_cross_entropy with a NaN, +Inf or -Inf logit at the target class and off it (B 3 and 257, C 7, class weights, loss and dlogits), the
+    loss and every dlogits element against the class the fp64 reference gives them; then tav_step_stats on that loss word: `nonfinite` goes up
+    by exactly one when the loss is NaN or Inf, and not at all when it is a number."""
+    rs, launch = [], 0
+    for B, C, weighted, gs in ((3, 7, True, 1.0), (257, 7, False, 0.125)):
+        p = FR.ce_inputs(B, C)
+        rc = FR.ce_ref(p, weighted, gs)
+        z, t = _dev(p["z"], _F32), _ints_dev(p["t"], torch.int64)
+        cw = _dev(p["cw"], _F32) if weighted else None
+
+        def run():
+            loss, dl = _blank((1,), _F32), _blank((B, C), _F32)
+            ops.check(ops.lib().tav_cross_entropy(ops.ptr(z), ops.ptr(t), ops.ptr(cw), ops.ptr(loss), ops.ptr(dl), B, C, gs, ops.stream()), "cross_entropy")
+            return loss, dl
+        loss_c, dl_c = run()
+        for row, col, where in NF.ce_sites(p):
+            for pat in (launch % 3, 3, 4):                            # a NaN pattern (rotating), +Inf and -Inf at every site
+                rp, lsets, dsets = NF.ce_case(p, rc, FR.ce_ref, weighted, gs, row, col, pat)
+                with _poisoned(z, (row, col), pat):
+                    loss, dl = run()
+                tag = f"nonfinite.ce[B{B},C{C},{NF.NAMES[pat]}@({row},{col}) {where}]"
+                rs += NF.verdict(tag + ".loss", _np(loss_c), _np(loss), rp["loss"], rp["loss_b"], lsets)
+                rs += NF.verdict(tag + ".dlogits", _np(dl_c), _np(dl), rp["dlogits"], rp["dlogits_b"], dsets)
+                acc = ops.loop_acc_new(DEV)
+                ops.step_stats(logits=z, target=t, cm=torch.zeros(C * C, dtype=torch.int64, device=DEV), loss=loss, acc=acc)
+                n_bad = ops.loop_acc_read(acc)["nonfinite"]
+                want = int(lsets["N"].any())
+                rs.append((tag + f".step_stats nonfinite {n_bad} (want {want})", float(abs(n_bad - want)), 0.0, n_bad == want))
+            launch += 1
+    return rs
+
+
+def check_nonfinite_layernorm(xdt, act):
+    """tav_ln_fwd and the isolated tav_ln_bwd at W 768 and 5 rows, f32 output alone and f32 + bf16, the parameter reduce immediate and deferred
+    (tav_ln_param_reduce_multi): poison in x, dy, gamma and dx_add against the sets NF.ln_expect() spells out."""
+    rows, W = NF.LN_SHAPE
+    p = NR.ln_inputs(rows, W, xdt, xdt)
+    dev = _ln_dev(p)
+    dyt, add = _dev(p["dy"], _TDT[xdt]), _dev(p["add"], torch.float32)
+    tensors = dict(x=dev[0], gamma=dev[1], dy=dyt, add=add)
+    rs, launch = [], 0
+
+    def run(fed, lp, defer):
+        f, _ = _ln_fwd_abi(p, dev, act=act, want32=True, lp=lp)
+        b, _ = _ln_bwd_abi(p, dev, dyt, _dev(fed[0], torch.float32), _dev(fed[1], torch.float32), act=act, want32=True, lp=lp, add=add, defer=defer)
+        if defer:
+            _ln_reduce_multi([(b["partials"], b["dgamma"], b["dbeta"], b["nb"], W, 0)])
+        return {n: _np(t) for n, t in list(f.items()) + list(b.items()) if n in NR.LN_FWD_OUT + NR.LN_BWD_OUT and t is not None}
+    for lp in (False, True):
+        for defer in (False, True):
+            clean = None
+            for tensor, index in NF.ln_sites(rows, W):
+                pat = launch % NF.NPAT
+                launch += 1
+                c = NF.ln_case(NR, p, tensor, index, pat, act, lp)
+                if clean is None:
+                    clean = run(c["fed_clean"], lp, defer)
+                with _poisoned(tensors[tensor], index, pat):
+                    got = run(c["fed"], lp, defer)
+                tag = f"nonfinite.ln[{xdt},act{act},lp{int(lp)},{'deferred' if defer else 'immediate'},{NF.NAMES[pat]}@{tensor}{index}]"
+                for side, names in (("fwd", NR.LN_FWD_OUT), ("bwd", NR.LN_BWD_OUT)):
+                    for n in names:
+                        if n in got:
+                            rs += NF.verdict(f"{tag}.{n}", clean[n], got[n], c[side][n], c[side][n + "_b"], c[side + "_sets"][n])
+    return rs
+
+
+def check_nonfinite_attention(dtype, S):
+    """tav_attn_fwd and the isolated tav_attn_bwd at B 2, nh 3, every mask mode, raw and pre-scaled q: one poisoned element of Q, K, V, the
+    mask or dO per launch (NF.attn_site rotates rows, entries, heads and patterns) against the sets NF.attn_expect() spells out -- the other
+    (batch, head) slices are the clean launch bit for bit.  The backward is fed the reference's own (poisoned) o, o_soft, lse and corr."""
+    dname = _GDT[dtype]
+    rs, cfg = [], 0
+    for mode in (0, 1, 2):
+        for pre in (False, True):
+            x = AR.make_inputs(2, S, 3, dname, seed=11, **AR.bound_config(S, mode, pre, None))
+            ops_in = _attn_operands(x, dtype)
+            dev = dict(zip(("q", "k", "v", "do", "mask"), ops_in))
+            names = [n for n in AR.FWD_OUT + AR.BWD_OUT if not (n == "corr" and mode != 2)]
+
+            def run(ref, tag):
+                f = _attn_fwd(x, ops_in, None)
+                got, gap = _attn_bwd(x, ops_in, None, *_attn_fed(x, AR.fed(ref, x), dtype), tag)
+                got.update(f)
+                return {n: _np(got[n]).reshape(ref[n].shape) for n in names}, gap
+            clean = {}
+            for i in range(len(NF.ATTN_SITES)):
+                site = NF.attn_site(S, mode, cfg, i)
+                if site is None:
+                    continue
+                tensor, index = site
+                pat = NF.attn_pattern(tensor, cfg + i, mode, pre)
+                xp, rc, rp, sets = NF.attn_case(AR, x, tensor, index, pat)
+                tag = f"nonfinite.attn[{dname},S{S},mode{mode},pre{int(pre)},{NF.NAMES[pat]}@{tensor}{index}]"
+                kind = "o_bound" in rp                                # (the clean launch is fed the clean reference of the same model)
+                if kind not in clean:
+                    clean[kind], gap = run(rc, tag + ".clean")
+                    rs.append(gap)
+                at = index if tensor == "mask" else (index[0] * S + index[1], index[2] * 64 + index[3])
+                with _poisoned(dev[tensor], at, pat):
+                    got, gap = run(rp, tag)
+                rs.append(gap)
+                for n in names:
+                    rs += NF.verdict(f"{tag}.{n}", clean[kind][n], got[n], rp[n], rp.get(n + "_bound"), sets[n])
+            cfg += 1
+    return rs
+
+
+def _nf_cast_rows(tag, clean, got, ref_c, ref_p):
+    return NF.verdict(tag, _np(clean), _np(got), ref_p, None, NF.classify(ref_c, ref_p))
+
+
+def check_nonfinite_casts():
+    """tav_cast_weight, tav_cast2d, tav_cast_weights_multi (with the scaled q rows and a scaled bias row) and tav_cast_conv_weight: a poisoned
+    source element is non-finite in the normal and in the transposed copy (and exactly once in the per-phase operand, a permutation of the
+    weights), everything else is the clean launch bit for bit."""
+    rs, launch = [], 0
+    R, Cc = 65, 127
+    w = _rnd(R, Cc, seed=1500)
+    w64 = _np(w)
+    sites = [(0, 0), (R - 1, Cc - 1), (32, 64)]
+    for dtype in (torch.bfloat16, torch.float32):
+        dn = _GDT[dtype]
+        n_c, t_c = ops.cast_weight(w, dtype)
+        ref_c = NF.cast_ref(w64, dn)
+        for site in sites:
+            pat = launch % NF.NPAT
+            launch += 1
+            ref_p = NF.cast_ref(NF.plant(w64, site, pat), dn)
+            with _poisoned(w, site, pat):
+                n, t = ops.cast_weight(w, dtype)
+            tag = f"nonfinite.cast[{dn},{NF.NAMES[pat]}@{site}]"
+            rs += _nf_cast_rows(tag + ".cast_weight.n", n_c, n, ref_c, ref_p) + _nf_cast_rows(tag + ".cast_weight.t", t_c, t, ref_c.T, ref_p.T)
+    for src in (torch.float32, torch.bfloat16):                        # tav_cast2d, every pair of dtypes
+        xs = _rnd(33, 64, dtype=src, seed=1501)
+        xs64 = _np(xs)
+        for dtype in (torch.bfloat16, torch.float32):
+            c2_c = ops.cast2d(xs, dtype)
+            for site in ((0, 0), (32, 63), (16, 32)):
+                pat = launch % NF.NPAT
+                launch += 1
+                with _poisoned(xs, site, pat):
+                    c2 = ops.cast2d(xs, dtype)
+                rs += _nf_cast_rows(f"nonfinite.cast2d[{_GDT[src]}->{_GDT[dtype]},{NF.NAMES[pat]}@{site}]", c2_c, c2, NF.cast_ref(xs64, _GDT[dtype]),
+                                    NF.cast_ref(NF.plant(xs64, site, pat, _GDT[src]), _GDT[dtype]))
+    # the multi-tensor launch: q rows scaled in dst and not in dst_t, a scaled f32 bias row
+    H, K, bf, qs = 64, 128, torch.bfloat16, ops.ATTN_Q_PRESCALE
+    wq, bq = _rnd(H, K, seed=1600), _rnd(1, H, seed=1610)
+    outs = dict(n=_blank((H, K), bf), t=_blank((K, H), bf), b=_blank((H,), torch.float32))
+    descs, tiles = ops.make_cast_descs([(wq, outs["n"], outs["t"], qs), (bq, outs["b"].view(1, H), None, qs)], DEV)
+    descs = _in(descs)
+
+    def multi():
+        for b_ in outs.values():
+            _refill(b_)
+        ops.cast_weights_multi(descs, 2, 3)
+        return {k: v.clone() for k, v in outs.items()}
+    clean = multi()
+    wq64, bq64 = _np(wq), _np(bq)
+    for src, s64, site in ((wq, wq64, (0, 0)), (wq, wq64, (H - 1, K - 1)), (wq, wq64, (32, 64)), (bq, bq64, (0, H - 1))):
+        pat = launch % NF.NPAT
+        launch += 1
+        with _poisoned(src, site, pat):
+            got = multi()
+        tag = f"nonfinite.cast_multi[{NF.NAMES[pat]}@{'bias' if src is bq else 'wq'}{site}]"
+        pw = NF.plant(wq64, site, pat) if src is wq else wq64
+        pb = NF.plant(bq64, site, pat) if src is bq else bq64
+        rs += _nf_cast_rows(tag + ".dst (scaled)", clean["n"], got["n"], NF.cast_ref(wq64, "bf16", qs), NF.cast_ref(pw, "bf16", qs))
+        rs += _nf_cast_rows(tag + ".dst_t", clean["t"], got["t"], NF.cast_ref(wq64, "bf16").T, NF.cast_ref(pw, "bf16").T)
+        rs += _nf_cast_rows(tag + ".bias (scaled)", clean["b"], got["b"], NF.cast_ref(bq64, "f32", qs)[0], NF.cast_ref(pb, "f32", qs)[0])
+    # conv weights [co][ci][k]: dst[c][kk ci + i] = W[c][i][kk], dst_t its transpose, the per-phase operand a permutation
+    co, ci, k = 16, 8, 3
+    wc = _rnd(co, ci, k, seed=1700)
+    wc64 = _np(wc)
+    for dtype in (torch.bfloat16, torch.float32):
+        dn = _GDT[dtype]
+        n_c, t_c, ph_c = ops.cast_conv_weight(wc, dtype, conv_stride=2)
+        for site in ((0, 0, 0), (co - 1, ci - 1, k - 1), (7, 3, 1)):
+            pat = launch % NF.NPAT
+            launch += 1
+            with _poisoned(wc, site, pat):
+                n, t, ph = ops.cast_conv_weight(wc, dtype, conv_stride=2)
+            lay = lambda a: NF.cast_ref(a, dn).transpose(0, 2, 1).reshape(co, k * ci)          # noqa: E731
+            ref_c, ref_p = lay(wc64), lay(NF.plant(wc64, site, pat))
+            tag = f"nonfinite.cast_conv[{dn},{NF.NAMES[pat]}@{site}]"
+            rs += _nf_cast_rows(tag + ".dst", n_c, n, ref_c, ref_p) + _nf_cast_rows(tag + ".dst_t", t_c, t, ref_c.T, ref_p.T)
+            bad = ~np.isfinite(_np(ph))
+            same = int(((_np(ph) != _np(ph_c)) & ~bad).sum())
+            rs.append((tag + f".phase operand: {int(bad.sum())} non-finite element(s), {same} others changed", float(abs(int(bad.sum()) - 1) + same), 0.0,
+                       int(bad.sum()) == 1 and same == 0))
+    return rs
+
+
+def check_nonfinite_dropout():
+    """tav_dropout_fwd / tav_dropout_bwd (y = keep ? x / (1 - p) : 0, a select): a kept poison stays non-finite, a dropped one is exactly 0, the
+    mask bytes are those of the clean launch, every other element is the clean launch bit for bit."""
+    n, p, seed = 5003, 0.3, 1234
+    x, dy = _rnd(n, seed=1800), _rnd(n, seed=1801)
+    y_c, mask_c = ops.dropout_fwd(x, p, seed, 0)
+    dx_c = ops.dropout_bwd(dy, mask_c, p)
+    keep = mask_c.cpu().numpy() != 0
+    x64, dy64 = _np(x), _np(dy)
+    kept, dropped = np.flatnonzero(keep), np.flatnonzero(~keep)
+    rs = [("nonfinite.dropout: kept and dropped elements both present", 0.0, 0.0, len(kept) > 2 and len(dropped) > 2)]
+    sites = [("kept", int(kept[0])), ("kept", int(kept[-1])), ("dropped", int(dropped[0])), ("dropped", int(dropped[-1])), ("kept", int(kept[len(kept) // 2]))]
+    for launch, (what, i) in enumerate(sites):
+        for pat in (launch % NF.NPAT, (launch + 3) % NF.NPAT):
+            with _poisoned(x, i, pat):
+                y, mask = ops.dropout_fwd(x, p, seed, 0)
+            with _poisoned(dy, i, pat):
+                dx = ops.dropout_bwd(dy, mask_c, p)
+            tag = f"nonfinite.dropout[{NF.NAMES[pat]}@{i} ({what})]"
+            rs.append(_exact(tag + ".mask bytes", mask, mask_c))
+            ref_c, ref_p = NF.dropout_ref(x64, keep, p), NF.dropout_ref(NF.plant(x64, i, pat), keep, p)
+            rs += NF.verdict(tag + ".fwd", _np(y_c), _np(y), ref_p, None, NF.classify(ref_c, ref_p))
+            ref_c, ref_p = NF.dropout_ref(dy64, keep, p), NF.dropout_ref(NF.plant(dy64, i, pat), keep, p)
+            rs += NF.verdict(tag + ".bwd", _np(dx_c), _np(dx), ref_p, None, NF.classify(ref_c, ref_p))
+            if what == "dropped":
+                z = float(y[i].abs().item()) + float(dx[i].abs().item())
+                rs.append((tag + ".dropped poison is exactly 0", z, 0.0, z == 0.0))
+    return rs
+
+
+def nonfinite_checks():
+    """The non-finite cases, in the order all_checks() appends them."""
+    out = []
+    for dtype in (torch.float32, torch.bfloat16):
+        for delayed in (False, True):
+            out.append(lambda d=dtype, l=delayed: check_nonfinite_fp8_quantize(d, l))
+    out += [check_nonfinite_fp8_saturation, check_nonfinite_fp8_amax, lambda: check_nonfinite_fp8_gemm(130, 132, 128, 4),
+            lambda: check_nonfinite_fp8_gemm(257, 260, 256, 16), check_nonfinite_fp8_wgrad]
+    out.append(lambda: check_nonfinite_gemm_nt(torch.float32, 0))
+    for hint in (0, 8, 16):
+        out.append(lambda h=hint: check_nonfinite_gemm_nt(torch.bfloat16, h))
+    for dtype in (torch.float32, torch.bfloat16):
+        out.append(lambda d=dtype: check_nonfinite_gemm_tn(d, 130, 1))
+        out.append(lambda d=dtype: check_nonfinite_gemm_tn(d, 249, 3))
+        out.append(lambda d=dtype: check_nonfinite_gemm_tn_grouped(d))
+    out.append(check_nonfinite_sumsq)
+    for form in ("multi", "chunked", "chunked_groups"):
+        out.append(lambda f=form: check_nonfinite_adamw(f))
+    out.append(check_nonfinite_cross_entropy)
+    for xdt in ("f32", "bf16"):
+        for act in (0, 1):
+            out.append(lambda x=xdt, a=act: check_nonfinite_layernorm(x, a))
+    for dtype in (torch.float32, torch.bfloat16):
+        for S in NF.ATTN_S:
+            out.append(lambda d=dtype, s=S: check_nonfinite_attention(d, s))
+    out += [check_nonfinite_casts, check_nonfinite_dropout]
+    return out
+
+
 def all_checks():
     out = []
     for dtype in (torch.float32, torch.bfloat16):
@@ -3170,4 +3830,6 @@ def all_checks():
     out += norm_fp64_checks()
     # the audio front-end, colsum, the GELU pair, pools, head, tanh, cross entropy and the index kernels against fp64
     out += front_fp64_checks()
+    # non-finite values: a poisoned operand element stays loud where the fp64 reference says so and reaches nothing else
+    out += nonfinite_checks()
     return out

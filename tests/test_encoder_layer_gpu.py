@@ -40,8 +40,9 @@ def _case(shape):
     return _layer(nh * 64, F, 7), x, gy
 
 
-def _step(policy, shape, pre_ln, params, x, gy):
-    """One forward + backward under a FRESH context (new operand cache, new delayed-scaling states) -> [x2, dx, 16 parameter gradients]."""
+def _step(policy, shape, pre_ln, params, x, gy, finite=True):
+    """One forward + backward under a FRESH context (new operand cache, new delayed-scaling states) -> [x2, dx, 16 parameter gradients].
+    finite=False: the caller feeds a poisoned gy and judges the outputs itself."""
     nh, _, B, S = SHAPES[shape]
     ectx = runtime.set_precision(policy)
     for p in params:
@@ -52,7 +53,7 @@ def _step(policy, shape, pre_ln, params, x, gy):
     (y * gy).sum().backward()
     torch.cuda.synchronize()
     out = [y.detach().clone(), x.grad.clone()] + [p.grad.clone() for p in params]
-    assert len(out) == 18 and all(torch.isfinite(t).all() for t in out)
+    assert len(out) == 18 and (not finite or all(torch.isfinite(t).all() for t in out))
     return out
 
 
@@ -82,3 +83,39 @@ def test_fp8_layer_replays_bitwise(gpu, shape, pre_ln, policy):
     assert all(torch.equal(a, b) for a, b in zip(first, again))
     sts = runtime.ctx().cache._fp8_states
     assert sts is not None and sts.calibrated                # the layer did run its e4m3 sites
+
+
+@pytest.mark.parametrize("policy", ["bf16", "fp8", "fp8-all", "fp8-wgrad8"])
+@pytest.mark.parametrize("pre_ln", [True, False])
+def test_poisoned_output_gradient_stays_loud(gpu, pre_ln, policy):
+    """One NaN or Inf element of gy in batch entry 0 ("Non-finite values"): the forward is untouched; attention spreads the row to
+    every token of ITS entry and to no token of the other one; every parameter gradient sums over the poisoned rows, so the gradient norm and the
+    clip coefficient are non-finite -- the step cannot go on quietly; and no fp8 scaling state takes a non-finite word, before or after
+    tav_fp8_roll_states."""
+    import nonfinite_ref as NF
+    from tav_amd import ops, optim
+    _, _, B, S = SHAPES["narrow"]
+    params, x, gy = _case("narrow")
+    clean = _step(policy, "narrow", pre_ln, params, x, gy)
+    pat = ["bf16", "fp8", "fp8-all", "fp8-wgrad8"].index(policy) + (0 if pre_ln else 1)          # all five patterns over the eight cases
+    bad = gy.clone()
+    bad.view(torch.int32)[S - 1, 77] = NF.signed_bits(pat, "f32")                                # the last token of entry 0
+    got = _step(policy, "narrow", pre_ln, params, x, bad, finite=False)
+    y, dx, grads = got[0], got[1], got[2:]
+    assert torch.equal(y, clean[0])
+    rows = torch.isfinite(dx).all(1)
+    print(f"[{policy}, pre_ln={pre_ln}, {NF.NAMES[pat % NF.NPAT]}] finite dx rows: entry 0 {int(rows[:S].sum())}/{S}, entry 1 {int(rows[S:].sum())}/{S}; "
+          f"parameter gradients without a non-finite element: {[i for i, g in enumerate(grads) if torch.isfinite(g).all()]}")
+    assert not rows[:S].any(), "a token of the poisoned entry has a finite input gradient"
+    assert rows[S:].all(), "the poison reached the other batch entry"
+    assert len(grads) == 16 and not any(torch.isfinite(g).all() for g in grads)
+    norm = optim.grad_norm(params)
+    scal = torch.stack([norm[0] * norm[0], norm[0], norm[0]]).contiguous()
+    ops.check(ops.lib().tav_clip_coef(ops.ptr(scal[0:1]), 1.0, ops.ptr(scal[1:2]), ops.ptr(scal[2:3]), ops.stream()), "clip_coef")
+    assert not torch.isfinite(norm).any() and not torch.isfinite(scal[1:]).any()
+    sts = runtime.ctx().cache._fp8_states
+    assert (sts is not None and bool(sts.calibrated)) == (policy != "bf16")
+    if sts is not None:
+        assert torch.isfinite(sts.dev).all()
+        ops.fp8_roll_all()
+        assert torch.isfinite(sts.dev).all()

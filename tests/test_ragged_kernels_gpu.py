@@ -69,6 +69,22 @@ def _same(a, b):
     return torch.equal(_bits(a), _bits(b))
 
 
+def _poison_fill(t, region):
+    """t[region] := the five poison patterns of tests/nonfinite_ref.py in turn (quiet NaN, all ones, signalling NaN, +Inf, -Inf), written
+    through an integer view: what a reused buffer may hold just as well as finite garbage."""
+    import nonfinite_ref as NF
+    dn = "bf16" if t.dtype == torch.bfloat16 else "f32"
+    sub = t.view(torch.int16 if dn == "bf16" else torch.int32)[region]
+    pats = torch.tensor([NF.signed_bits(i, dn) for i in range(NF.NPAT)], dtype=sub.dtype, device=t.device)
+    sub.copy_(pats[torch.arange(sub.numel(), device=t.device) % NF.NPAT].view(sub.shape))
+
+
+def _same_class(a, b):
+    """Non-finite in the same places (NaN for Inf passes) and bitwise equal everywhere else."""
+    fa, fb = torch.isfinite(a), torch.isfinite(b)
+    return torch.equal(fa, fb) and _same(torch.where(fa, a, torch.zeros_like(a)), torch.where(fb, b, torch.zeros_like(b)))
+
+
 CASES = [(dt, mode, pre) for dt in (torch.bfloat16, torch.float32) for mode in (0, 1, 2) for pre in (False, True)]
 
 
@@ -138,6 +154,60 @@ def test_attention_padding_content_and_empty_rows(gpu, dtype, mode, pre):
         assert not a["corr"][0].abs().sum().item()
     full = _run(qkv[2 * S:3 * S], dout[2 * S:3 * S], None if mask is None else _g(mask[2:3].contiguous()), 1, S, mode, pre)
     assert _same(a["o"][2 * S:3 * S], full["o"]) and _same(a["dqkv"][2 * S:3 * S], full["dqkv"])
+    # ... and neither does NaN / Inf there: the padded slots hold the five poison patterns instead of finite garbage
+    qkv3, dout3 = qkv.clone(), dout.clone()
+    mask3 = None if mask is None else mask.clone()
+    for b, L in enumerate(lens):
+        L = min(L, S)
+        _poison_fill(qkv3, slice(b * S + L, (b + 1) * S))
+        _poison_fill(dout3, slice(b * S + L, (b + 1) * S))
+        if mask3 is not None:
+            _poison_fill(mask3, (b, slice(L, S)))
+    assert not torch.isfinite(qkv3[37:S].float()).any() and not torch.isfinite(dout3[S + 37:2 * S].float()).any()
+    d = _run(_g(qkv3), _g(dout3), _g(mask3), B, S, mode, pre, seq_lens=sl)
+    for key in c:
+        assert _same(c[key], d[key]), f"mode {mode}: {key} depends on NaN / Inf in the padded slots"
+    for b, L in enumerate(lens):
+        r1 = b * S + min(L, S)
+        assert not d["o"][r1:(b + 1) * S].float().abs().sum().item() and not d["dqkv"][r1:(b + 1) * S].float().abs().sum().item(), f"row {b}: padded outputs"
+        assert not d["lse"][b, :, min(L, S):].abs().sum().item(), f"row {b}: padded lse"
+
+
+@pytest.mark.parametrize("dtype,mode,pre", CASES, ids=[f"{'bf16' if d == torch.bfloat16 else 'f32'}-m{m}-{'pre' if p else 'raw'}" for d, m, p in CASES])
+@under_guard
+def test_attention_poison_in_last_valid_row(gpu, dtype, mode, pre):
+    """A NaN / Inf in the LAST valid row of a batch entry: the ragged tile's clamp re-reads that row for the keys past L_b.  The entry must
+    come out exactly as the plain kernel run on that row alone with the same poison (non-finite in the same places, bitwise equal elsewhere),
+    its padded slots exactly zero, and the other entries bit for bit as without the poison."""
+    import nonfinite_ref as NF
+    lens = [65, 37, 129]
+    B, b, L = len(lens), 1, 37
+    qkv, dout, mask = _inputs(dtype, mode, lens, seed=4)
+    sl = _g(torch.tensor(lens, dtype=torch.int32, device="cuda"))
+    clean = _run(qkv, dout, mask, B, S, mode, pre, seq_lens=sl)
+    r0, r1, last = b * S, b * S + L, b * S + L - 1
+    dn = "bf16" if dtype == torch.bfloat16 else "f32"
+    for i, (name, col) in enumerate((("q", 5), ("k", H + 70), ("v", 2 * H + 3), ("dout", 9))):
+        pat = i + mode + int(pre)                                     # every pattern over the cases
+        qkv2, dout2 = qkv.clone(), dout.clone()
+        t = dout2 if name == "dout" else qkv2
+        t.view(torch.int16 if dn == "bf16" else torch.int32)[last, col] = NF.signed_bits(pat, dn)
+        qkv2, dout2 = _g(qkv2), _g(dout2)
+        rag = _run(qkv2, dout2, mask, B, S, mode, pre, seq_lens=sl)
+        m1 = None if mask is None else _g(mask[b:b + 1, :L].contiguous())
+        one = _run(qkv2[r0:r1], dout2[r0:r1], m1, 1, L, mode, pre)
+        tag = f"{NF.NAMES[pat % NF.NPAT]} in {name}, last valid row"
+        assert not torch.isfinite(rag["dqkv"][r0:r1].float()).all(), f"{tag}: laundered"
+        assert _same_class(rag["o"][r0:r1], one["o"]), f"{tag}: o"
+        assert _same_class(rag["lse"][b, :, :L], one["lse"][0]), f"{tag}: lse"
+        assert _same_class(rag["dqkv"][r0:r1], one["dqkv"]), f"{tag}: dq/dk/dv"
+        if mode == 2:
+            assert _same_class(rag["o_soft"][r0:r1], one["o_soft"]), f"{tag}: o_soft"
+        assert not rag["o"][r1:(b + 1) * S].float().abs().sum().item() and not rag["dqkv"][r1:(b + 1) * S].float().abs().sum().item(), f"{tag}: padded slots"
+        for key in clean:
+            for other in (0, 2):
+                x, y = (clean[key][other], rag[key][other]) if key in ("lse", "corr") else (clean[key][other * S:(other + 1) * S], rag[key][other * S:(other + 1) * S])
+                assert _same(x, y), f"{tag}: {key} of entry {other} changed"
 
 
 @under_guard
@@ -159,6 +229,13 @@ def test_mean_pool_len_bitwise(gpu):
             ref, reflp = ops.mean_pool_bwd(dy[b:b + 1], 1, L, lp_dtype=torch.bfloat16)
             assert _same(dx[b * S:b * S + L], ref) and _same(dxlp[b * S:b * S + L], reflp), f"row {b} (L={L}): backward"
         assert not dx[b * S + L:(b + 1) * S].abs().sum().item() and not dxlp[b * S + L:(b + 1) * S].float().abs().sum().item()
+    # NaN / Inf in the padded slots of x: the valid rows' means are bit for bit the same, an empty row's mean stays exactly zero
+    x2 = x.clone()
+    for b, L in enumerate(lens):
+        _poison_fill(x2, slice(b * S + L, (b + 1) * S))
+    assert not torch.isfinite(x2[:S]).any()
+    y2 = ops.mean_pool_fwd(_g(x2), B, S, seq_lens=sl)
+    assert _same(y, y2) and not y2[0].abs().sum().item()
     full = _g(torch.full((B,), S, dtype=torch.int32, device="cuda"))
     assert _same(ops.mean_pool_fwd(x, B, S, seq_lens=full), ops.mean_pool_fwd(x, B, S))
     assert _same(ops.mean_pool_bwd(dy, B, S, seq_lens=full)[0], ops.mean_pool_bwd(dy, B, S)[0])
