@@ -1,4 +1,4 @@
-"""ctypes binding of libtavhip.so (include/tavhip.h).
+"""ctypes binding of libtavhip.so: one table per public header under include/, the tables listed in ABIS.
 
 The library is the product: there is no CPU or eager-PyTorch fallback.  `lib()` raises if the shared object has not
 been built (run `python -c "import __graft_entry__ as g; g.build()"` or `make -C multi-modal-emotion_amd/csrc`).
@@ -6,6 +6,7 @@ Every wrapper turns a non-zero return code into RuntimeError carrying tav_error_
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -176,8 +177,11 @@ _SIGS = {
     "tav_adamw_chunked_groups": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp]),
 }
 
-# include/tavhip_align.h: the forced-alignment entry points.  A table of their own, bound by lib() like _SIGS but not part of
-# declared_symbols(): the symbol set of include/tavhip.h is pinned by a recorded table ("alignment ABI").
+# Every public header after include/tavhip.h has a table, a version constant and a version function of its own and one row in ABIS
+# below; lib() binds and checks all rows alike.  declared_symbols() stays the main table alone: the symbol set of include/tavhip.h is
+# pinned by a recorded table ("Adding an entry-point family").
+
+# include/tavhip_align.h: the forced-alignment entry points.
 ALIGN_ABI_VERSION = 1
 
 
@@ -199,8 +203,7 @@ _ALIGN_SIGS = {
     "tav_ctc_align": (C.c_int, [C.POINTER(CtcAlignArgs), vp]),
 }
 
-# include/tavhip_rnn.h: the recurrent entry points (LSTM recurrence, log-sigmoid).  A third table, bound like _ALIGN_SIGS and for the
-# same reason outside declared_symbols().
+# include/tavhip_rnn.h: the recurrent entry points (LSTM recurrence, log-sigmoid).
 RNN_ABI_VERSION = 1
 
 
@@ -231,7 +234,7 @@ _RNN_SIGS = {
 }
 
 # include/tavhip_conv.h: the dense 3-D convolution entry points (Conv3d forward / input gradient / weight gradient, flatten + Linear,
-# sigmoid).  A fourth table, bound like the two above and for the same reason outside declared_symbols().
+# sigmoid).
 CONV_ABI_VERSION = 1
 
 
@@ -279,11 +282,38 @@ _CONV_SIGS = {
     "tav_sigmoid_bwd": (C.c_int, [vp, vp, vp, i64, vp]),
 }
 
+
+class Abi(NamedTuple):
+    """One public header and its binding.  `version` is the constant as it stood at import, for readers of the table; lib() reads the
+    constant named `version_const` when it is called, so that a changed constant is what the loaded library is held to."""
+    header: str            # file name under include/
+    version_fn: str        # the exported function that returns the library's version of this family
+    version_const: str     # the module constant of this file that holds the binding's version
+    version: int
+    sigs: dict             # name -> (restype, argtypes): the table object itself
+    structs: dict          # C struct name -> ctypes Structure class
+    what: str              # the family's word in the version message ("" for the main header)
+
+
+ABIS = (
+    Abi("tavhip.h", "tav_version", "ABI_VERSION", ABI_VERSION, _SIGS,
+        {"tav_gemm_nt_args": GemmNTArgs, "tav_gemm_tn_args": GemmTNArgs, "tav_gemm_tn_problem": GemmTNProblem, "tav_attn_args": AttnArgs,
+         "tav_ln_args": LnArgs, "tav_ln_reduce_item": LnReduceItem, "tav_text_embed_args": TextEmbedArgs, "tav_clip_xform": ClipXform,
+         "tav_resample_args": ResampleArgs}, ""),
+    Abi("tavhip_align.h", "tav_align_version", "ALIGN_ABI_VERSION", ALIGN_ABI_VERSION, _ALIGN_SIGS,
+        {"tav_align_plan": AlignPlan, "tav_ctc_align_args": CtcAlignArgs}, "alignment"),
+    Abi("tavhip_rnn.h", "tav_rnn_version", "RNN_ABI_VERSION", RNN_ABI_VERSION, _RNN_SIGS,
+        {"tav_lstm_plan": LstmPlan, "tav_lstm_fwd_args": LstmFwdArgs, "tav_lstm_bwd_args": LstmBwdArgs}, "recurrent"),
+    Abi("tavhip_conv.h", "tav_conv_version", "CONV_ABI_VERSION", CONV_ABI_VERSION, _CONV_SIGS,
+        {"tav_conv3d_plan": Conv3dPlan, "tav_conv3d_fwd_args": Conv3dFwdArgs, "tav_conv3d_wgrad_args": Conv3dWgradArgs,
+         "tav_flat_linear_fwd_args": FlatLinearFwdArgs, "tav_flat_linear_bwd_args": FlatLinearBwdArgs}, "convolution"),
+)
+
 _lib = None
 
 
 def lib():
-    """Load (once) and return the ctypes handle; fail loudly when the HIP library is absent."""
+    """Load (once) and return the ctypes handle; fail loudly when the HIP library is absent, lacks a declared symbol or is of another version."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -291,18 +321,16 @@ def lib():
                 f"{LIB_PATH} is missing: the TAV hot path has no fallback. Build it with "
                 "`make -C multi-modal-emotion_amd/csrc` (hipcc --offload-arch=gfx950).")
         h = C.CDLL(LIB_PATH)
-        for table in (_SIGS, _ALIGN_SIGS, _RNN_SIGS, _CONV_SIGS):
-            for name, (res, args) in table.items():
-                fn = getattr(h, name)      # AttributeError here = header/library mismatch
+        for abi in ABIS:
+            for name, (res, args) in abi.sigs.items():
+                fn = getattr(h, name, None)
+                if fn is None:
+                    raise RuntimeError(f"{LIB_PATH} does not export {name}, which include/{abi.header} declares; rebuild")
                 fn.restype, fn.argtypes = res, args
-        if h.tav_version() != ABI_VERSION:
-            raise RuntimeError(f"libtavhip ABI {h.tav_version()} != binding {ABI_VERSION}; rebuild")
-        if h.tav_align_version() != ALIGN_ABI_VERSION:
-            raise RuntimeError(f"libtavhip alignment ABI {h.tav_align_version()} != binding {ALIGN_ABI_VERSION}; rebuild")
-        if h.tav_rnn_version() != RNN_ABI_VERSION:
-            raise RuntimeError(f"libtavhip recurrent ABI {h.tav_rnn_version()} != binding {RNN_ABI_VERSION}; rebuild")
-        if h.tav_conv_version() != CONV_ABI_VERSION:
-            raise RuntimeError(f"libtavhip convolution ABI {h.tav_conv_version()} != binding {CONV_ABI_VERSION}; rebuild")
+        for abi in ABIS:
+            got, want = getattr(h, abi.version_fn)(), globals()[abi.version_const]
+            if got != want:
+                raise RuntimeError(f"libtavhip {abi.what + ' ' if abi.what else ''}ABI {got} != binding {want}; rebuild")
         _lib = h
     return _lib
 

@@ -3,18 +3,9 @@
 #include <stdio.h>
 #include <vector>
 #include "../../multi-modal-emotion_amd/csrc/align_plan.h"
+#include "check.h"
 
 using namespace tav::plan;
-static int failed = 0;
-#define CHECK(cond, ...)                                \
-    do {                                                \
-        if (!(cond)) {                                  \
-            ++failed;                                   \
-            printf("FAILED %s : ", #cond);              \
-            printf(__VA_ARGS__);                        \
-            printf("\n");                               \
-        }                                               \
-    } while (0)
 
 int main() {
     const std::vector<int64_t> Ts = {1, 2, 3, 63, 64, 65, 128, 499, 714, 715, 1499, 3000, 4095, ALIGN_MAX_T};
@@ -102,6 +93,5 @@ int main() {
               log_softmax_validate(true, 4, LSM_MAX_V + 1, 1 << 20, 1 << 20) == TAV_ERR_SHAPE && log_softmax_validate(true, 5, 29, 29, 33) == 0, "log-softmax");
     CHECK(log_softmax_blocks(1) == 1 && log_softmax_blocks(4) == 1 && log_softmax_blocks(5) == 2, "log-softmax grid");
     printf("plans %ld in_ws %ld\n", plans, in_ws);
-    printf("ok: %d failed checks\n", failed);
-    return failed ? 1 : 0;
+    return check_summary();
 }

@@ -4,18 +4,9 @@
 #include <stdio.h>
 #include <vector>
 #include "../../multi-modal-emotion_amd/csrc/conv3d_plan.h"
+#include "check.h"
 
 using namespace tav::plan;
-static int failed = 0;
-#define CHECK(cond, ...)                                \
-    do {                                                \
-        if (!(cond)) {                                  \
-            ++failed;                                   \
-            printf("FAILED %s : ", #cond);              \
-            printf(__VA_ARGS__);                        \
-            printf("\n");                               \
-        }                                               \
-    } while (0)
 
 int main() {
     long plans = 0, refused = 0;
@@ -117,6 +108,5 @@ int main() {
     CHECK(sigmoid_validate(true, 1) == 0 && sigmoid_validate(false, 1) == TAV_ERR_NULL && sigmoid_validate(true, 0) == TAV_ERR_SHAPE, "sigmoid");
     CHECK(conv_dz_validate(true, 64, TAV_F32) == 0 && conv_dz_validate(true, 6, TAV_F32) == TAV_ERR_SHAPE && conv_dz_validate(false, 64, TAV_F32) == TAV_ERR_NULL, "dz");
     printf("%ld plans checked, %ld shapes refused\n", plans, refused);
-    printf("ok: %d failed checks\n", failed);
-    return failed ? 1 : 0;
+    return check_summary();
 }

@@ -16,19 +16,9 @@
 #include <vector>
 
 #include "../../multi-modal-emotion_amd/csrc/entry_plan.h"
+#include "check.h"
 
 using namespace tav::plan;
-
-static int failures = 0;
-#define CHECK(cond, ...)                                                  \
-    do {                                                                  \
-        if (!(cond)) {                                                    \
-            ++failures;                                                   \
-            std::printf("FAILED %s:%d %s -- ", __FILE__, __LINE__, #cond); \
-            std::printf(__VA_ARGS__);                                     \
-            std::printf("\n");                                            \
-        }                                                                 \
-    } while (0)
 
 static void* const PTR = (void*)0x1000;   // stands for a device pointer: tested for NULL-ness only
 static const int F32 = TAV_F32, BF16 = TAV_BF16;
@@ -293,6 +283,5 @@ int main() {
     audio_frontend();
     fp8_specaug_media();
     for (const auto& f : findings) std::printf("finding %s : %s\n", f.first.c_str(), f.second.c_str());
-    std::printf("ok: %d failed checks\n", failures);
-    return failures ? 1 : 0;
+    return check_summary();
 }

@@ -12,19 +12,9 @@
 #include <vector>
 
 #include "../../multi-modal-emotion_amd/csrc/gemm_plan.h"
+#include "check.h"
 
 using namespace tav::plan;
-
-static int failures = 0;
-#define CHECK(cond, ...)                                                  \
-    do {                                                                  \
-        if (!(cond)) {                                                    \
-            ++failures;                                                   \
-            std::printf("FAILED %s:%d %s -- ", __FILE__, __LINE__, #cond); \
-            std::printf(__VA_ARGS__);                                     \
-            std::printf("\n");                                            \
-        }                                                                 \
-    } while (0)
 
 static const void* const PTR = (const void*)0x1000;   // stands for a device pointer: tested for NULL-ness only
 static const int F32 = TAV_F32, BF16 = TAV_BF16, FP8 = TAV_FP8;
@@ -236,6 +226,5 @@ int main() {
     sweep_nt_keys();
     sweep_tn_splits();
     sweep_tn_grouped();
-    std::printf("%s: %d failed checks\n", failures ? "FAILED" : "ok", failures);
-    return failures ? 1 : 0;
+    return check_summary();
 }

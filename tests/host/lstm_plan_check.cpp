@@ -3,18 +3,9 @@
 #include <stdio.h>
 #include <vector>
 #include "../../multi-modal-emotion_amd/csrc/lstm_plan.h"
+#include "check.h"
 
 using namespace tav::plan;
-static int failed = 0;
-#define CHECK(cond, ...)                                \
-    do {                                                \
-        if (!(cond)) {                                  \
-            ++failed;                                   \
-            printf("FAILED %s : ", #cond);              \
-            printf(__VA_ARGS__);                        \
-            printf("\n");                               \
-        }                                               \
-    } while (0)
 
 int main() {
     long plans = 0, refused = 0;
@@ -97,6 +88,5 @@ int main() {
     CHECK(logsigmoid_validate(false, 1) == TAV_ERR_NULL && logsigmoid_validate(true, 0) == TAV_ERR_SHAPE && logsigmoid_validate(true, 4097) == 0, "log-sigmoid");
     CHECK(logsigmoid_blocks(1) == 1 && logsigmoid_blocks(256) == 1 && logsigmoid_blocks(257) == 2, "log-sigmoid grid");
     printf("plans %ld refused %ld\n", plans, refused);
-    printf("ok: %d failed checks\n", failed);
-    return failed ? 1 : 0;
+    return check_summary();
 }

@@ -1,17 +1,17 @@
-"""CPU: the C-ABI library loads and exports every symbol include/tavhip.h declares (no compute calls without a GPU),
+"""CPU: the C-ABI library loads and exports every symbol the headers under include/ declare (no compute calls without a GPU), a library of
+another version or without a declared symbol is refused, include/tavhip.h matches its binding type by type (tests/abi_check.py),
 argument validation returns TAV_ERR_* before anything is launched, the product path refuses to run without the GPU /
 library (no CPU fallback), and the host-side logic (masks, samplers, schedules, key remaps, synthetic batches)."""
 import ctypes as C
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_check
 import tav_amd  # noqa: F401
 from oracle import tav_oracle as O
 from tav_amd import _lib, synthetic
@@ -23,20 +23,16 @@ from tav_amd.utils.global_functions import MySampler, Metrics, arg_parse
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
-    src = open(os.path.join(ROOT, "include", "tavhip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(tav_[a-z0-9_]+)\s*\(", src)))
-
-
 def test_every_declared_symbol_is_exported_and_bound():
     h = _lib.lib()
-    names = _declared()
-    assert len(names) >= 50
-    for n in names:
-        assert hasattr(h, n), f"{n} declared in include/tavhip.h but not exported by libtavhip.so"
-    assert set(names) == set(_lib.declared_symbols()), set(names) ^ set(_lib.declared_symbols())
-    assert h.tav_version() == _lib.ABI_VERSION
+    assert sorted(a.header for a in _lib.ABIS) == sorted(os.listdir(os.path.join(ROOT, "include")))      # no header without a row
+    for abi in _lib.ABIS:
+        names = abi_check.declared_names(abi_check.header_text(abi.header))
+        for n in names:
+            assert hasattr(h, n), f"{n} declared in include/{abi.header} but not exported by libtavhip.so"
+        assert names == set(abi.sigs), names ^ set(abi.sigs)
+        assert getattr(h, abi.version_fn)() == abi.version == getattr(_lib, abi.version_const)
+    assert len(_lib.ABIS[0].sigs) >= 50 and set(_lib.ABIS[0].sigs) == set(_lib.declared_symbols())
 
 
 def test_argument_validation_without_gpu():
@@ -755,89 +751,52 @@ def test_bucket_norm_is_used_only_when_the_gradients_live_in_the_buckets():
     assert not opt._grads_in_norm_buffers(ps)
 
 
-# ---- include/tavhip.h against the ctypes binding: a wrong argtype or field order is memory corruption, not an error
-_STRUCTS = {"tav_gemm_nt_args": "GemmNTArgs", "tav_gemm_tn_args": "GemmTNArgs", "tav_gemm_tn_problem": "GemmTNProblem", "tav_attn_args": "AttnArgs",
-            "tav_ln_args": "LnArgs", "tav_ln_reduce_item": "LnReduceItem", "tav_text_embed_args": "TextEmbedArgs", "tav_clip_xform": "ClipXform",
-            "tav_resample_args": "ResampleArgs"}
-_SCALARS = {"int": "int32", "int32_t": "int32", "int64_t": "int64", "uint64_t": "uint64", "float": "float", "double": "double"}
-
-
-def _c_class(decl):
-    """Class of a C type as the header writes it: pointer, char*, int32, int64, uint64, float, double."""
-    t = " ".join(decl.replace("const", " ").split())
-    if "*" in t:
-        return "char*" if t.replace(" ", "") == "char*" else "pointer"
-    return _SCALARS[t]
-
-
-def _ctypes_class(t):
-    if t is C.c_char_p:
-        return "char*"
-    if t is C.c_void_p or hasattr(t, "contents") or isinstance(t, type(C.POINTER(C.c_int))):
-        return "pointer"
-    return {C.c_int32: "int32", C.c_int64: "int64", C.c_uint64: "uint64", C.c_float: "float", C.c_double: "double"}[t]
-
-
-def _parse_header():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tavhip.h")).read(), flags=re.S)
-    structs = {}
-    for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
-        fields = []
-        for decl in filter(None, (d.strip() for d in body.split(";"))):
-            m = re.match(r"(.*?[\s\*])(\w+(?:\[\d+\])?(?:\s*,\s*\w+(?:\[\d+\])?)*)$", decl, flags=re.S)
-            assert m, decl
-            for item in m.group(2).split(","):
-                fname, _, dim = item.strip().partition("[")
-                fields.append((fname, _c_class(m.group(1)), int(dim[:-1]) if dim else 0))
-        structs[name] = fields
-    protos = {}
-    for res, name, args in re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(tav_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [a.strip() for a in args.split(",")]
-        if args == ["void"]:
-            args = []
-        kinds = []
-        for a in args:
-            m = re.match(r"(.*?[\s\*])(\w+)$", a, flags=re.S)             # type, then the parameter's name
-            kinds.append((_c_class(m.group(1)), next((s for s in structs if re.search(r"\b%s\b" % s, m.group(1))), None)))
-        protos[name] = (_c_class(res), kinds)
-    return structs, protos
-
-
+# ---- the headers against the ctypes binding (tests/abi_check.py): a wrong argtype or field order is memory corruption, not an error
 def test_binding_matches_the_header_type_by_type(tmp_path):
     """Every prototype of include/tavhip.h against _lib._SIGS (arity, result and argument classes, which struct a struct pointer points to),
     every struct against its ctypes Structure (field names, order, classes, array lengths), and sizeof / offsetof of every struct as a C
     compiler lays it out."""
-    structs, protos = _parse_header()
-    assert set(protos) == set(_lib._SIGS) and len(protos) >= 90
-    for name, (res, args) in protos.items():
-        cres, cargs = _lib._SIGS[name]
-        assert _ctypes_class(cres) == res, f"{name}: result {cres} vs {res}"
-        assert len(cargs) == len(args), f"{name}: {len(cargs)} argtypes, {len(args)} parameters"
-        for k, (ct, (kind, struct)) in enumerate(zip(cargs, args)):
-            assert _ctypes_class(ct) == kind, f"{name}: argument {k} is {ct}, the header says {kind}"
-            if struct in _STRUCTS:
-                assert ct._type_ is getattr(_lib, _STRUCTS[struct]), f"{name}: argument {k} points to {ct._type_}, the header says {struct}"
-    assert set(_STRUCTS) <= set(structs)
-    for cname, pyname in _STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert [f[0] for f in cls._fields_] == [f[0] for f in structs[cname]], cname
-        for (fname, ct), (_, kind, dim) in zip(cls._fields_, structs[cname]):
-            if dim:
-                assert ct._length_ == dim and _ctypes_class(ct._type_) == kind, f"{cname}.{fname}"
-            else:
-                assert _ctypes_class(ct) == kind, f"{cname}.{fname}"
-    cc = next((p for p in (shutil.which(c) for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang")) if p), None)
-    assert cc is not None, "no host C compiler: the library was built here, so one exists"
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "tavhip.h"', 'int main(void) {']
-    for cname in _STRUCTS:
-        lines.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'    printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _, _ in structs[cname]]
-    lines += ['    return 0;', '}']
-    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
-    laid = dict(ln.split() for ln in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
-    for cname, pyname in _STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert C.sizeof(cls) == int(laid[cname]), f"sizeof({cname})"
-        for f, _ in cls._fields_:
-            assert getattr(cls, f).offset == int(laid[f"{cname}.{f}"]), f"offsetof({cname}, {f})"
+    # tav_loop_acc: the accumulator of tav_step_stats lives on the device and is never built on the host; the binding passes a pointer
+    protos = abi_check.check_binding(abi_check.abi("tavhip.h"), tmp_path, unbound=("tav_loop_acc",))
+    assert len(protos) >= 90
+
+
+_FAMILY = {"tavhip.h": "libtavhip", "tavhip_align.h": "libtavhip alignment", "tavhip_rnn.h": "libtavhip recurrent", "tavhip_conv.h": "libtavhip convolution"}
+
+
+@pytest.mark.parametrize("header", list(_FAMILY))
+def test_a_wrong_version_is_refused_for_every_family(monkeypatch, header):
+    abi = abi_check.abi(header)
+    assert abi.what in _FAMILY[header]
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, abi.version_const, abi.version + 1)
+    with pytest.raises(RuntimeError, match=rf"{_FAMILY[header]} ABI {abi.version} != binding {abi.version + 1}; rebuild"):
+        _lib.lib()
+    assert _lib._lib is None                                      # nothing half-checked is kept
+    monkeypatch.undo()
+    assert getattr(_lib.lib(), abi.version_fn)() == abi.version
+
+
+def test_a_symbol_the_library_does_not_export_is_refused(monkeypatch):
+    abi = abi_check.abi("tavhip_rnn.h")
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setitem(abi.sigs, "tav_no_such_symbol", (C.c_int, []))
+    with pytest.raises(RuntimeError, match=r"tav_no_such_symbol.*include/tavhip_rnn\.h.*; rebuild$"):
+        _lib.lib()
+    monkeypatch.undo()
+    assert "tav_no_such_symbol" not in _lib._RNN_SIGS and _lib.lib() is not None
+
+
+def test_the_header_parser_reads_array_fields_and_refuses_the_rest():
+    structs, protos = abi_check.parse_header_text("typedef struct t {\n    int32_t nf, frame[32]; const float* scale; uint64_t seed; double sum;\n} t;\n"
+                                                  "const char* tav_name(const t* a, void* stream);\nint tav_none(void);\n")
+    assert structs == {"t": [("nf", "int32", 0), ("frame", "int32", 32), ("scale", "pointer", 0), ("seed", "uint64", 0), ("sum", "double", 0)]}
+    assert protos == {"tav_name": ("char*", [("pointer", "t"), ("pointer", None)]), "tav_none": ("int32", [])}
+    for bad in ("typedef struct t {\n    int32_t frame[N];\n} t;\n",                  # a length that is not a literal
+                "typedef struct t {\n    size_t n;\n} t;\n",                           # a type the binding has no class for
+                "typedef struct t {\n    int32_t (*fn)(int);\n} t;\n",
+                "struct t {\n    int32_t n;\n};\n",                                    # not the typedef form: would be skipped, not read
+                "int tav_f(int32_t (*cb)(int), void* stream);\n",
+                "int tav_f(unsigned n);\n"):
+        with pytest.raises(ValueError):
+            abi_check.parse_header_text(bad)

@@ -1,21 +1,20 @@
 """CPU: the dense 3-D convolution's host side.
 
 tests/conv3d_ref.py against torch.nn.functional.conv3d, its autograd gradients and nn.Linear in float64; the mutants of that reference, each
-caught by the inputs the GPU tests use; csrc/conv3d_plan.h alone under ASan + UBSan as a program of its own; include/tavhip_conv.h against
-_lib._CONV_SIGS type by type; the other three symbol tables untouched; argument faults through the built library; and the pieces of
-VisualClassification and its entrypoint that need no GPU."""
+caught by the inputs the GPU tests use; csrc/conv3d_plan.h alone under ASan + UBSan as a program of its own (tests/host_program.py);
+include/tavhip_conv.h against its row of _lib.ABIS type by type and the families kept apart (tests/abi_check.py); argument faults through
+the built library; and the pieces of VisualClassification and its entrypoint that need no GPU."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_check
 import conv3d_ref as R
 import tav_amd  # noqa: F401
-import test_ctc_align_host as AH
+from host_program import run_alone_under_sanitizers
 from tav_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -115,73 +114,16 @@ def test_exact_integer_generator_and_chain_lengths():
 
 # ---------------------------------------------------------------------------------------------- conv3d_plan.h alone
 def test_conv3d_plan_header_alone_under_sanitizers(tmp_path):
-    compilers = AH._host_compilers()
-    assert compilers, "no host C++ compiler: the library was built here, so one exists"
-    for k, (cxx, extra) in enumerate(compilers):
-        exe = tmp_path / f"conv3d_plan_check_{k}"
-        subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *extra,
-                        os.path.join(ROOT, "tests", "host", "conv3d_plan_check.cpp"), "-o", str(exe)], check=True)
-        run = subprocess.run([str(exe)], capture_output=True, text=True)
-        lines = run.stdout.splitlines()
-        failed = [ln for ln in lines if ln.startswith("FAILED")]
-        assert run.returncode == 0 and not failed and not run.stderr, cxx + "\n" + "\n".join(failed[:20]) + "\n" + run.stderr[-4000:]
-        assert lines[-1] == "ok: 0 failed checks"
+    run_alone_under_sanitizers("conv3d_plan_check.cpp", tmp_path)
 
 
 # ---------------------------------------------------------------------------------------------- header against binding
-_STRUCTS = {"tav_conv3d_plan": "Conv3dPlan", "tav_conv3d_fwd_args": "Conv3dFwdArgs", "tav_conv3d_wgrad_args": "Conv3dWgradArgs",
-            "tav_flat_linear_fwd_args": "FlatLinearFwdArgs", "tav_flat_linear_bwd_args": "FlatLinearBwdArgs"}
-
-
 def test_conv_binding_matches_its_header_type_by_type(tmp_path):
-    structs, protos = AH._parse(AH._header("tavhip_conv.h"))
-    assert set(protos) == set(_lib._CONV_SIGS) and len(protos) == 14
-    for name, (res, args) in protos.items():
-        cres, cargs = _lib._CONV_SIGS[name]
-        assert AH._ctypes_class(cres) == res, name
-        assert len(cargs) == len(args), name
-        for k, (ct, (kind, struct)) in enumerate(zip(cargs, args)):
-            assert AH._ctypes_class(ct) == kind, f"{name}: argument {k} is {ct}, the header says {kind}"
-            if struct:
-                assert ct._type_ is getattr(_lib, _STRUCTS[struct]), f"{name}: argument {k}"
-    assert set(structs) == set(_STRUCTS)
-    for cname, pyname in _STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert [f[0] for f in cls._fields_] == [f[0] for f in structs[cname]], cname
-        for (fname, ct), (_, kind) in zip(cls._fields_, structs[cname]):
-            assert AH._ctypes_class(ct) == kind, f"{cname}.{fname}"
-    cc = next((p for p in (shutil.which(c) for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang")) if p), None)
-    assert cc is not None
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "tavhip_conv.h"', 'int main(void) {']
-    for cname in _STRUCTS:
-        lines.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'    printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in structs[cname]]
-    lines += ['    return 0;', '}']
-    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
-    laid = dict(ln.split() for ln in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
-    for cname, pyname in _STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert C.sizeof(cls) == int(laid[cname]), cname
-        for f, _ in cls._fields_:
-            assert getattr(cls, f).offset == int(laid[f"{cname}.{f}"]), f"{cname}.{f}"
-    h = _lib.lib()
-    assert h.tav_conv_version() == _lib.CONV_ABI_VERSION
-    for name in _lib._CONV_SIGS:
-        assert hasattr(h, name)
+    assert len(abi_check.check_binding(abi_check.abi("tavhip_conv.h"), tmp_path)) == 14
 
 
 def test_the_other_three_symbol_tables_are_unchanged():
-    import re
-    declared = set(re.findall(r"\b(tav_[a-z0-9_]+)\s*\(", AH._header("tavhip.h")))
-    assert declared == set(_lib.declared_symbols()) == set(_lib._SIGS) and len(declared) == 92
-    assert len(_lib._ALIGN_SIGS) == 5 and len(_lib._RNN_SIGS) == 7
-    for table in (_lib._SIGS, _lib._ALIGN_SIGS, _lib._RNN_SIGS):
-        assert set(table).isdisjoint(_lib._CONV_SIGS)
-    assert _lib.ABI_VERSION == 7 and _lib.lib().tav_version() == 7 and _lib.ALIGN_ABI_VERSION == 1 and _lib.RNN_ABI_VERSION == 1
-    for other in ("tavhip.h", "tavhip_align.h", "tavhip_rnn.h"):
-        text = open(os.path.join(ROOT, "include", other)).read()
-        assert "conv3d" not in text and "flat_linear" not in text and "tav_sigmoid" not in text, other
+    abi_check.check_families_apart()
 
 
 # ---------------------------------------------------------------------------------------------- argument faults, nothing launches

@@ -1,20 +1,19 @@
 """CPU: the forced alignment's host side.
 
 The numpy restatement (tests/ctc_align_ref.py) against the record of the reference's own get_trellis / backtrack (tests/golden/
-ctc_align_golden.npz) bit for bit; csrc/align_plan.h alone under ASan + UBSan as a program of its own; include/tavhip_align.h against
-_lib._ALIGN_SIGS type by type; include/tavhip.h's symbol set untouched; argument faults through the built library; and the Python
-pieces of run_scripts/get_times.py that need no GPU."""
+ctc_align_golden.npz) bit for bit; csrc/align_plan.h alone under ASan + UBSan as a program of its own (tests/host_program.py);
+include/tavhip_align.h against its row of _lib.ABIS type by type and the families kept apart (tests/abi_check.py); argument faults
+through the built library; and the Python pieces of run_scripts/get_times.py that need no GPU."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_check
 import ctc_align_ref as R
 import tav_amd  # noqa: F401
+from host_program import run_alone_under_sanitizers
 from tav_amd import _lib
 from tav_amd.run_scripts import get_times as GT
 
@@ -69,116 +68,19 @@ def test_restatement_edges():
 
 
 # ---------------------------------------------------------------------------------------------- align_plan.h alone
-def _host_compilers():
-    found, seen = [], set()
-    for cxx, extra in (("/opt/rocm/llvm/bin/clang++", []), ("clang++", []), ("g++", ["-static-libasan", "-static-libubsan"])):
-        path = shutil.which(cxx)
-        if path and os.path.realpath(path) not in seen:
-            seen.add(os.path.realpath(path))
-            found.append((path, extra))
-    return found
-
-
 def test_plan_header_alone_under_sanitizers(tmp_path):
-    compilers = _host_compilers()
-    assert compilers, "no host C++ compiler: the library was built here, so one exists"
-    for k, (cxx, extra) in enumerate(compilers):
-        exe = tmp_path / f"align_plan_check_{k}"
-        subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *extra,
-                        os.path.join(ROOT, "tests", "host", "align_plan_check.cpp"), "-o", str(exe)], check=True)
-        run = subprocess.run([str(exe)], capture_output=True, text=True)
-        lines = run.stdout.splitlines()
-        failed = [ln for ln in lines if ln.startswith("FAILED")]
-        assert run.returncode == 0 and not failed and not run.stderr, cxx + "\n" + "\n".join(failed[:20]) + "\n" + run.stderr[-4000:]
-        assert lines[-1] == "ok: 0 failed checks"
+    run_alone_under_sanitizers("align_plan_check.cpp", tmp_path)
 
 
 # ---------------------------------------------------------------------------------------------- header against binding
-_SCALARS = {"int": "int32", "int32_t": "int32", "int64_t": "int64", "float": "float"}
-_STRUCTS = {"tav_align_plan": "AlignPlan", "tav_ctc_align_args": "CtcAlignArgs"}
-
-
-def _c_class(decl):
-    t = " ".join(decl.replace("const", " ").split())
-    return "pointer" if "*" in t else _SCALARS[t]
-
-
-def _ctypes_class(t):
-    if t is C.c_void_p or hasattr(t, "contents") or isinstance(t, type(C.POINTER(C.c_int))):
-        return "pointer"
-    return {C.c_int32: "int32", C.c_int64: "int64", C.c_float: "float"}[t]
-
-
-def _header(name):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
-def _parse(src):
-    structs = {}
-    for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
-        fields = []
-        for decl in filter(None, (d.strip() for d in body.split(";"))):
-            m = re.match(r"(.*?[\s\*])(\w+(?:\s*,\s*\w+)*)$", decl, flags=re.S)
-            assert m, decl
-            fields += [(item.strip(), _c_class(m.group(1))) for item in m.group(2).split(",")]
-        structs[name] = fields
-    protos = {}
-    for res, name, args in re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(tav_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [a.strip() for a in args.split(",")]
-        kinds = []
-        for a in ([] if args == ["void"] else args):
-            m = re.match(r"(.*?[\s\*])(\w+)$", a, flags=re.S)
-            kinds.append((_c_class(m.group(1)), next((s for s in structs if re.search(r"\b%s\b" % s, m.group(1))), None)))
-        protos[name] = (_c_class(res), kinds)
-    return structs, protos
-
-
 def test_align_binding_matches_its_header_type_by_type(tmp_path):
-    structs, protos = _parse(_header("tavhip_align.h"))
-    assert set(protos) == set(_lib._ALIGN_SIGS) and len(protos) == 5
-    for name, (res, args) in protos.items():
-        cres, cargs = _lib._ALIGN_SIGS[name]
-        assert _ctypes_class(cres) == res, name
-        assert len(cargs) == len(args), name
-        for k, (ct, (kind, struct)) in enumerate(zip(cargs, args)):
-            assert _ctypes_class(ct) == kind, f"{name}: argument {k} is {ct}, the header says {kind}"
-            if struct:
-                assert ct._type_ is getattr(_lib, _STRUCTS[struct]), f"{name}: argument {k}"
-    assert set(structs) == set(_STRUCTS)
-    for cname, pyname in _STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert [f[0] for f in cls._fields_] == [f[0] for f in structs[cname]], cname
-        for (fname, ct), (_, kind) in zip(cls._fields_, structs[cname]):
-            assert _ctypes_class(ct) == kind, f"{cname}.{fname}"
-    cc = next((p for p in (shutil.which(c) for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang")) if p), None)
-    assert cc is not None
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "tavhip_align.h"', 'int main(void) {']
-    for cname in _STRUCTS:
-        lines.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'    printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in structs[cname]]
-    lines += ['    return 0;', '}']
-    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
-    laid = dict(ln.split() for ln in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
-    for cname, pyname in _STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert C.sizeof(cls) == int(laid[cname]), cname
-        for f, _ in cls._fields_:
-            assert getattr(cls, f).offset == int(laid[f"{cname}.{f}"]), f"{cname}.{f}"
-    h = _lib.lib()
-    assert h.tav_align_version() == _lib.ALIGN_ABI_VERSION
-    for name in _lib._ALIGN_SIGS:
-        assert hasattr(h, name)
+    assert len(abi_check.check_binding(abi_check.abi("tavhip_align.h"), tmp_path)) == 5
 
 
 def test_main_header_symbol_set_is_unchanged():
     """The alignment entry points live in their own header and table: include/tavhip.h declares exactly what _SIGS binds, as before, and
     none of the new names; the main ABI version did not move."""
-    declared = set(re.findall(r"\b(tav_[a-z0-9_]+)\s*\(", _header("tavhip.h")))
-    assert declared == set(_lib.declared_symbols()) == set(_lib._SIGS) and len(declared) == 92
-    assert declared.isdisjoint(_lib._ALIGN_SIGS)
-    assert _lib.ABI_VERSION == 7 and _lib.lib().tav_version() == 7
-    assert "ctc" not in open(os.path.join(ROOT, "include", "tavhip.h")).read()
+    abi_check.check_families_apart()
 
 
 # ---------------------------------------------------------------------------------------------- argument faults, nothing launches

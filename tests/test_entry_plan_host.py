@@ -1,18 +1,15 @@
 """CPU: the host decisions of the entry points outside gemm.hip (csrc/entry_plan.h) against the table recorded from the parent of the commit
 that moved them out of the .hip files (tests/golden/entry_plan_golden.json, made by tests/make_entry_plan_golden.py), twice: through the
 built library, and through the header compiled stand-alone under AddressSanitizer + UndefinedBehaviorSanitizer
-(tests/host/entry_plan_check.cpp), which also checks the invariants of every launch geometry and workspace layout over a sweep that
-includes the caps."""
+(tests/host/entry_plan_check.cpp, built and run by tests/host_program.py), which also checks the invariants of every launch geometry and
+workspace layout over a sweep that includes the caps."""
 import functools
 import json
 import os
 import re
-import shutil
-import subprocess
-
-import pytest
 
 import make_entry_plan_golden as G
+from host_program import run_alone_under_sanitizers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -101,34 +98,11 @@ def test_dispatch_lists_accept_what_the_record_says():
                 assert set(lst) == {(a, b) for (a,) in _recorded_dtypes("floats") for (b,) in _recorded_dtypes("floats")}, entry
 
 
-def _host_compilers():
-    """[(compiler, extra flags)] of every host compiler here: the sanitizer runtimes linked statically (clang's default), so that the
-    program starts whatever the environment preloads into every process."""
-    found, seen = [], set()
-    for cxx, extra in (("/opt/rocm/llvm/bin/clang++", []), ("clang++", []), ("g++", ["-static-libasan", "-static-libubsan"])):
-        path = shutil.which(cxx)
-        if path and os.path.realpath(path) not in seen:
-            seen.add(os.path.realpath(path))
-            found.append((path, extra))
-    return found
-
-
 def test_header_alone_under_sanitizers(tmp_path):
     """entry_plan.h built without HIP, with ASan + UBSan, as a program of its own (no sanitizer runtime is loaded into this process), by
     every host compiler of the machine: nothing reported, every invariant holds, its size queries equal the recorded table, and the
     narrowings it finds are the known ones."""
-    compilers = _host_compilers()
-    if not compilers:
-        pytest.skip("no host C++ compiler (g++ or clang++) on this machine")
-    for k, (cxx, extra) in enumerate(compilers):
-        exe = tmp_path / f"entry_plan_check_{k}"
-        subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *extra,
-                        os.path.join(ROOT, "tests", "host", "entry_plan_check.cpp"), "-o", str(exe)], check=True)
-        run = subprocess.run([str(exe)], capture_output=True, text=True)
-        lines = run.stdout.splitlines()
-        failed = [ln for ln in lines if ln.startswith("FAILED")]
-        assert run.returncode == 0 and not failed and not run.stderr, cxx + "\n" + "\n".join(failed[:20]) + "\n" + run.stderr[-4000:]
-        assert lines[-1] == "ok: 0 failed checks"
+    for cxx, lines in run_alone_under_sanitizers("entry_plan_check.cpp", tmp_path).items():
         got = {ln.split(" :", 1)[0][len("query "):]: [int(v) for v in ln.split(" :", 1)[1].split()] for ln in lines if ln.startswith("query ")}
         assert got == golden()["size_queries"], cxx
         assert {ln[len("finding "):].split(" : ")[0] for ln in lines if ln.startswith("finding ")} == KNOWN_NARROWINGS, cxx

@@ -2,23 +2,20 @@
 
 tests/lstm_ref.py against torch.nn.LSTM in float64 (outputs, final states and every gradient, 1 and 2 layers, with and without initial
 states); the mutants of that reference, each caught in both modes by the inputs the GPU tests use; the chained caps; csrc/lstm_plan.h alone
-under ASan + UBSan as a program of its own; include/tavhip_rnn.h against _lib._RNN_SIGS type by type; the other two symbol tables untouched;
-argument faults through the built library; and the pieces of LSTMClassifier that need no GPU."""
+under ASan + UBSan as a program of its own (tests/host_program.py); include/tavhip_rnn.h against its row of _lib.ABIS type by type and
+the families kept apart (tests/abi_check.py); argument faults through the built library; and the pieces of LSTMClassifier that need no GPU."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_check
 import lstm_ref as R
 import tav_amd  # noqa: F401
-import test_ctc_align_host as AH
+from host_program import run_alone_under_sanitizers
 from tav_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_NULL, ERR_SHAPE, ERR_DTYPE, ERR_ALIGN = -1, -2, -3, -4
 
 
@@ -105,69 +102,16 @@ def test_logsigmoid_reference():
 
 # ---------------------------------------------------------------------------------------------- lstm_plan.h alone
 def test_lstm_plan_header_alone_under_sanitizers(tmp_path):
-    compilers = AH._host_compilers()
-    assert compilers, "no host C++ compiler: the library was built here, so one exists"
-    for k, (cxx, extra) in enumerate(compilers):
-        exe = tmp_path / f"lstm_plan_check_{k}"
-        subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *extra,
-                        os.path.join(ROOT, "tests", "host", "lstm_plan_check.cpp"), "-o", str(exe)], check=True)
-        run = subprocess.run([str(exe)], capture_output=True, text=True)
-        lines = run.stdout.splitlines()
-        failed = [ln for ln in lines if ln.startswith("FAILED")]
-        assert run.returncode == 0 and not failed and not run.stderr, cxx + "\n" + "\n".join(failed[:20]) + "\n" + run.stderr[-4000:]
-        assert lines[-1] == "ok: 0 failed checks"
+    run_alone_under_sanitizers("lstm_plan_check.cpp", tmp_path)
 
 
 # ---------------------------------------------------------------------------------------------- header against binding
-_STRUCTS = {"tav_lstm_plan": "LstmPlan", "tav_lstm_fwd_args": "LstmFwdArgs", "tav_lstm_bwd_args": "LstmBwdArgs"}
-
-
 def test_rnn_binding_matches_its_header_type_by_type(tmp_path):
-    structs, protos = AH._parse(AH._header("tavhip_rnn.h"))
-    assert set(protos) == set(_lib._RNN_SIGS) and len(protos) == 7
-    for name, (res, args) in protos.items():
-        cres, cargs = _lib._RNN_SIGS[name]
-        assert AH._ctypes_class(cres) == res, name
-        assert len(cargs) == len(args), name
-        for k, (ct, (kind, struct)) in enumerate(zip(cargs, args)):
-            assert AH._ctypes_class(ct) == kind, f"{name}: argument {k} is {ct}, the header says {kind}"
-            if struct:
-                assert ct._type_ is getattr(_lib, _STRUCTS[struct]), f"{name}: argument {k}"
-    assert set(structs) == set(_STRUCTS)
-    for cname, pyname in _STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert [f[0] for f in cls._fields_] == [f[0] for f in structs[cname]], cname
-        for (fname, ct), (_, kind) in zip(cls._fields_, structs[cname]):
-            assert AH._ctypes_class(ct) == kind, f"{cname}.{fname}"
-    cc = next((p for p in (shutil.which(c) for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang")) if p), None)
-    assert cc is not None
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "tavhip_rnn.h"', 'int main(void) {']
-    for cname in _STRUCTS:
-        lines.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'    printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in structs[cname]]
-    lines += ['    return 0;', '}']
-    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
-    laid = dict(ln.split() for ln in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
-    for cname, pyname in _STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert C.sizeof(cls) == int(laid[cname]), cname
-        for f, _ in cls._fields_:
-            assert getattr(cls, f).offset == int(laid[f"{cname}.{f}"]), f"{cname}.{f}"
-    h = _lib.lib()
-    assert h.tav_rnn_version() == _lib.RNN_ABI_VERSION
-    for name in _lib._RNN_SIGS:
-        assert hasattr(h, name)
+    assert len(abi_check.check_binding(abi_check.abi("tavhip_rnn.h"), tmp_path)) == 7
 
 
 def test_the_other_two_symbol_tables_are_unchanged():
-    import re
-    declared = set(re.findall(r"\b(tav_[a-z0-9_]+)\s*\(", AH._header("tavhip.h")))
-    assert declared == set(_lib.declared_symbols()) == set(_lib._SIGS) and len(declared) == 92
-    assert len(_lib._ALIGN_SIGS) == 5 and declared.isdisjoint(_lib._RNN_SIGS) and set(_lib._ALIGN_SIGS).isdisjoint(_lib._RNN_SIGS)
-    assert _lib.ABI_VERSION == 7 and _lib.lib().tav_version() == 7 and _lib.ALIGN_ABI_VERSION == 1 and _lib.lib().tav_align_version() == 1
-    main = open(os.path.join(ROOT, "include", "tavhip.h")).read()
-    assert "lstm" not in main and "logsigmoid" not in main and "lstm" not in open(os.path.join(ROOT, "include", "tavhip_align.h")).read()
+    abi_check.check_families_apart()
 
 
 # ---------------------------------------------------------------------------------------------- argument faults, nothing launches
