@@ -1117,6 +1117,22 @@ class TailFn(torch.autograd.Function):
         return (d_av, dpool[1], d_aud, d_vid, None, None, None, None, None, None, *dparams, dW, db, None, None)
 
 
+class MeanPoolFn(torch.autograd.Function):
+    """mean over the S rows of every batch entry of an f32 sequence [B*S, W] -> [B, W] (torch.mean(outputs[0], dim=1) of the reference's
+    SingleModels/models/audio.py:57): every row counts, padding frames included."""
+
+    @staticmethod
+    def forward(ctx, x, B, S):
+        ctx.geom = (B, S)
+        return ops.mean_pool_fwd(_c(x), B, S)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, S = ctx.geom
+        dx, _ = ops.mean_pool_bwd(_c(g), B, S)
+        return dx, None, None
+
+
 class HeadFn(torch.autograd.Function):
     """dropout(p) -> Linear(K, N) on a [B, K] f32 feature matrix, N small (7): the classifier head of the single- and dual-modal
     models (reference SingleModels/models/text.py:61-65; models/tav.py:497-499 is the same pair inside TailFn)."""
