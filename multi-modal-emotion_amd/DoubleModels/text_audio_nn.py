@@ -1,26 +1,22 @@
 """Entrypoint of the text+audio dual path (reference DoubleModels/text_audio_nn.py, which does not run: SURVEY.md §8f row 2).
 Same main()/runModel() shape as tav_nn.py; synthetic batches of 10 s audio (160000 samples -> 499 audio frames) and 128 text tokens
 (BASELINE.json configs[3])."""
-import numpy as np
-import torch
-from torch.utils.data import DataLoader, Dataset
+from torch.utils.data import DataLoader
 
 from .. import config as C
-from .. import runtime, synthetic
+from ..train_model.classifier_loop import clip_step_epochs
+from ..utils.entrypoint import SyntheticBatches, common_params, refuse_tav_only, start, synthetic_splits
 from ..utils.global_functions import CrossEntropyLoss, Metrics, NewCrossEntropyLoss, arg_parse
 from .models.text_audio import BertAudioClassifier
-from .train_model.text_audio_training import TextAudioTrainStep, get_statistics
+from .train_model.text_audio_training import TextAudioTrainStep
 
 
-class SyntheticTextAudioBatches(Dataset):
+class SyntheticTextAudioBatches(SyntheticBatches):
     def __init__(self, cfg, n_utterances, batch_size, seed, s_text=128, t_audio=160000):
-        self.cfg, self.n, self.bs, self.seed, self.s_text, self.t_audio = cfg, max(1, n_utterances // batch_size), batch_size, seed, s_text, t_audio
-
-    def __len__(self):
-        return self.n
+        super().__init__(cfg, n_utterances, batch_size, seed, s_text=s_text, t_audio=t_audio, with_video=False)
 
     def __getitem__(self, i):
-        (tx, au, _), lab = synthetic.make_batch(self.cfg, self.bs, seed=self.seed + i, s_text=self.s_text, t_audio=self.t_audio, with_video=False)
+        (tx, au, _), lab = super().__getitem__(i)
         return [tx, au], lab
 
 
@@ -37,35 +33,19 @@ def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
     Metric = Metrics(num_classes=model_param["output_dim"], id2label=param_dict["id2label"], rank=device)
     model = BertAudioClassifier(model_param).to(device)
     step = TextAudioTrainStep(model, criterion, lr=param_dict["lr"], weight_decay=param_dict["weight_decay"], clip=param_dict["clip"])
-    for epoch in range(param_dict["epoch"]):
-        total = 0.0
-        for inp, lab in prepare_dataloader(df_train, param_dict["batch_size"], None, None):
-            loss, _ = step(inp, lab, check="train", epoch=epoch)
-            total += loss.item()
-        print(f"epoch {epoch}: train loss {total / max(1, len(df_train)):.4f}", flush=True)
-        with torch.no_grad():
-            vl = [get_statistics(i, l, model, criterion, Metric, check="val", epoch=epoch).item() for i, l in prepare_dataloader(df_val, 0, None, None)]
-        print(f"epoch {epoch}: val loss {sum(vl) / max(1, len(vl)):.4f}", flush=True)
-    return model
+    return clip_step_epochs(step, Metric, df_train, df_val, param_dict["epoch"], prepare_dataloader, param_dict["batch_size"])
 
 
 def main(argv=None):
     args = arg_parse("TextAudio", argv)
-    if args.graph:
-        raise SystemExit("--graph 1: graph mode exists for the tri-modal loop only (tav_nn); run this entrypoint with --graph 0")
-    np.random.seed(args.seed)
-    torch.random.manual_seed(args.seed)
-    C.set_default_preset(args.preset)
-    runtime.set_precision(args.dtype)
+    refuse_tav_only(args)
+    start(args, preset=True)
     cfg = C.default_config()
-    id2label = {i: f"class{i}" for i in range(args.output_dim)}
-    param_dict = {"epoch": args.epoch, "patience": args.patience, "lr": args.learning_rate, "clip": args.clip, "batch_size": args.batch_size,
-                  "weight_decay": args.weight_decay, "loss": args.loss, "epoch_switch": args.epoch_switch,
-                  "weights": torch.linspace(0.6, 0.95, args.output_dim), "id2label": id2label}
+    param_dict = common_params(args, loss=args.loss, epoch_switch=args.epoch_switch)
     model_param = {"output_dim": args.output_dim, "dropout": args.dropout}
     small = cfg["video"]["image"] != 224
     mk = lambda n, seed: SyntheticTextAudioBatches(cfg, n, args.batch_size, seed, s_text=16 if small else 128, t_audio=8000 if small else 160000)   # noqa: E731
-    return runModel("cuda", mk(args.synthetic, 1000), mk(max(args.batch_size, args.synthetic // 4), 2000), None, param_dict, model_param)
+    return runModel("cuda", *synthetic_splits(mk, args)[:2], None, param_dict, model_param)
 
 
 if __name__ == "__main__":

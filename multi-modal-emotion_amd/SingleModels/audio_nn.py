@@ -10,12 +10,11 @@ block of preset B, the wav2vec2-base the reference loads, whatever the other ent
 import math
 from argparse import ArgumentParser
 
-import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
 from .. import config as C
-from .. import runtime
+from ..utils.entrypoint import common_params, refuse_tav_only, start, synthetic_splits
 from ..utils.global_functions import CrossEntropyLoss, Metrics, arg_parse
 from .models.audio import Wav2Vec2ForSpeechClassification, collate_batch_device
 from .train_model.audio_training import evaluate_audio, train_audio_network
@@ -83,20 +82,13 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.graph:
-        raise SystemExit("--graph 1: graph mode exists for the tri-modal loop only (tav_nn); run this entrypoint with --graph 0")
-    np.random.seed(args.seed)
-    torch.random.manual_seed(args.seed)
-    runtime.set_precision(args.dtype)
-    id2label = {i: f"class{i}" for i in range(args.output_dim)}
-    param_dict = {"epoch": args.epoch, "patience": args.patience, "lr": args.learning_rate, "clip": args.clip, "batch_size": args.batch_size,
-                  "weight_decay": args.weight_decay, "model": args.model, "T_max": args.T_max, "seed": args.seed, "label_task": args.label_task,
-                  "weights": torch.linspace(0.6, 0.95, args.output_dim), "id2label": id2label, "label2id": {v: k for k, v in id2label.items()}}
+    refuse_tav_only(args)
+    start(args)
+    param_dict = common_params(args, model=args.model, T_max=args.T_max, seed=args.seed, label_task=args.label_task)
     model_param = {"input_dim": args.input_dim, "output_dim": args.output_dim, "lstm_layers": args.lstm_layers, "hidden_layers": args.hidden_layers,
                    "dropout": args.dropout, "config": C.preset(args.preset) if args.preset is not None else None}
     mk = lambda n, seed: SyntheticUtterances(n, args.audio_seconds, args.sampling_rate, args.output_dim, seed)          # noqa: E731
-    n_eval = max(args.batch_size, args.synthetic // 4)
-    return runModel("cuda", mk(args.synthetic, 1000), mk(n_eval, 2000), mk(n_eval, 3000), param_dict, model_param)
+    return runModel("cuda", *synthetic_splits(mk, args), param_dict, model_param)
 
 
 if __name__ == "__main__":

@@ -2,15 +2,15 @@
 shape and CLI flags; `--model LSTM --lstm_layers L --hidden_layers H` trains the reference's LSTMClassifier baseline (hyper_parameter_config/
 lstm.yaml), with `--synthetic` on a seeded random vector table of width H.  The reference tokenises a dataset pickle (text_nn.py:28-57); offline, batches come from synthetic.make_batch
 with the contract of its DataLoader: ({"input_ids": int64 [b,1,S], "attention_mask": float [b,S]}, labels)."""
-import numpy as np
 import torch
-from torch.utils.data import DataLoader, Dataset
+from torch.utils.data import DataLoader
 
 from .. import config as C
-from .. import runtime, synthetic
+from ..train_model.classifier_loop import clip_step_epochs
+from ..utils.entrypoint import SyntheticBatches, common_params, refuse_tav_only, start, synthetic_splits
 from ..utils.global_functions import CrossEntropyLoss, Metrics, NewCrossEntropyLoss, arg_parse
 from .models.text import BertClassifier, LSTMClassifier
-from .train_model.text_training import TextTrainStep, get_statistics
+from .train_model.text_training import TextTrainStep
 
 
 class SyntheticVectors:
@@ -20,15 +20,12 @@ class SyntheticVectors:
         self.vectors = torch.randn(vocab, width, generator=torch.Generator().manual_seed(seed)) * 0.4
 
 
-class SyntheticTextBatches(Dataset):
+class SyntheticTextBatches(SyntheticBatches):
     def __init__(self, cfg, n_utterances, batch_size, seed, s_text=128):
-        self.cfg, self.n, self.bs, self.seed, self.s_text = cfg, max(1, n_utterances // batch_size), batch_size, seed, s_text
-
-    def __len__(self):
-        return self.n
+        super().__init__(cfg, n_utterances, batch_size, seed, s_text=s_text, t_audio=400, n_visual_true=4, text_only=True)
 
     def __getitem__(self, i):
-        (tx, _, _), lab = synthetic.make_batch(self.cfg, self.bs, seed=self.seed + i, s_text=self.s_text, t_audio=400, n_visual_true=4, text_only=True)
+        (tx, _, _), lab = super().__getitem__(i)
         return {"input_ids": tx["input_ids"].unsqueeze(1), "attention_mask": tx["attention_mask"]}, lab
 
 
@@ -48,31 +45,15 @@ def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
     else:
         model = BertClassifier(model_param).to(device)
     step = TextTrainStep(model, criterion, lr=param_dict["lr"], weight_decay=param_dict["weight_decay"], clip=param_dict["clip"])
-    for epoch in range(param_dict["epoch"]):
-        total = 0.0
-        for inp, lab in prepare_dataloader(df_train, param_dict["batch_size"], None, None):
-            loss, _ = step(inp, lab, check="train", epoch=epoch)
-            total += loss.item()
-        print(f"epoch {epoch}: train loss {total / max(1, len(df_train)):.4f}", flush=True)
-        with torch.no_grad():
-            vl = [get_statistics(i, l, model, criterion, Metric, check="val", epoch=epoch).item() for i, l in prepare_dataloader(df_val, 0, None, None)]
-        print(f"epoch {epoch}: val loss {sum(vl) / max(1, len(vl)):.4f}", flush=True)
-    return model
+    return clip_step_epochs(step, Metric, df_train, df_val, param_dict["epoch"], prepare_dataloader, param_dict["batch_size"])
 
 
 def main(argv=None):
     args = arg_parse("Text", argv)
-    if args.graph:
-        raise SystemExit("--graph 1: graph mode exists for the tri-modal loop only (tav_nn); run this entrypoint with --graph 0")
-    np.random.seed(args.seed)
-    torch.random.manual_seed(args.seed)
-    C.set_default_preset(args.preset)
-    runtime.set_precision(args.dtype)
+    refuse_tav_only(args)
+    start(args, preset=True)
     cfg = C.default_config()
-    id2label = {i: f"class{i}" for i in range(args.output_dim)}
-    param_dict = {"epoch": args.epoch, "patience": args.patience, "lr": args.learning_rate, "clip": args.clip, "batch_size": args.batch_size,
-                  "weight_decay": args.weight_decay, "loss": args.loss, "epoch_switch": args.epoch_switch,
-                  "weights": torch.linspace(0.6, 0.95, args.output_dim), "id2label": id2label}
+    param_dict = common_params(args, loss=args.loss, epoch_switch=args.epoch_switch)
     model_param = {"output_dim": args.output_dim, "dropout": args.dropout}
     s_text = 128
     if args.model == "LSTM":
@@ -81,7 +62,7 @@ def main(argv=None):
                            glove_vec=SyntheticVectors(cfg["text"]["vocab"], _first_hidden(args.hidden_layers), args.seed))
         s_text = 70                                                            # the reference pads every utterance to 70 tokens for this model
     mk = lambda n, seed: SyntheticTextBatches(cfg, n, args.batch_size, seed, s_text)   # noqa: E731
-    return runModel("cuda", mk(args.synthetic, 1000), mk(max(args.batch_size, args.synthetic // 4), 2000), None, param_dict, model_param)
+    return runModel("cuda", *synthetic_splits(mk, args)[:2], None, param_dict, model_param)
 
 
 if __name__ == "__main__":

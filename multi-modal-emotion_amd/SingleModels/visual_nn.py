@@ -12,8 +12,9 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from .. import ops, runtime
+from .. import ops
 from ..models.tav import subsample_indices
+from ..utils.entrypoint import common_params, refuse_tav_only, start, synthetic_splits
 from ..utils.global_functions import CrossEntropyLoss, Metrics, arg_parse
 from .models.visual import ResNet50Classification, VisualClassification, hidden_layer_list
 from .train_model.visual_training import evaluate_visual, visual_train
@@ -84,20 +85,13 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.graph:
-        raise SystemExit("--graph 1: graph mode exists for the tri-modal loop only (tav_nn); run this entrypoint with --graph 0")
-    np.random.seed(args.seed)
-    torch.random.manual_seed(args.seed)
-    runtime.set_precision(args.dtype)
-    id2label = {i: f"class{i}" for i in range(args.output_dim)}
-    param_dict = {"epoch": args.epoch, "patience": args.patience, "lr": args.learning_rate, "clip": args.clip, "batch_size": args.batch_size,
-                  "weight_decay": args.weight_decay, "model": args.model, "T_max": args.T_max, "seed": args.seed,
-                  "weights": torch.linspace(0.6, 0.95, args.output_dim), "id2label": id2label, "label2id": {v: k for k, v in id2label.items()}}
+    refuse_tav_only(args)
+    start(args)
+    param_dict = common_params(args, model=args.model, T_max=args.T_max, seed=args.seed)
     model_param = {"input_dim": 3, "output_dim": args.output_dim, "lstm_layers": args.lstm_layers,
                    "hidden_layers": hidden_layer_list(args.hidden_layers), "clip_shape": args.clip_shape}
     mk = lambda n, seed: SyntheticClips(n, args.clip_shape, args.output_dim, seed)          # noqa: E731
-    n_eval = max(args.batch_size, args.synthetic // 4)
-    return runModel("cuda", mk(args.synthetic, 1000), mk(n_eval, 2000), mk(n_eval, 3000), param_dict, model_param)
+    return runModel("cuda", *synthetic_splits(mk, args), param_dict, model_param)
 
 
 if __name__ == "__main__":

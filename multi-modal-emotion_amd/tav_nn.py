@@ -2,32 +2,29 @@
 shape and the same CLI flags (utils/global_functions.arg_parse).  The reference reads a dataset pickle + mp4/wav files and a
 wandb sweep config (tav_nn.py:116-188); offline there is neither, so utterances come from synthetic.make_batch with the
 contract of collate_batch."""
-import numpy as np
 import torch
-from torch.utils.data import DataLoader, Dataset
+from torch.utils.data import DataLoader
 
 from . import config as C
-from . import runtime, synthetic
+from . import runtime
 from .models.tav import PreFormer, TAVForMAE
 from .train_model.tav_train import evaluate_tav, train_tav_network
+from .utils.entrypoint import SyntheticBatches, common_params, start, synthetic_splits
 from .utils.global_functions import CrossEntropyLoss, Metrics, NewCrossEntropyLoss, arg_parse
 
 
-class SyntheticTAVBatches(Dataset):
+class SyntheticTAVBatches(SyntheticBatches):
     """Each item is one already-collated batch (the reference's DataLoader yields ([text, audio, visual], labels))."""
 
     def __init__(self, cfg, n_utterances, batch_size, seed, s_text=70, t_audio=80000):
-        self.cfg, self.n, self.bs, self.seed, self.s_text, self.t_audio = cfg, max(1, n_utterances // batch_size), batch_size, seed, s_text, t_audio
-
-    def __len__(self):
-        return self.n
+        super().__init__(cfg, n_utterances, batch_size, seed, s_text=s_text, t_audio=t_audio)
 
     def __getitem__(self, i):
         nv = 104 if self.cfg["video"]["image"] == 224 else 4
         if runtime.visual_rows() == "ragged":     # unequal rows around the same mean (a seeded spread of +-2 tokens)
             g = torch.Generator().manual_seed(self.seed + i)
             nv = [nv + int(d) for d in torch.randint(-2, 3, (self.bs,), generator=g)]
-        return synthetic.make_batch(self.cfg, self.bs, seed=self.seed + i, s_text=self.s_text, t_audio=self.t_audio, n_visual_true=nv)
+        return super().__getitem__(i, n_visual_true=nv)
 
 
 def prepare_dataloader(df, batch_size, label_task, epoch_switch, pin_memory=True, num_workers=0, check="train"):
@@ -59,27 +56,20 @@ def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
 
 def main(argv=None):
     args = arg_parse("TAV", argv)
-    np.random.seed(args.seed)
-    torch.random.manual_seed(args.seed)
-    C.set_default_preset(args.preset)
-    runtime.set_precision(args.dtype)
+    start(args, preset=True)
     runtime.set_visual_rows(args.visual_rows, bucket=args.visual_bucket)
     runtime.set_specaugment(args.specaugment)
     cfg = C.default_config()
-    weights = torch.linspace(0.6, 0.95, args.output_dim)            # reference: 1 - class frequency (tav_nn.py:171)
-    id2label = {i: f"class{i}" for i in range(args.output_dim)}
-    param_dict = {"epoch": args.epoch, "patience": args.patience, "lr": args.learning_rate, "clip": args.clip, "batch_size": args.batch_size,
-                  "weight_decay": args.weight_decay, "model": args.model, "T_max": args.T_max, "seed": args.seed, "label_task": args.label_task,
-                  "mask": args.mask, "loss": args.loss, "beta": args.beta, "epoch_switch": args.epoch_switch, "weights": weights,
-                  "label2id": {v: k for k, v in id2label.items()}, "id2label": id2label, "graph": args.graph, "loop_sync": args.loop_sync,
-                  "encoder_lr_scale": args.encoder_lr_scale, "no_decay_norm_bias": args.no_decay_norm_bias}
+    param_dict = common_params(args, model=args.model, T_max=args.T_max, seed=args.seed, label_task=args.label_task, mask=args.mask, loss=args.loss,
+                               beta=args.beta, epoch_switch=args.epoch_switch)
+    param_dict.update(graph=args.graph, loop_sync=args.loop_sync, encoder_lr_scale=args.encoder_lr_scale,      # last in the dict printed below
+                      no_decay_norm_bias=args.no_decay_norm_bias)
     model_param = {"output_dim": args.output_dim, "dropout": args.dropout, "early_div": args.early_div, "num_layers": args.num_layers,
                    "learn_PosEmbeddings": args.learn_PosEmbeddings}
     small = cfg["video"]["image"] != 224
     mk = lambda n, seed: SyntheticTAVBatches(cfg, n, args.batch_size, seed, s_text=16 if small else 70, t_audio=8000 if small else 80000)   # noqa: E731
     print(f" in main \n param_dict = { {k: v for k, v in param_dict.items() if k != 'weights'} } \n model_param = {model_param} \n synthetic utterances = {args.synthetic}")
-    return runModel("cuda", mk(args.synthetic, 1000), mk(max(args.batch_size, args.synthetic // 4), 2000), mk(max(args.batch_size, args.synthetic // 4), 3000),
-                    param_dict, model_param)
+    return runModel("cuda", *synthetic_splits(mk, args), param_dict, model_param)
 
 
 if __name__ == "__main__":
