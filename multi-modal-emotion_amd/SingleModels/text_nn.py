@@ -7,8 +7,8 @@ from torch.utils.data import DataLoader
 
 from .. import config as C
 from ..train_model.classifier_loop import clip_step_epochs
-from ..utils.entrypoint import SyntheticBatches, common_params, refuse_tav_only, start, synthetic_splits
-from ..utils.global_functions import CrossEntropyLoss, Metrics, NewCrossEntropyLoss, arg_parse
+from ..utils.entrypoint import SyntheticBatches, build_criterion, common_params, refuse_tav_only, start, synthetic_splits
+from ..utils.global_functions import Metrics, arg_parse
 from .models.text import BertClassifier, LSTMClassifier
 from .train_model.text_training import TextTrainStep
 
@@ -35,10 +35,7 @@ def prepare_dataloader(df, batch_size, label_task, epoch_switch, pin_memory=True
 
 def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
     device = accelerator
-    if param_dict["loss"] == "CrossEntropy":
-        criterion = CrossEntropyLoss()
-    else:
-        criterion = NewCrossEntropyLoss(class_weights=param_dict["weights"].to(device), epoch_switch=param_dict["epoch_switch"])
+    criterion = build_criterion(param_dict, model_param["output_dim"], device)
     Metric = Metrics(num_classes=model_param["output_dim"], id2label=param_dict["id2label"], rank=device)
     if model_param.get("model") == "LSTM":
         model = LSTMClassifier(model_param["glove_vec"], model_param).to(device)
@@ -53,7 +50,7 @@ def main(argv=None):
     refuse_tav_only(args)
     start(args, preset=True)
     cfg = C.default_config()
-    param_dict = common_params(args, loss=args.loss, epoch_switch=args.epoch_switch)
+    param_dict = common_params(args, loss=args.loss, beta=args.beta, epoch_switch=args.epoch_switch)
     model_param = {"output_dim": args.output_dim, "dropout": args.dropout}
     s_text = 128
     if args.model == "LSTM":

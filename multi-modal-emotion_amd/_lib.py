@@ -286,7 +286,7 @@ _CONV_SIGS = {
 class Abi(NamedTuple):
     """One public header and its binding.  `version` is the constant as it stood at import, for readers of the table; lib() reads the
     constant named `version_const` when it is called, so that a changed constant is what the loaded library is held to."""
-    header: str            # file name under include/
+    header: str            # file name under include/ (under csrc/ for a row of PRIVATE_ABIS)
     version_fn: str        # the exported function that returns the library's version of this family
     version_const: str     # the module constant of this file that holds the binding's version
     version: int
@@ -309,7 +309,33 @@ ABIS = (
          "tav_flat_linear_fwd_args": FlatLinearFwdArgs, "tav_flat_linear_bwd_args": FlatLinearBwdArgs}, "convolution"),
 )
 
+# Package-private entry points: declared in a header next to the sources (csrc/), bound and version-checked by lib() like the public
+# rows, but not part of the recorded public tables.  A change that re-records those tables promotes such a header to include/ and its
+# row to ABIS.
+# csrc/tavhip_loss.h: the soft F-beta / soft precision loss.
+LOSS_ABI_VERSION = 1
+SOFT_F_FBETA, SOFT_F_PRECISION = 0, 1
+
+
+class SoftFArgs(C.Structure):
+    _fields_ = [("logits", vp), ("target", vp), ("weight", vp), ("loss", vp), ("dlogits", vp), ("stats", vp), ("B", i64), ("C", i64), ("ld", i64),
+                ("beta", C.c_double), ("eps", C.c_double), ("grad_scale", f32), ("mode", i32)]
+
+
+_LOSS_SIGS = {
+    "tav_loss_version": (C.c_int, []),
+    "tav_soft_f_loss": (C.c_int, [C.POINTER(SoftFArgs), vp]),
+}
+
+PRIVATE_ABIS = (
+    Abi("tavhip_loss.h", "tav_loss_version", "LOSS_ABI_VERSION", LOSS_ABI_VERSION, _LOSS_SIGS, {"tav_soft_f_args": SoftFArgs}, "loss"),
+)
+
 _lib = None
+
+
+def _header_path(abi):
+    return ("csrc/" if abi in PRIVATE_ABIS else "include/") + abi.header
 
 
 def lib():
@@ -321,13 +347,13 @@ def lib():
                 f"{LIB_PATH} is missing: the TAV hot path has no fallback. Build it with "
                 "`make -C multi-modal-emotion_amd/csrc` (hipcc --offload-arch=gfx950).")
         h = C.CDLL(LIB_PATH)
-        for abi in ABIS:
+        for abi in ABIS + PRIVATE_ABIS:
             for name, (res, args) in abi.sigs.items():
                 fn = getattr(h, name, None)
                 if fn is None:
-                    raise RuntimeError(f"{LIB_PATH} does not export {name}, which include/{abi.header} declares; rebuild")
+                    raise RuntimeError(f"{LIB_PATH} does not export {name}, which {_header_path(abi)} declares; rebuild")
                 fn.restype, fn.argtypes = res, args
-        for abi in ABIS:
+        for abi in ABIS + PRIVATE_ABIS:
             got, want = getattr(h, abi.version_fn)(), globals()[abi.version_const]
             if got != want:
                 raise RuntimeError(f"libtavhip {abi.what + ' ' if abi.what else ''}ABI {got} != binding {want}; rebuild")

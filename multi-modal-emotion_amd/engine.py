@@ -1229,6 +1229,21 @@ class CrossEntropyFn(torch.autograd.Function):
         return dlog * g, None, None
 
 
+class SoftFLossFn(torch.autograd.Function):
+    """Soft F-beta / soft precision loss of the batch (utils/global_functions.FBetaLoss, PrecisionLoss): 1 - sum_k w_k clamp(F_k)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, beta, mode, eps):
+        loss, dlog = ops.soft_f_loss(_c(logits), target, weight, beta, mode, eps)
+        ctx.save_for_backward(dlog)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlog,) = ctx.saved_tensors
+        return dlog * g, None, None, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------- TransformerBlock (alt. fusion stack)
 class TransformerBlockFn(torch.autograd.Function):
     """One block of the reference's TransformerEncoder (utils/TAVFormer.py:93-142 with MultiHeadAttention :10-90):

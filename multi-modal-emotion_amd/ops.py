@@ -6,6 +6,7 @@ No arithmetic happens here; torch is used for device memory and streams only.  S
 import collections
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import torch
@@ -931,6 +932,35 @@ def cross_entropy(logits, target, class_weight=None, grad_scale=1.0, want_grad=T
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     dlog = torch.empty_like(logits) if want_grad else None
     check(lib().tav_cross_entropy(ptr(logits), ptr(target), ptr(class_weight), ptr(loss), ptr(dlog), B, Cn, grad_scale, stream()), "cross_entropy")
+    return loss, dlog
+
+
+SOFT_F_MODES = {"FBeta": L.SOFT_F_FBETA, "Precision": L.SOFT_F_PRECISION}
+_DEBUG_CHECKS = os.environ.get("TAV_DEBUG_CHECKS", "0") == "1"      # host-synchronising input checks on the sync-free paths
+
+
+def soft_f_loss(logits, target, weight, beta, mode, eps=1e-7, grad_scale=1.0, want_grad=True, want_loss=True, stats=None):
+    """One launch of tav_soft_f_loss on the current stream -> (loss [1], dlogits [B, C]); either is None when not wanted.  logits f32
+    [B, C] with unit column stride (any row pitch >= C), target int64 [B], weight f32 [C] or None, mode "FBeta" / "Precision"; stats, if
+    given, is a contiguous f32 [3, C] tensor that receives tp, fp, fn.  A target outside [0, C) belongs to no class (its row counts as a
+    false positive of every class); with TAV_DEBUG_CHECKS=1 it raises instead, as F.one_hot would -- that check reads the targets back."""
+    if mode not in SOFT_F_MODES:
+        raise ValueError(f"soft_f_loss: mode must be one of {sorted(SOFT_F_MODES)}, got {mode!r}")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or target.dtype != torch.int64 or not target.is_contiguous():
+        raise ValueError(f"soft_f_loss: logits must be f32 [B, C] with unit column stride and target contiguous int64, got {logits.dtype} "
+                         f"{tuple(logits.shape)} strides {tuple(logits.stride())}, {target.dtype}")
+    B, Cn = logits.shape
+    if target.numel() != B or (weight is not None and (weight.dtype != torch.float32 or weight.numel() != Cn or not weight.is_contiguous())):
+        raise ValueError(f"soft_f_loss: {B} rows of {Cn} classes need {B} targets and a contiguous f32 weight of {Cn} elements")
+    if stats is not None and (stats.dtype != torch.float32 or stats.numel() != 3 * Cn or not stats.is_contiguous()):
+        raise ValueError(f"soft_f_loss: stats must be a contiguous f32 tensor of 3 x {Cn} elements")
+    if _DEBUG_CHECKS and bool(((target < 0) | (target >= Cn)).any()):
+        raise ValueError(f"soft_f_loss: a target lies outside [0, {Cn})")
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device) if want_loss else None
+    dlog = torch.empty(B, Cn, dtype=torch.float32, device=logits.device) if want_grad else None
+    a = L.SoftFArgs(ptr(logits), ptr(target), ptr(weight), ptr(loss), ptr(dlog), ptr(stats), B, Cn, logits.stride(0) if B > 1 else Cn,
+                    float(beta), float(eps), float(grad_scale), SOFT_F_MODES[mode])
+    check(lib().tav_soft_f_loss(C.byref(a), stream()), "soft_f_loss")
     return loss, dlog
 
 

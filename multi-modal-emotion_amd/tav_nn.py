@@ -9,8 +9,8 @@ from . import config as C
 from . import runtime
 from .models.tav import PreFormer, TAVForMAE
 from .train_model.tav_train import evaluate_tav, train_tav_network
-from .utils.entrypoint import SyntheticBatches, common_params, start, synthetic_splits
-from .utils.global_functions import CrossEntropyLoss, Metrics, NewCrossEntropyLoss, arg_parse
+from .utils.entrypoint import SyntheticBatches, build_criterion, common_params, start, synthetic_splits
+from .utils.global_functions import Metrics, arg_parse
 
 
 class SyntheticTAVBatches(SyntheticBatches):
@@ -34,10 +34,7 @@ def prepare_dataloader(df, batch_size, label_task, epoch_switch, pin_memory=True
 
 def runModel(accelerator, df_train, df_val, df_test, param_dict, model_param):
     device = accelerator
-    if param_dict["loss"] == "CrossEntropy":
-        criterion = CrossEntropyLoss()
-    else:
-        criterion = NewCrossEntropyLoss(class_weights=param_dict["weights"].to(device), epoch_switch=param_dict["epoch_switch"])
+    criterion = build_criterion(param_dict, model_param["output_dim"], device)
     sync = param_dict.get("loop_sync", "step")
     Metric = Metrics(num_classes=model_param["output_dim"], id2label=param_dict["id2label"], rank=device, on_device=sync == "log")
     bs, lt, es = param_dict["batch_size"], param_dict["label_task"], param_dict["epoch_switch"]

@@ -1,11 +1,12 @@
 """What the main() of every entry point (tav_nn.py, SingleModels/*_nn.py, DoubleModels/text_audio_nn.py) does before it builds a model: seeding and
-precision, the common param_dict, the seeded synthetic splits, the refusal of flags only tav_nn implements; and the dataset of collated batches."""
+precision, the common param_dict, the criterion of --loss, the seeded synthetic splits, the refusal of flags only tav_nn implements; and the dataset of collated batches."""
 import numpy as np
 import torch
 from torch.utils.data import Dataset
 
 from .. import config as C
 from .. import runtime, synthetic
+from .global_functions import CrossEntropyLoss, FBetaLoss, NewCrossEntropyLoss, PrecisionLoss
 
 # flags of utils.global_functions.arg_parse that only tav_nn implements: (attribute, flag, default, what it selects)
 TAV_ONLY = (("graph", "--graph", 0, "graph mode"), ("loop_sync", "--loop-sync", "step", "the loop without per-step host reads"),
@@ -29,6 +30,20 @@ def common_params(args, **own):
     return {"epoch": args.epoch, "patience": args.patience, "lr": args.learning_rate, "clip": args.clip, "batch_size": args.batch_size,
             "weight_decay": args.weight_decay, **own, "weights": torch.linspace(0.6, 0.95, args.output_dim),     # reference: 1 - class frequency (tav_nn.py:171)
             "label2id": {v: k for k, v in id2label.items()}, "id2label": id2label}
+
+
+def build_criterion(param_dict, output_dim, device):
+    """The training criterion of --loss (reference tav_nn.py:85-98): "CrossEntropy" -> CrossEntropyLoss(), "FBeta" ->
+    FBetaLoss(num_classes, beta=--beta), "Precision" -> PrecisionLoss(num_classes), every other name -> NewCrossEntropyLoss on the class
+    weights with --epoch_switch."""
+    name = param_dict["loss"]
+    if name == "CrossEntropy":
+        return CrossEntropyLoss()
+    if name == "FBeta":
+        return FBetaLoss(num_classes=output_dim, beta=param_dict["beta"])
+    if name == "Precision":
+        return PrecisionLoss(num_classes=output_dim)
+    return NewCrossEntropyLoss(class_weights=param_dict["weights"].to(device), epoch_switch=param_dict["epoch_switch"])
 
 
 def synthetic_splits(mk, args):

@@ -1,6 +1,8 @@
 """Drop-in for the parts of the reference's utils/global_functions.py that the TAV path touches:
 NewCrossEntropyLoss (:51-83), MySampler (:21-49), arg_parse (:260-297, same flag names) and a dependency-free Metrics
-(the reference wraps torchmetrics, :114-188, which is outside the hot path and not installed here)."""
+(the reference wraps torchmetrics, :114-188, which is outside the hot path and not installed here); FBetaLoss and PrecisionLoss, which
+the reference's tav_nn.py imports from that file (:92-98) and whose surviving definition is the soft F1 of notebooks/loss.ipynb."""
+import math
 import os
 from argparse import ArgumentParser, ArgumentTypeError
 
@@ -61,6 +63,49 @@ class NewCrossEntropyLoss(nn.Module):
         if epoch % self.epoch_switch == 0:
             return self.normalCEL(logits, target)
         return self.weightedCEL(logits, target)
+
+
+class _SoftFLoss(nn.Module):
+    """1 - sum_k w_k clamp(F_k, epsilon, 1 - epsilon) over the soft per-class counts of the batch, on libtavhip (ops.soft_f_loss): one
+    launch, no host read.  weights: None (every class 1), a number, or one value per class."""
+    mode = None
+
+    def __init__(self, num_classes, beta=1.0, weights=None, epsilon=1e-7):
+        super().__init__()
+        beta, epsilon = float(beta), float(epsilon)
+        if not (math.isfinite(beta) and beta > 0):
+            raise ValueError(f"{type(self).__name__}: beta must be finite and > 0, got {beta}")
+        if not (math.isfinite(epsilon) and 0 < epsilon < 0.5):
+            raise ValueError(f"{type(self).__name__}: epsilon must lie in (0, 0.5), got {epsilon}")
+        if not 1 <= int(num_classes) <= 16:
+            raise ValueError(f"{type(self).__name__}: 1..16 classes, got {num_classes}")
+        self.num_classes, self.beta, self.epsilon = int(num_classes), beta, epsilon
+        if weights is not None:
+            weights = torch.as_tensor(weights, dtype=torch.float32).detach()
+            weights = weights.expand(self.num_classes).contiguous() if weights.dim() == 0 else weights.reshape(-1).contiguous()
+            if weights.numel() != self.num_classes:
+                raise ValueError(f"{type(self).__name__}: {weights.numel()} weights for {self.num_classes} classes")
+        self.weights = weights
+
+    def forward(self, logits, target, epoch=None):
+        if logits.dim() != 2 or logits.shape[1] != self.num_classes:
+            raise ValueError(f"{type(self).__name__}: logits {tuple(logits.shape)} for {self.num_classes} classes")
+        if self.weights is not None and self.weights.device != logits.device:
+            self.weights = self.weights.to(logits.device)             # once: later calls (and graph captures) copy nothing
+        return E.SoftFLossFn.apply(logits, target.to(logits.device).long(), self.weights, self.beta, self.mode, self.epsilon)
+
+
+class FBetaLoss(_SoftFLoss):
+    """Soft F-beta loss (reference tav_nn.py:97 `FBetaLoss(num_classes=, beta=)`); beta = 1 is notebooks/loss.ipynb's F1_Loss."""
+    mode = "FBeta"
+
+
+class PrecisionLoss(_SoftFLoss):
+    """Soft precision loss (reference tav_nn.py:93 `PrecisionLoss(num_classes=)`): F_k = P_k."""
+    mode = "Precision"
+
+    def __init__(self, num_classes, weights=None, epsilon=1e-7):
+        super().__init__(num_classes, 1.0, weights, epsilon)
 
 
 def _run_names():
